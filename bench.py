@@ -1,6 +1,11 @@
 """Benchmark of the aggregation hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2] [--e2e]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2] [--dump-outputs DIR] [--full [--e2e]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``--dump-outputs``:
+the last timed step's result as ``DIR/<name>.npy`` first). ``--full`` adds, after the timed
+region, the check against the oracle, the host-resident end-to-end leg, the traffic record, the
+drop-in surface and the CPU baseline.
 
 ``--gpus N`` > 1 works bare (this process spawns N ranks through a
 ``torch.distributed.run`` child and forwards rank 0's JSON line) or under an
@@ -21,7 +26,7 @@ value = K*P*4 bytes of client deltas / wall time of the K timed steps (max over
 ranks). roofline.achieved = the same algorithmic bytes per fold launch / the
 launch's mean duration from HIP events on the launch stream. cpu_baseline =
 the oracle's C restatement of the reference op sequence (oracle/fold_ref.c,
-``oracle_tree_mean_refseq_f32``) on a bounded sample, rank 0, N = 1 only.
+``oracle_tree_mean_refseq_f32``) on a bounded sample, rank 0, N = 1 and ``--full`` only.
 """
 
 from __future__ import annotations
@@ -627,11 +632,14 @@ def spawn_ranks(nproc: int, argv, script: str = None, timeout: float = None) -> 
     else:  # a script that does not write FJ_BENCH_JSON: rank 0's JSON object on the shared pipe
         lines = []
         for ln in out.decode(errors="replace").splitlines():
-            i = ln.find('{"')  # another rank's unterminated banner can precede the JSON
+            # another rank's unterminated banner can precede the JSON, and another rank's output
+            # can follow it on the same line (an unbuffered rank writes the object and its
+            # newline in two calls: whatever lands between them joins the line)
+            i = ln.find('{"')
             if i >= 0:
                 try:
-                    json.loads(ln[i:])
-                    lines.append(ln[i:])
+                    _, end = json.JSONDecoder().raw_decode(ln[i:])
+                    lines.append(ln[i:i + end])
                 except ValueError:
                     pass
     if len(lines) != 1:
@@ -685,7 +693,7 @@ def measure_traffic(workload, dst=None):
 
     out = tempfile.mkdtemp(prefix="fj_pmc_")
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-dropin"]
+           "--full", "--no-cpu-baseline", "--no-dropin"]
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         log(f"[bench] PMC pass {counter}")
         subprocess.run(["rocprofv3", "--pmc", counter, "-d", os.path.join(out, counter), "-o", "run",
@@ -771,12 +779,41 @@ def host_resident_rate(x, w_local, sharded_step, out, scale, nt, dev, rank, shar
                         "bytes = all clients' deltas; max over ranks"}
 
 
+# --dump-outputs: bytes the files of one run may take together
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every (name, tensor) of ``arrays`` as ``dirname/<name>.npy`` in float32
+    (bf16 widens exactly), in the tensor's own shape. The files share DUMP_MAX_BYTES in equal
+    parts; an output above its part is written as a 1-D sample of its flattened elements, at the
+    sorted distinct indices RandomState(0) draws for that element count: the same elements in
+    every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) // 4 - 64  # float32 elements per file, less the .npy header
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, t.numel(), size=share))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the check of the "
+                         "timed result against the oracle, the host-resident end-to-end leg, the PMC traffic record, "
+                         "the drop-in surface sub-record and the CPU baseline (each still has its --no-... switch). "
+                         "A plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the arrays its caller "
+                         "receives) as DIR/<name>.npy in float32; an output above the size budget is written as a "
+                         "fixed, seeded sample of its elements")
     ap.add_argument("--candidate-deadline", type=float, default=60.0,
                     help="host seconds one exchange auto-tune measurement may take before the library's own "
                          "communicator is aborted and its candidates dropped (torch-engine candidates run first)")
@@ -829,6 +866,8 @@ def main():
                     help="upload the weights each step (pinned H2D in front of the fold) instead of passing "
                          "them in the kernel arguments (A/B of FJAGG_HOST_TABLES)")
     args = ap.parse_args()
+    if args.measure_traffic and not args.full:
+        raise SystemExit("--measure-traffic runs rocprofv3 passes of its own: it goes with --full")
     if args.single_process:
         return single_process(args)
     if args.reference_bf16 and (WORKLOADS[args.workload][2] != torch.bfloat16 or args.gpus > 1 or args.with_norms):
@@ -1082,9 +1121,20 @@ def main():
     mean_kernel_s = float(np.mean(kernel_ms)) / 1e3
     achieved = bytes_per_launch / mean_kernel_s / 1e9
 
+    if rank == 0 and args.dump_outputs:  # what the last timed step left its caller
+        phase(rank, "dump the outputs of the last timed step")
+        if args.server != "none":
+            dumped = [("server_params", sparams)] + [("server_state_" + k, sstate[k]) for k in ("m", "v")
+                                                     if k in sstate]
+        else:
+            dumped = [("mean" if nshard == world else "partial", final if final is not None else out)]
+            if args.with_norms:
+                dumped.append(("l2sq", l2sq))
+        dump_outputs(args.dump_outputs, dumped)
+
     # the timed result against the oracle (rank 0, after the timed region)
     check, check_detail = None, None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         if args.server != "none":
             check_detail = {"skipped": "the fused server step writes params, not the mean"}
         else:
@@ -1099,7 +1149,7 @@ def main():
             log(f"[bench rank 0] check: {check} {check_detail}")
 
     e2e = None
-    if not args.no_e2e and args.server == "none" and not args.with_norms:
+    if args.full and not args.no_e2e and args.server == "none" and not args.with_norms:
         phase(rank, "e2e: host-resident deltas (pinned H2D + fold [+ reduce] + D2H)")
         ns = Kl if (sharded or args.e2e) else min(Kl, E2E_SAMPLE_CLIENTS)
         e2e = host_resident_rate(x[:ns], w_local, step if sharded else None, out, scale, nt, dev, rank, sharded,
@@ -1109,8 +1159,8 @@ def main():
                                  if ns < Kl else f"all {Kl} clients ({ns * P * esize / 1e9:.2f} GB)")
 
     traffic = (None, None)
-    if rank == 0 and not sharded and not args.with_norms and args.server == "none" and not args.variant \
-            and not args.clients:
+    if args.full and rank == 0 and not sharded and not args.with_norms and args.server == "none" \
+            and not args.variant and not args.clients:
         traffic = (measure_traffic(args.workload, args.traffic_out or None) if args.measure_traffic
                    else load_traffic(args.workload))
     if rank == 0:
@@ -1163,10 +1213,10 @@ def main():
             res.update(e2e)
         if nshard != world:
             res["rehearsal_projected_whole_job_GBs"] = round(value * nshard, 2)
-        if (not sharded and not args.no_dropin and args.workload == "c3" and not args.clients
+        if (args.full and not sharded and not args.no_dropin and args.workload == "c3" and not args.clients
                 and args.server == "none" and not args.with_norms):
             res["drop_in"] = dropin_surface(dev)
-        if not sharded and not args.no_cpu_baseline and dtype == torch.float32:
+        if args.full and not sharded and not args.no_cpu_baseline and dtype == torch.float32:
             res["cpu_baseline"] = cpu_baseline(K)
         emit_json(json_fd, res)
     if comm is not None:
@@ -1233,8 +1283,10 @@ def single_process(args):
     sync()
     elapsed = time.perf_counter() - t0
     comm.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("mean", outs[0])])
     check, check_detail = None, None
-    if not args.no_check:  # device 0's mean over all K clients vs the oracle, after the timed region
+    if args.full and not args.no_check:  # device 0's mean over all K clients vs the oracle, after the timed region
         check, check_detail = check_result(outs[0], K=K, P=P, k0=0, k1=K, weights=weights, W=W, dtype=dtype,
                                            exact=False, nranks=N,
                                            edges=[p0 for p0, _ in fd.bucket_edges(P, buckets)[1:]])

@@ -62,6 +62,19 @@ def test_spawn_finds_json_after_unterminated_banner(tmp_path, capfd):
     assert out.strip() == '{"n_gpus": 1}'
 
 
+def test_spawn_finds_json_before_another_ranks_output(tmp_path, capfd):
+    """An unbuffered rank (python -u, PYTHONUNBUFFERED) writes its JSON object and the
+    newline after it in two calls, and another rank's banner can land between the two; the
+    launcher still forwards exactly the JSON."""
+    p = tmp_path / "rank.py"
+    p.write_text("import json, sys\nsys.stdout.write(json.dumps({'n_gpus': 1}))\n"
+                 "sys.stdout.write('rank 1 banner on stdout\\n')\n")
+    rc = bench.spawn_ranks(1, [], script=str(p), timeout=120)
+    out = capfd.readouterr().out
+    assert rc == 0
+    assert out.strip() == '{"n_gpus": 1}'
+
+
 def test_spawn_propagates_rank_failure(rank_script, capfd):
     rc = bench.spawn_ranks(2, ["1"], script=rank_script, timeout=180)
     assert rc != 0

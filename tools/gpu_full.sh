@@ -10,10 +10,10 @@ run gpu-tests 900 1 bash -c "python -u -m pytest tests -q -m gpu -rfs --timeout 
 tail -2 $OUT/${TAG}_gpu_tests.log
 run smoke 300 0 bash -c "python -c 'import __graft_entry__ as g; g.smoke()' > $OUT/${TAG}_smoke.log 2>&1"
 tail -1 $OUT/${TAG}_smoke.log
-run bench 600 0 bash -c "python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err"
+run bench 600 0 bash -c "python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err"
 cat $OUT/${TAG}_bench.json
-run rocprof 600 0 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run --output-format csv -- python bench.py --no-cpu-baseline
+run rocprof 600 0 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run --output-format csv -- python bench.py --full --no-cpu-baseline
 cat $OUT/${TAG}_prof/run_kernel_stats.csv
-run pmc-fetch 600 0 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}_pmc_fetch -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-run pmc-write 600 0 rocprofv3 --pmc WRITE_SIZE -d $OUT/${TAG}_pmc_write -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+run pmc-fetch 600 0 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}_pmc_fetch -o run --output-format csv -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+run pmc-write 600 0 rocprofv3 --pmc WRITE_SIZE -d $OUT/${TAG}_pmc_write -o run --output-format csv -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 run traffic 60 0 python tools/pmc_summary.py $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write $OUT/${TAG}_traffic_c3.json

@@ -18,7 +18,7 @@ for v in new old; do
   timeout -s KILL 200 rocprofv3 --kernel-trace --stats -d "$O/$v/loop" -o run --output-format csv -- \
     python tools/time_norms_loop.py 10 > "$O/$v/loop.json" 2> "$O/$v/loop.err" || exit $?
   timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d "$O/$v/dense" -o run --output-format csv -- \
-    python bench.py --with-norms --no-cpu-baseline --no-dropin > "$O/$v/dense.json" 2> "$O/$v/dense.err" || exit $?
+    python bench.py --full --with-norms --no-cpu-baseline --no-dropin > "$O/$v/dense.json" 2> "$O/$v/dense.err" || exit $?
   rm -f "$O"/$v/*/run_kernel_trace.csv
   unset FJAGG_LIB
 done

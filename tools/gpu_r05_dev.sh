@@ -19,9 +19,9 @@ timeout -k 10 300 python tools/probe_l2_ab.py 50 5 > "$O/l2_ab.jsonl" 2> "$O/l2_
 cat "$O/l2_ab.jsonl"
 timeout -k 10 300 python tools/prof_norm_call.py 40 > "$O/norm_call.json" 2> "$O/norm_call.err" || { tail -20 "$O/norm_call.err"; exit 1; }
 cat "$O/norm_call.json"
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
-timeout -k 10 600 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/bench_n2_gloo.json" \
+timeout -k 10 600 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/bench_n2_gloo.json" \
   2> "$O/bench_n2_gloo.err" || { tail -20 "$O/bench_n2_gloo.err"; exit 1; }
 cat "$O/bench_n2_gloo.json"
 echo done

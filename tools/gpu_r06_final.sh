@@ -16,16 +16,16 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rfs --timeout 300 --timeo
 tail -3 "$O/gpu_tests.log"
 timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > "$O/smoke.log" 2>&1 || exit $?
 tail -1 "$O/smoke.log"
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || exit $?
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || exit $?
 cat "$O/bench.json"
-timeout -k 10 900 python bench.py --measure-traffic --traffic-out "$O/traffic_c3.json" --no-cpu-baseline --no-dropin --no-e2e \
+timeout -k 10 900 python bench.py --full --measure-traffic --traffic-out "$O/traffic_c3.json" --no-cpu-baseline --no-dropin --no-e2e \
   > "$O/bench_traffic.json" 2> "$O/bench_traffic.err" || exit $?
 cat "$O/bench_traffic.json"
-timeout -k 10 600 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/bench_n2_gloo.json" \
+timeout -k 10 600 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/bench_n2_gloo.json" \
   2> "$O/bench_n2_gloo.err" || exit $?
 cat "$O/bench_n2_gloo.json"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- \
-  python bench.py --no-cpu-baseline --no-dropin --no-e2e > "$O/prof.log" 2>&1 || exit $?
+  python bench.py --full --no-cpu-baseline --no-dropin --no-e2e > "$O/prof.log" 2>&1 || exit $?
 cat "$O"/prof/run_kernel_stats.csv | head -8
 rm -f "$O"/prof/run_kernel_trace.csv
 # the examples/fed_avg.py round: timing (lazy / eager norms / mean only) and its PMC traffic per mode

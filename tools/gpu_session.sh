@@ -29,11 +29,11 @@ fi
 tail -5 "$OUT/${TAG}_gpu_tests.log"
 step smoke 300 1 python -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/${TAG}_smoke.log" 2>&1
 tail -2 "$OUT/${TAG}_smoke.log"
-step bench 600 0 python bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+step bench 600 0 python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 cat "$OUT/${TAG}_bench.json"
-step bench-n2-gloo 600 0 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 \
+step bench-n2-gloo 600 0 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 \
   > "$OUT/${TAG}_bench_n2_gloo.json" 2> "$OUT/${TAG}_bench_n2_gloo.err"
 cat "$OUT/${TAG}_bench_n2_gloo.json"
 step rocprof 600 0 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_prof" -o run --output-format csv -- \
-  python bench.py --no-cpu-baseline
+  python bench.py --full --no-cpu-baseline
 find "$OUT/${TAG}_prof" -name '*kernel_stats.csv' -exec cat {} \;

@@ -93,12 +93,12 @@ case "$STUDY" in
     cat $O/time_pytree.jsonl
     for wl in c2 c3; do
       for dw in "" "--device-weights"; do
-        timeout -k 10 300 python bench.py --workload $wl --steps 50 --warmup 10 --no-cpu-baseline $dw \
+        timeout -k 10 300 python bench.py --full --workload $wl --steps 50 --warmup 10 --no-cpu-baseline $dw \
           > $O/bench_${wl}${dw:+_dw}.json 2> $O/bench_${wl}${dw:+_dw}.err || die "bench $wl $dw"
       done
     done
     for dw in "" "--device-weights"; do
-      timeout -k 10 300 python bench.py --rehearse-shard 8 --steps 50 --warmup 10 --buckets 1 $dw \
+      timeout -k 10 300 python bench.py --full --rehearse-shard 8 --steps 50 --warmup 10 --buckets 1 $dw \
         > $O/shard8${dw:+_dw}.json 2> $O/shard8${dw:+_dw}.err || die "shard8 $dw"
     done
     grep -h -o '"ms_per_step": [0-9.]*\|"workload": "[^"]*"\|"weights_path": [^}]*}\|"mean_launch_ms": [0-9.]*' \
@@ -109,7 +109,7 @@ case "$STUDY" in
   c5_rehearse)
     # configs[4]: rank 0's share (1024 of 8192 clients x 125 M bf16) through the full sharded
     # step on a world-1 RCCL communicator: fold -> f32 partial -> reduce -> bf16 cast
-    timeout -k 10 900 python bench.py --workload c5 --rehearse-shard 8 --steps ${STEPS:-10} --warmup 3 \
+    timeout -k 10 900 python bench.py --full --workload c5 --rehearse-shard 8 --steps ${STEPS:-10} --warmup 3 \
       > $O/c5_rehearse.json 2> $O/c5_rehearse.err || die c5_rehearse
     cat $O/c5_rehearse.json
     ;;
