@@ -194,13 +194,14 @@ struct OptEpi {
         params[e] = __fadd_rn(p, o.nesterov ? __fadd_rn(s, __fmul_rn(o.decay, t)) : t);
         return;
       }
-    } else {  // optax.scale_by_yogi: nu - (1 - b2) * sign(nu - g^2) * g^2, no bias correction
+    } else {  // optax.scale_by_yogi: nu - (1 - b2) * sign(nu - g^2) * g^2, bias-corrected as adam's
       const float mu = __fadd_rn(__fmul_rn(o.one_minus_b1, g), __fmul_rn(o.b1, m[e]));
       const float g2 = __fmul_rn(g, g), nv = v[e];
       const float nu = __fsub_rn(nv, __fmul_rn(__fmul_rn(o.one_minus_b2, xla_sign(__fsub_rn(nv, g2))), g2));
       m[e] = mu;
       v[e] = nu;
-      u = div_rn(mu, __fadd_rn(sqrt_rn(__fadd_rn(nu, o.eps_root)), o.eps));
+      const float mh = div_rn(mu, o.bc1), nh = div_rn(nu, o.bc2);
+      u = div_rn(mh, __fadd_rn(sqrt_rn(__fadd_rn(nh, o.eps_root)), o.eps));
     }
     params[e] = __fadd_rn(p, __fmul_rn(o.neg_lr, u));  // scale_by_learning_rate, apply_updates
   }

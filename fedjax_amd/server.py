@@ -142,7 +142,8 @@ def rmsprop(learning_rate: float, decay: float = 0.9, eps: float = 1e-8, initial
 
 def yogi(learning_rate: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-3) -> ServerOptimizer:
     """fedjax.optimizers.yogi (optimizers.py:253-281): optax.scale_by_yogi (eps_root 0,
-    initial_accumulator_value 1e-6 for both moments), then -lr."""
+    initial_accumulator_value 1e-6 for both moments; both are bias-corrected by
+    ``1 - b ** count`` before the division, as adam's are), then -lr."""
     return ServerOptimizer(_lib.OPT_YOGI, learning_rate, b1=b1, b2=b2, eps=eps, init_m=1e-6, init_v=1e-6)
 
 

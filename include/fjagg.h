@@ -240,9 +240,11 @@ int fjagg_wsum_l2_dense(int in_dtype, int acc_dtype, int out_dtype, const void* 
  *             u = (mu/bc1) / (sqrt(nu/bc2 + eps_root) + eps); p += neg_lr * u
  *   ADAGRAD   v = g*g + v; u = (v > 0 ? rsqrt(v + eps) : 0) * g; p += neg_lr * u
  *   RMSPROP   v = (1-b2) g*g + b2 v; u = g * rsqrt(v + eps);
- *             [F_MOMENTUM: t = u + decay*m; u = nesterov ? u + decay*t : t]; p += neg_lr * u
+ *             p += neg_lr * u  [F_MOMENTUM: s = neg_lr * u; t = s + decay*m;
+ *             p += nesterov ? s + decay*t : t]
  *   YOGI      mu = (1-b1) g + b1 mu; nu = nu - ((1-b2) sign(nu - g*g)) g*g;
- *             u = mu / (sqrt(nu + eps_root) + eps); p += neg_lr * u
+ *             u = (mu/bc1) / (sqrt(nu/bc2 + eps_root) + eps); p += neg_lr * u
+ *             (bias-corrected as ADAM: optax.scale_by_yogi keeps a count for it)
  * (rsqrt = 1/sqrt evaluated in f64, rounded once; div / sqrt correctly rounded)
  * with every constant pre-rounded to f32 on the host as JAX's weak typing does
  * (bc1 = f32(1 - b1^t), bc2 = f32(1 - b2^t) for the step count t after the
@@ -256,7 +258,7 @@ enum fjagg_opt_kind {
   FJAGG_OPT_ADAM = 3,     /* optimizers.py:148-178, optax.scale_by_adam (m, v)               */
   FJAGG_OPT_ADAGRAD = 4,  /* optimizers.py:117-145, optax.scale_by_rss (v = sum of squares)  */
   FJAGG_OPT_RMSPROP = 5,  /* optimizers.py:181-224, optax.scale_by_rms (v) [+ trace (m)]     */
-  FJAGG_OPT_YOGI = 6      /* optimizers.py:253-281, optax.scale_by_yogi (m, v)               */
+  FJAGG_OPT_YOGI = 6      /* optimizers.py:253-281, optax.scale_by_yogi (m, v; bc1, bc2)     */
 };
 /* RMSPROP: b2 / one_minus_b2 = decay / 1 - decay. optax.rmsprop's chain is the rescale,
  * then scale_by_learning_rate, then (flags & FJAGG_OPT_F_MOMENTUM) optax.trace(decay = this

@@ -87,8 +87,14 @@ def init(params: dict, *, factored=True, min_dim_size_to_factor=128, momentum=No
 def apply(grads: dict, state: dict, params: dict, *, learning_rate=None, min_dim_size_to_factor=128,
           decay_rate=0.8, decay_offset=0, multiply_by_parameter_scale=True,
           clipping_threshold: Optional[float] = 1.0, momentum: Optional[float] = None,
-          weight_decay_rate: Optional[float] = None, eps=1e-30, factored=True, weight_decay_mask=None):
-    """One optimizer.apply(grads, state, params) -> (state, params), new arrays."""
+          weight_decay_rate: Optional[float] = None, eps=1e-30, factored=True, weight_decay_mask=None,
+          trace: Optional[dict] = None):
+    """One optimizer.apply(grads, state, params) -> (state, params), new arrays. ``trace``
+    (a dict) receives per leaf the clip's denominator ``max(1, rms(u) / threshold)`` under
+    "clip_denom" and ``rms(p)`` before its 1e-3 clamp under "param_rms", so a test can tell
+    which side of each max() its inputs took."""
+    if trace is not None:
+        trace.update(clip_denom={}, param_rms={})
     count = state["count"]
     d = decay_rate_pow(count - decay_offset, decay_rate)
     omd = f32(1) - d
@@ -117,11 +123,16 @@ def apply(grads: dict, state: dict, params: dict, *, learning_rate=None, min_dim
         if clipping_threshold is not None:
             denom = np.maximum(f32(1), _div(_sqrt(_mean(u * u)), f32(clipping_threshold)))
             u = _div(u, denom)
+            if trace is not None:
+                trace["clip_denom"][k] = float(denom)
         if learning_rate is not None:
             lr = learning_rate(count) if callable(learning_rate) else learning_rate
             u = u * f32(lr)
         if multiply_by_parameter_scale:
-            u = u * np.maximum(_sqrt(_mean(p * p)), f32(1e-3))
+            rms = _sqrt(_mean(p * p))
+            u = u * np.maximum(rms, f32(1e-3))
+            if trace is not None:
+                trace["param_rms"][k] = float(rms)
         if momentum is not None:
             u = f32(1.0 - momentum) * u + f32(momentum) * state["m"][k]
             new["m"][k] = u

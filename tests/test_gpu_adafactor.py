@@ -85,6 +85,78 @@ def test_adafactor_matches_restated_optax(name, cuda):
             _compare(_host(state[what]), ref_state[what], f"step {step} {what}")
 
 
+def _run_against_ref(cfg, p_host, grads):
+    """One opt.apply per entry of ``grads`` on the GPU and in the restatement; params and
+    state compared after every step. Returns the restatement's trace of each step."""
+    opt = server.adafactor(**cfg)
+    params = _dev(p_host)
+    state = opt.init(params)
+    ref_state = ref.init(p_host, factored=opt.factored, min_dim_size_to_factor=opt.min_dim_size_to_factor,
+                         momentum=opt.momentum)
+    for what in ("v_row", "v_col", "v"):
+        for k in p_host:
+            assert tuple(state[what][k].shape) == ref_state[what][k].shape, (k, what)
+    traces = []
+    for step, g_host in enumerate(grads):
+        state, params = opt.apply(_dev(g_host), state, params)
+        traces.append({})
+        ref_state, p_host = ref.apply(g_host, ref_state, p_host, trace=traces[-1], **cfg)
+        torch.cuda.synchronize()
+        _compare(_host(params), p_host, f"step {step} params")
+        for what in ("v_row", "v_col", "v"):
+            _compare(_host(state[what]), ref_state[what], f"step {step} {what}")
+    return traces
+
+
+def test_adafactor_strided_reduce_of_short_rows(cuda):
+    """min_dim_size_to_factor=2 factors tiny leaves: their sums along the last axis are
+    [O, N, 1] with N < 64, which the plan sends to the strided reduce (a thread per (chunk,
+    o, i)) with I == 1 instead of the wave-per-row one."""
+    shapes = {"a": (3, 2), "b": (2, 5, 3), "c": (40, 33)}
+    cfg = dict(learning_rate=0.05, min_dim_size_to_factor=2)
+    for k, s in shapes.items():
+        assert ref.factored_dims(s, True, 2) is not None, k
+    _run_against_ref(cfg, _draw(2, shapes), [_draw(200 + i, shapes, scale=0.01 * (i + 1)) for i in range(3)])
+
+
+def test_adafactor_row_chunks_clamp_and_clip_sides(cuda):
+    """(130, 2500): rows of 2500 reduce in 10 row-mode chunks of 256 (between 8 and 63: the
+    thread-per-statistic finish over more than one group of 8 partials). A leaf of zero
+    params and one of 1e-5-scale params take the 1e-3 side of max(rms(p), 1e-3). Grads that
+    shrink tenfold on some leaves and double on others put both sides of the clip's
+    max(1, rms(u) / threshold) in one step, read off the restatement's own denominators."""
+    shapes = {"a_rows": (130, 2500), "b_zero": (64, 32), "c_tiny": (200,), "d_shrink": (300, 200),
+              "e_shrink": (200,)}
+    p_host = _draw(3, shapes)
+    p_host["b_zero"][...] = 0.0
+    p_host["c_tiny"] *= np.float32(1e-5)
+    g0 = _draw(300, shapes, scale=0.01)
+    grads = [g0]
+    for i in (1, 2):
+        g = _draw(300 + i, shapes, scale=0.01)
+        grads.append({k: (v * np.float32(0.1 ** i if "shrink" in k else 2.0 ** i)) for k, v in g.items()})
+    traces = _run_against_ref(dict(learning_rate=0.05), p_host, grads)
+    assert traces[0]["param_rms"]["b_zero"] == 0.0
+    for tr in traces:
+        assert tr["param_rms"]["b_zero"] < 1e-3 and 0.0 < tr["param_rms"]["c_tiny"] < 1e-3
+        assert all(tr["param_rms"][k] > 1e-3 for k in ("a_rows", "d_shrink", "e_shrink"))
+    for tr in traces[1:]:
+        assert any(d > 1.0 for d in tr["clip_denom"].values()), tr["clip_denom"]
+        assert any(d == 1.0 for d in tr["clip_denom"].values()), tr["clip_denom"]
+
+
+def test_adafactor_row_chunks_longer_than_256(cuda):
+    """(8200, 2100), one step: 17.2 M elements put more than 256 * 65536 elements behind
+    the row-mode reductions, so their chunks grow to 263 elements, for the rows of g * g
+    (8200 rows of 2100) and for the sum of p * p (one row of 17.2 M)."""
+    shapes = {"w": (8200, 2100)}
+    rs = np.random.RandomState(4)
+    p_host = {"w": rs.standard_normal(shapes["w"]).astype(np.float32)}
+    g_host = {"w": (rs.standard_normal(shapes["w"]) * 0.01).astype(np.float32)}
+    _run_against_ref(dict(learning_rate=0.05), p_host, [g_host])
+    torch.cuda.empty_cache()
+
+
 def test_adafactor_first_step_closed_form(cuda):
     """Count 0: decay_rate_t = 0, so v = g*g + eps and, unfactored, u = g / sqrt(g*g + eps);
     with clipping off, no param scale and lr 1 the params move by exactly -u."""

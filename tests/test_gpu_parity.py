@@ -788,8 +788,10 @@ def _np_server_step(opt, d, g, p, m, v):
             return p + (s_ + f(d.decay) * m if opt.nesterov else m), m, v
     else:  # optax.scale_by_yogi
         m = f(d.one_minus_b1) * g + f(d.b1) * m
-        v = v - (f(d.one_minus_b2) * np.sign(v - g * g)).astype(f) * (g * g)
-        u = m / (np.sqrt(v + f(d.eps_root)) + f(d.eps))
+        dv = v - g * g
+        sign = np.where(dv == 0, dv, np.sign(dv))  # jnp.sign keeps the sign of zero (np.sign(-0.0) is +0.0)
+        v = v - (f(d.one_minus_b2) * sign).astype(f) * (g * g)
+        u = (m / f(d.bc1)) / (np.sqrt(v / f(d.bc2) + f(d.eps_root)) + f(d.eps))  # bias-corrected as adam's
     return p + f(d.neg_lr) * u, m, v
 
 
