@@ -34,7 +34,7 @@ ZEROED_WS = 128  # fused-norm calls: the workspace's 16-byte completion counter 
 KARG_MAX_WEIGHTS, KARG_MAX_WORDS = 1024, 3584
 # enum fjagg_mode
 MODE_EXACT, MODE_SPLIT = 0, 1
-ABI_VERSION = 3
+ABI_VERSION = 4
 COMP_ABI_VERSION = 1
 COMM_ABI_VERSION = 1
 COMM_ID_BYTES = 128
@@ -73,6 +73,12 @@ _SIGNATURES = {
     "fjagg_l2sq_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "fjagg_l2sq_rows_workspace_bytes": (_i64, [_i64, _i64]),
     "fjagg_l2sq_rows": (_i32, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "fjagg_clip_scales": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp]),
+    "fjagg_wsum_clip_workspace_bytes": (_i64, [_i64, _i64]),
+    "fjagg_wsum_clip_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "fjagg_wsum_clip_ptrs_workspace_bytes": (_i64, [_i64, _i64]),
+    "fjagg_wsum_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _i32, _vp, _i64, _vp]),
+    "fjagg_clip_finish": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

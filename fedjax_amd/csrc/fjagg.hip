@@ -135,6 +135,35 @@ __device__ __forceinline__ void sq_acc(const T (&t)[V], f32x2& q) {
   }
 }
 
+// ---------------------------------------------------------------- clip policy
+// Per-client norm clipping inside the fold (fjagg_wsum_clip_*): client k's elements are
+// multiplied by the device factor c[k] BEFORE the weight, t = fl(fl(c_k * x) * w_k), the
+// reference's rounding sequence (tree_clip_by_global_norm, tree_util.py:133, then tree_weight,
+// :32). With fused norms the squares are those of the product fl(c_k * x): the clipped norm.
+// NoClip (every other fold): nothing of this is emitted.
+struct NoClip {
+  static constexpr bool kOn = false;
+  __device__ __forceinline__ float factor(int64_t) const { return 1.0f; }
+};
+struct DevClip {
+  static constexpr bool kOn = true;
+  const float* __restrict__ c;
+  __device__ __forceinline__ float factor(int64_t k) const { return c[k]; }
+};
+// t <- fl(ck * t); a lane's invalid unit (zeros, see fold) stays +0 whatever ck is, so an
+// infinite or NaN factor reaches the squares through real elements only
+template <class CLIP, bool NORM_ON, class T, int V>
+__device__ __forceinline__ void clip_unit(T (&t)[V], float ck, bool valid) {
+  if constexpr (CLIP::kOn) {
+    static_assert(std::is_same<T, float>::value, "the clipped fold is a float32 fold");
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      t[i] = __fmul_rn(ck, t[i]);
+      if constexpr (NORM_ON) t[i] = valid ? t[i] : 0.0f;
+    }
+  }
+}
+
 // ----------------------------------------------------------------- epilogues
 // PlainEpi: the fold's result goes to the output (tree_mean). OptEpi: the mean
 // y = fl(s * scale) feeds the server optimizer step of the round in registers
@@ -213,14 +242,15 @@ struct OptEpi {
 // wave-uniform base address of client k. Clients are folded in order 0..K-1.
 // The output of the unit at input byte offset off is at obase + off / sizeof(IN) *
 // sizeof(OUT) (same element index); valid[j] == false skips unit j's store.
+// CLIP (default NoClip): the per-client factor applied before the weight (clip policy above).
 template <int IN, class ACC, int OUT, int V, int E, int U, bool NT, bool BURST = true, class RowFn,
-          class NORM = NoNorm, class EPI = PlainEpi>
+          class NORM = NoNorm, class EPI = PlainEpi, class CLIP = NoClip>
 __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
                                      const uint32_t (&off)[E],
                                      uint8_t* __restrict__ obase, const bool (&valid)[E],
                                      const typename ACC::T* __restrict__ w, bool do_scale,
                                      float scale, bool accumulate, NORM nrm = NORM(),
-                                     const EPI& epi = EPI()) {
+                                     const EPI& epi = EPI(), CLIP clip = CLIP()) {
   constexpr int IB = Elem<IN>::B, OB = Elem<OUT>::B;
   auto outp = [&](int j) { return obase + (size_t)(off[j] / IB) * OB; };
   using T = typename ACC::T;
@@ -239,11 +269,13 @@ __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
 #pragma unroll
     for (int j = 0; j < E; ++j) v[j] = load_unit<IN, V, NT>(r, loff[j]);
     const T w0 = ACC::weight(w[0]);
+    const float c0 = clip.factor(0);
     f32x2 q[1] = {{0.f, 0.f}};
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       T t[V];
       decode<IN, ACC, V>(v[j], t);
+      clip_unit<CLIP, NORM::kOn>(t, c0, valid[j]);
       if constexpr (NORM::kOn) sq_acc<T, V>(t, q[0]);
 #pragma unroll
       for (int i = 0; i < V; ++i) acc[j][i] = ACC::mul(t[i], w0);
@@ -291,10 +323,12 @@ __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const T wk = ACC::weight(w[k + u]);
+      const float ck = clip.factor(k + u);
 #pragma unroll
       for (int j = 0; j < E; ++j) {
         T t[V];
         decode<IN, ACC, V>(v[u][j], t);
+        clip_unit<CLIP, NORM::kOn>(t, ck, valid[j]);
         if constexpr (NORM::kOn) sq_acc<T, V>(t, q[u]);
 #pragma unroll
         for (int i = 0; i < V; ++i) acc[j][i] = ACC::add(acc[j][i], ACC::mul(t[i], wk));
@@ -305,11 +339,13 @@ __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
   for (; k < K; ++k) {
     const auto r = row_rsrc(row(k), row_bytes);
     const T wk = ACC::weight(w[k]);
+    const float ck = clip.factor(k);
     f32x2 q[1] = {{0.f, 0.f}};
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       T t[V];
       decode<IN, ACC, V>(load_unit<IN, V, NT>(r, loff[j]), t);
+      clip_unit<CLIP, NORM::kOn>(t, ck, valid[j]);
       if constexpr (NORM::kOn) sq_acc<T, V>(t, q[0]);
 #pragma unroll
       for (int i = 0; i < V; ++i) acc[j][i] = ACC::add(acc[j][i], ACC::mul(t[i], wk));
@@ -583,6 +619,94 @@ __global__ __launch_bounds__(kThreads) void k_dense_l2(
   l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
 }
 
+// The dense exact fold with per-client clip factors c[K] applied before the weights
+// (fjagg_wsum_clip_dense; float32 slab, fold and output): k_dense's grid and unit layout.
+// L2: also the per-client squares of the clipped products fl(c_k x), through k_dense_l2's
+// LDS-per-wave rows and workgroup partial rows ws[b*K + k]; k_l2_combine adds them (a
+// separate launch always: l2out.done is never set here).
+template <int V, int E, int U, bool NT, bool L2>
+__global__ __launch_bounds__(kThreads) void k_dense_clip(
+    const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
+    const float* __restrict__ w, const float* __restrict__ c, float scale, int do_scale, int accumulate,
+    uint8_t* __restrict__ out, int64_t S, float* __restrict__ ws, const L2Out l2out) {
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  const int tid = threadIdx.x;
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  const DevClip clip{c};
+  auto row = [=](int64_t k) { return x + k * ld_bytes; };
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  bool is_tail = false;
+  if (tail_n > 0) {
+    if (b == 0) {
+      is_tail = true;
+      const bool active = tid < tail_n;
+      if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+        const int64_t e = nunits * V + (active ? tid : 0);
+        const uint32_t off[1] = {(uint32_t)(e * IB)};
+        const bool valid[1] = {active};
+        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0, scale,
+                                         accumulate != 0, nrm, PlainEpi(), clip);
+      }
+    }
+    b -= 1;
+  }
+  if (!is_tail) {
+    const int64_t u_begin = b * S;
+    const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+      uint32_t off[E];
+      bool valid[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        int64_t u = g + j * kThreads + tid;
+        valid[j] = u < u_end;
+        if (!valid[j]) u = u_end - 1;
+        off[j] = (uint32_t)(u * (V * IB));
+      }
+      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0, scale,
+                                       accumulate != 0, nrm, PlainEpi(), clip);
+    }
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+}
+
+// Clip factors of K clients from their squared norms (fjagg_clip_scales), one lane per client:
+//   n = sqrt_rn(q); r = div_rn(C, n); c = isnan(r) ? r : (r < 1 ? r : 1)
+// jnp.minimum(1, max_norm / tree_l2_norm(delta)) of tree_clip_by_global_norm (tree_util.py:131-132):
+// NaN propagates (fminf would drop it), n = 0 gives r = +inf (or NaN for C = 0) and c = 1 (NaN).
+__global__ __launch_bounds__(kThreads) void k_clip_scales(const float* __restrict__ l2sq, int64_t K, float C,
+                                                          float* __restrict__ norm, float* __restrict__ c) {
+  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= K) return;
+  const float n = sqrt_rn(l2sq[k]);
+  const float r = div_rn(C, n);
+  if (norm) norm[k] = n;
+  c[k] = (r != r) ? r : (r < 1.0f ? r : 1.0f);
+}
+
+// The round's per-client diagnostics after a clipped fold (fjagg_clip_finish; mime_lite.py:139-146):
+// clipped[k] = (c_k != 1) (true for NaN, as jnp.not_equal of two NaN norms is) and the clipped
+// norm: the unclipped client's norm verbatim, else sqrt_rn of the squares of fl(c_k x).
+__global__ __launch_bounds__(kThreads) void k_clip_finish(const float* __restrict__ norm,
+                                                          const float* __restrict__ c,
+                                                          const float* __restrict__ l2sq_clipped, int64_t K,
+                                                          float* __restrict__ clipped_norm,
+                                                          uint8_t* __restrict__ clipped) {
+  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= K) return;
+  const float ck = c[k];
+  if (clipped) clipped[k] = (ck != 1.0f) ? 1 : 0;
+  if (clipped_norm) clipped_norm[k] = (ck == 1.0f) ? norm[k] : sqrt_rn(l2sq_clipped[k]);
+}
+
 // out[k] = sum over b of ws[b*K + k]. Workgroup = 64 clients x 16 waves: wave w sums
 // partials b = w, w+16, ... in that order (coalesced 256-B rows), then the 16 wave sums
 // are added in wave order: deterministic. The kernel runs after the fold, on a few
@@ -709,10 +833,11 @@ __global__ __launch_bounds__(kThreads) void k_dense_opt(
 // kThreads*8 units (E=8, U=4: the dense default; lanes past the range are masked)
 // when the range gives a lane more than one unit, else in groups of kThreads units
 // (E=1, U=8).
-template <int IN, class ACC, int OUT, int VV, bool NT, bool BURST, class RowFn, class NORM, class EPI>
+template <int IN, class ACC, int OUT, int VV, bool NT, bool BURST, class RowFn, class NORM, class EPI,
+          class CLIP = NoClip>
 __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_t K, int64_t u0, int64_t u1,
                                            uint8_t* ob, const typename ACC::T* __restrict__ w, bool dsc,
-                                           float scale, bool acm, NORM nrm, const EPI& epi) {
+                                           float scale, bool acm, NORM nrm, const EPI& epi, CLIP clip = CLIP()) {
   constexpr int IB = Elem<IN>::B;
   const int tid = threadIdx.x;
   if (u1 - u0 > (int64_t)kThreads) {
@@ -726,7 +851,7 @@ __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_
         if (!valid[j]) u = u1 - 1;
         off[j] = (uint32_t)(u * (VV * IB));
       }
-      fold<IN, ACC, OUT, VV, 8, 4, NT, BURST>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi);
+      fold<IN, ACC, OUT, VV, 8, 4, NT, BURST>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip);
     }
     return;
   }
@@ -735,7 +860,7 @@ __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_
     const bool valid[1] = {u < u1};
     if (!valid[0]) u = u1 - 1;
     const uint32_t off[1] = {(uint32_t)(u * (VV * IB))};
-    fold<IN, ACC, OUT, VV, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi);
+    fold<IN, ACC, OUT, VV, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip);
   }
 }
 
@@ -813,6 +938,64 @@ __global__ __launch_bounds__(kThreads) void k_ptrs(const int64_t* __restrict__ i
     walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, dsc, scale, acm, nrm, PlainEpi());
   } else {
     walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, dsc, scale, acm, nrm, PlainEpi());
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
+}
+
+// k_ptrs with per-client clip factors c[K] applied before the weights (fjagg_wsum_clip_ptrs):
+// float32 leaves and fold, device image and weights; the plan image, block words and unit walk
+// are k_ptrs's (restated here rather than shared, so that k_ptrs compiles to the code it always
+// did). L2: also the per-client squares of the clipped products, into the partial rows ws
+// (added by k_l2_combine only: l2out.done is never set here).
+template <int V, bool NT, bool L2, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_ptrs_clip(const int64_t* __restrict__ img, int L, int64_t K,
+                                                        const float* __restrict__ w, const float* __restrict__ c,
+                                                        float scale, int do_scale, int accumulate,
+                                                        float* __restrict__ ws, const L2Out l2out) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  using ACC = AccF;
+  const int tid = threadIdx.x;
+  const DevClip clip{c};
+  const int64_t* in_ptrs = img;
+  const int64_t* out_ptrs = img + K * L;
+  const int64_t* leaf_n = out_ptrs + L;
+  const int64_t bid = (accumulate & 2) ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1);
+  const int64_t u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t nunits = n / V;
+  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);  // rebased as in k_ptrs
+  uint8_t* ob = reinterpret_cast<uint8_t*>(out_ptrs[leaf]) + e_base * Elem<OUT>::B;
+  auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((n - e_base) * IB);
+  const bool dsc = do_scale != 0, acm = (accumulate & 1) != 0;
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  if (tail) {
+    const bool active = tid < n - nunits * V;
+    if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+      const int64_t e = active ? tid : 0;
+      const uint32_t off[1] = {(uint32_t)(e * IB)};
+      const bool valid[1] = {active};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, PlainEpi(), clip);
+    }
+  } else if (V > 1 && elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, dsc, scale, acm, nrm, PlainEpi(),
+                                           clip);
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, dsc, scale, acm, nrm, PlainEpi(),
+                                           clip);
   }
   if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
 }
@@ -2298,6 +2481,196 @@ int fjagg_l2sq_rows(int in_dtype, const int64_t* image_dev, int64_t R, int64_t m
   hipLaunchKernelGGL(k_l2sq_groups, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, ws, nb, G,
                      rows_per_group, take_sqrt, out_dev);
   return check_launch("k_l2sq_groups");
+}
+
+// ------------------------------------------------- clipped weighted mean (fjagg.h)
+namespace {
+// The flags a clipped fold takes; everything else is refused before any launch.
+int clip_flags_check(int in_dtype, int flags, int allowed) {
+  if (in_dtype != FJAGG_F32)
+    return fail(FJAGG_EUNSUPPORTED, "clipped fold: float32 deltas, fold and output only");
+  if (flags & FJAGG_NARROW) return fail(FJAGG_EUNSUPPORTED, "clipped fold: no FJAGG_NARROW plans");
+  if (flags & FJAGG_HOST_TABLES)
+    return fail(FJAGG_EUNSUPPORTED, "clipped fold: device weights and factors only (no FJAGG_HOST_TABLES)");
+  if (flags & FJAGG_ZEROED_WS)
+    return fail(FJAGG_EUNSUPPORTED, "clipped fold: the norm partials are combined by a separate launch "
+                                    "(no FJAGG_ZEROED_WS)");
+  if (flags & 0xff00) return fail(FJAGG_EUNSUPPORTED, "clipped fold: no kernel variants");
+  if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "clipped fold: unsupported flags 0x%x", flags & ~allowed);
+  return FJAGG_OK;
+}
+
+extern "C++" {
+template <int V, int E, int U, bool NT, bool L2>
+int launch_dense_clip_t(const DenseArgs& a, const float* c, float* ws, int64_t ws_floats, L2Out l2,
+                        hipStream_t s) {
+  auto kern = k_dense_clip<V, E, U, NT, L2>;
+  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
+  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  int64_t S = (int64_t)kThreads * E, nblk = 0;
+  balanced_grid(residency(reinterpret_cast<const void*>(kern), smem), a.nunits, (int64_t)kThreads * E, 1, &S,
+                &nblk);
+  if (a.nunits == 0) nblk = 0;
+  const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
+  if (L2 && grid * a.K > ws_floats)
+    return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
+                (long long)a.K);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
+                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, a.do_scale, a.accumulate, a.out, S,
+                     ws, l2);
+  if (int rc = check_launch("k_dense_clip")) return rc;
+  return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
+}
+
+// the shapes of launch_dense_l2_io: E=8 x U=4 where pick_variant says so, else E=1 x U=8
+template <bool L2>
+int launch_dense_clip(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, float* ws,
+                      int64_t ws_floats, L2Out l2, hipStream_t s) {
+  if (!vec)
+    return nt ? launch_dense_clip_t<1, 1, 8, true, L2>(a, c, ws, ws_floats, l2, s)
+              : launch_dense_clip_t<1, 1, 8, false, L2>(a, c, ws, ws_floats, l2, s);
+  if (variant == 12)
+    return nt ? launch_dense_clip_t<4, 8, 4, true, L2>(a, c, ws, ws_floats, l2, s)
+              : launch_dense_clip_t<4, 8, 4, false, L2>(a, c, ws, ws_floats, l2, s);
+  return nt ? launch_dense_clip_t<4, 1, 8, true, L2>(a, c, ws, ws_floats, l2, s)
+            : launch_dense_clip_t<4, 1, 8, false, L2>(a, c, ws, ws_floats, l2, s);
+}
+
+template <int V, bool L2>
+int launch_ptrs_clip(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w, const float* c,
+                     float scale, int ds, int ac, float* ws, L2Out l2, hipStream_t s) {
+  const dim3 grid((unsigned)nblk), block(kThreads);
+  ac = (ac ? 1 : 0) | xcd_remap_bit();
+  if constexpr (L2) {
+    const size_t smem = l2_smem(K, l2);
+    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip<V, true, true, true>)
+                        : reinterpret_cast<const void*>(k_ptrs_clip<V, false, true, true>);
+    if (int rc = allow_lds(kf, smem)) return rc;
+    if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, ds, ac, ws,
+                         l2);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, ds, ac,
+                         ws, l2);
+    if (int rc = check_launch("k_ptrs_clip (l2)")) return rc;
+    return launch_l2_combine(ws, nblk, K, l2, s);
+  } else {
+    // the schedule rule of launch_ptrs_t
+    const bool burst = nblk < 2 * (int64_t)cu_count();
+    if (nt && burst)
+      hipLaunchKernelGGL((k_ptrs_clip<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
+                         nullptr, l2);
+    else if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
+                         nullptr, l2);
+    else if (burst)
+      hipLaunchKernelGGL((k_ptrs_clip<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
+                         nullptr, l2);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
+                         nullptr, l2);
+    return check_launch("k_ptrs_clip");
+  }
+}
+}  // extern "C++"
+}  // namespace
+
+/* c_k = min(1, max_norm / sqrt(l2sq_k)), NaN propagating (fjagg.h) */
+int fjagg_clip_scales(const float* l2sq_dev, int64_t K, float max_norm, float* norm_dev, float* c_dev,
+                      void* stream) {
+  g_err[0] = 0;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (!l2sq_dev || !c_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipLaunchKernelGGL(k_clip_scales, dim3((unsigned)((K + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), l2sq_dev, K, max_norm, norm_dev, c_dev);
+  return check_launch("k_clip_scales");
+}
+
+int fjagg_clip_finish(const float* norm_dev, const float* c_dev, const float* l2sq_clipped_dev, int64_t K,
+                      float* clipped_norm_dev, uint8_t* clipped_dev, void* stream) {
+  g_err[0] = 0;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (!c_dev || (!clipped_norm_dev && !clipped_dev) || (clipped_norm_dev && (!norm_dev || !l2sq_clipped_dev)))
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipLaunchKernelGGL(k_clip_finish, dim3((unsigned)((K + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), norm_dev, c_dev, l2sq_clipped_dev, K, clipped_norm_dev,
+                     clipped_dev);
+  return check_launch("k_clip_finish");
+}
+
+int64_t fjagg_wsum_clip_workspace_bytes(int64_t K, int64_t P) { return fjagg_wsum_l2_workspace_bytes(K, P); }
+int64_t fjagg_wsum_clip_ptrs_workspace_bytes(int64_t K, int64_t nblk) {
+  return (K < 1 || nblk < 1) ? 0 : K * nblk * 4;
+}
+
+int fjagg_wsum_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const float* w_dev,
+                          const float* c_dev, float scale, void* out_dev, float* l2sq_clipped_dev, int flags,
+                          void* ws_dev, int64_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (int rc = clip_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_ACCUMULATE | FJAGG_NONTEMPORAL)) return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "clipped fold: rows <= 1 GiB");
+  if (!x_dev || !w_dev || !c_dev || !out_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < 0)) return fail(FJAGG_EINVAL, "null pointer argument");
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  uint8_t* y = reinterpret_cast<uint8_t*>(out_dev);
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0) &&
+                   ((ld * 4) % 16 == 0) && P >= 4;
+  const int V = vec ? 4 : 1;
+  DenseArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.K = K;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.w = w_dev;
+  a.scale = scale;
+  a.do_scale = (flags & FJAGG_SCALE) ? 1 : 0;
+  a.accumulate = (flags & FJAGG_ACCUMULATE) ? 1 : 0;
+  a.out = y;
+  a.kchunk = K;
+  a.out_ystride = 0;
+  a.balanced = true;
+  a.host_w = false;
+  const int variant = pick_variant(a.nunits, K);
+  const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (l2sq_clipped_dev)
+    return launch_dense_clip<true>(vec, nt, variant, a, c_dev, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
+                                   L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_dense_clip<false>(vec, nt, variant, a, c_dev, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr}, s);
+}
+
+int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                         const float* w_dev, const float* c_dev, float scale, float* l2sq_clipped_dev, int flags,
+                         void* ws_dev, int64_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (int rc = clip_flags_check(in_dtype, flags,
+                                FJAGG_SCALE | FJAGG_ACCUMULATE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED))
+    return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (nblk < 1 || nblk > 0x7fffffff || !image_dev || !w_dev || !c_dev || L < 1)
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)))
+    return fail(FJAGG_EINVAL, "clip workspace too small (need %lld bytes)",
+                (long long)fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, ac = (flags & FJAGG_ACCUMULATE) ? 1 : 0;
+  float* ws = reinterpret_cast<float*>(ws_dev);
+  if (l2sq_clipped_dev) {
+    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
+    return vec ? launch_ptrs_clip<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, ws, l2, s)
+               : launch_ptrs_clip<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, ws, l2, s);
+  }
+  const L2Out l2{nullptr, nullptr, 0, nullptr};
+  return vec ? launch_ptrs_clip<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s)
+             : launch_ptrs_clip<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s);
 }
 
 int fjagg_fill_synth(int dtype, void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t k0,

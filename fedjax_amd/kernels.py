@@ -287,6 +287,78 @@ def l2_squared_dense(x: torch.Tensor, out: Optional[torch.Tensor] = None,
     return out
 
 
+def _f32_vector(name: str, t: torch.Tensor, K: int) -> None:
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != (K,) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous float32 device tensor of shape ({K},)")
+
+
+def clip_scales(l2sq: torch.Tensor, max_norm: float):
+    """``(norms, c)`` of K clients from their squared l2 norms ``l2sq`` (float32 [K] on the
+    device): ``norms = sqrt(l2sq)`` and ``c = minimum(1, f32(max_norm) / norms)`` with the
+    reference's rounding and NaN propagation (tree_clip_by_global_norm, tree_util.py:131-132),
+    in one small launch; nothing visits the host."""
+    K = l2sq.numel()
+    _f32_vector("l2sq", l2sq, K)
+    dev = _require_device(l2sq)
+    norms, c = torch.empty_like(l2sq), torch.empty_like(l2sq)
+    _lib.call("fjagg_clip_scales", l2sq.data_ptr(), K, float(np.float32(max_norm)), norms.data_ptr(), c.data_ptr(),
+              _stream_handle(dev))
+    return norms, c
+
+
+def clipped_sum_dense(x: torch.Tensor, w: torch.Tensor, c: torch.Tensor, *, scale: Optional[float] = None,
+                      out: Optional[torch.Tensor] = None, accumulate: bool = False, nontemporal: bool = False,
+                      with_clipped_l2sq: bool = False):
+    """The exact fold of a float32 slab ``x[K, P]`` with every client's elements multiplied by
+    its device factor ``c[k]`` before its weight ``w[k]``: ``fl(fl(c_k x) w_k)`` summed in
+    client order (then ``* scale``), the reference's sequence for clipping each delta before
+    the weighted mean (tree_util.py:133, :32, :47-54). ``w`` and ``c`` are device float32 [K];
+    ``c`` is any such vector (:func:`clip_scales` makes the clip factors).
+
+    ``with_clipped_l2sq=True`` returns ``(out, l2sq_clipped)`` with ``l2sq_clipped[k] =
+    sum_p fl(c_k x_k[p])^2`` from the same pass (K <= 4096)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the clipped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    _f32_vector("w", w, K)
+    _f32_vector("c", c, K)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, w, c, out)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.ACCUMULATE if accumulate else 0)
+    flags |= _lib.NONTEMPORAL if nontemporal else 0
+    l2sq, ws, ws_ptr, ws_bytes = None, None, None, 0
+    if with_clipped_l2sq:
+        l2sq = torch.empty(K, dtype=torch.float32, device=dev)
+        ws_bytes = max(int(_lib.load().fjagg_wsum_clip_workspace_bytes(K, P)), 4)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws_ptr = ws.data_ptr()
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_wsum_clip_dense", _lib.F32, x.data_ptr(), ld, K, P, w.data_ptr(), c.data_ptr(),
+              float(scale if scale is not None else 1.0), out.data_ptr(), None if l2sq is None else l2sq.data_ptr(),
+              flags, ws_ptr, ws_bytes, _stream_handle(dev))
+    return (out, l2sq) if with_clipped_l2sq else out
+
+
+def clip_finish(norms: torch.Tensor, c: torch.Tensor, l2sq_clipped: torch.Tensor):
+    """``(clipped_norms, clipped)`` of a clipped fold: ``clipped = (c != 1)`` (bool [K]; true for
+    a NaN factor) and the clipped norms — an unclipped client's norm verbatim, else the
+    correctly rounded root of ``l2sq_clipped`` (mime_lite.py:139-146). One small launch."""
+    K = c.numel()
+    for name, t in (("norms", norms), ("c", c), ("l2sq_clipped", l2sq_clipped)):
+        _f32_vector(name, t, K)
+    dev = _require_device(norms, c, l2sq_clipped)
+    clipped_norms = torch.empty_like(norms)
+    clipped = torch.empty(K, dtype=torch.bool, device=dev)
+    _lib.call("fjagg_clip_finish", norms.data_ptr(), c.data_ptr(), l2sq_clipped.data_ptr(), K,
+              clipped_norms.data_ptr(), clipped.data_ptr(), _stream_handle(dev))
+    return clipped_norms, clipped
+
+
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:
     """Synthetic deltas x[k, p] = amp * u(seed, k0 + k, p) (tests/bench only)."""
     if x.dim() != 2 or x.stride(1) != 1:

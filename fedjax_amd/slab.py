@@ -134,6 +134,36 @@ class ClientDeltaSlab:
         flat = self.weighted_sum_flat(self.host_weights(weights), scale=scale, out=out, mode=mode)
         return self.unflatten(flat)
 
+    def clipped_mean(self, weights: Sequence, max_norm: float, *,
+                     out: Optional[torch.Tensor] = None) -> "tree_util.ClippedMean":
+        """Weighted mean of the K rows with every client's delta clipped to l2 norm
+        ``max_norm`` first: the loop of fedjax/algorithms/mime_lite.py:131-149
+        (tree_clip_by_global_norm, tree_util.py:117-133, before weighting and adding) for the
+        whole round, with the reference's W and f32(1/W) — clipping does not change W.
+
+        Two passes over the slab and three small launches, no host synchronisation and no
+        clipped copy: the squared norms, the clip factors ``c = min(1, max_norm / norm)`` on
+        the device, the fold ``fl(fl(c_k x) w_k)`` with the clipped squares from the same
+        pass, their combine, and the diagnostics. Returns a
+        :class:`~fedjax_amd.tree_util.ClippedMean`; a float32 slab of up to 4096 clients."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"clipped_mean needs a float32 slab, not {self.dtype}")
+        if self.num_clients > tree_util._L2_MAX_CLIENTS:
+            raise ValueError(f"clipped_mean supports up to {tree_util._L2_MAX_CLIENTS} clients")
+        W = 0.0
+        for x in weights:
+            W += tree_util._host_weight(x)
+        scale = tree_util._inverse(W)
+        rows = self.rows
+        w_dev = self.weight_vector(weights)
+        norms, c = kernels.clip_scales(kernels.l2_squared_dense(rows), max_norm)
+        nbytes = rows.numel() * rows.element_size()
+        flat, l2sq_clipped = kernels.clipped_sum_dense(
+            rows, w_dev, c, scale=float(np.float32(scale)), out=out,
+            nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES, with_clipped_l2sq=True)
+        clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+        return tree_util.ClippedMean(self.unflatten(flat), norms, clipped_norms, clipped)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

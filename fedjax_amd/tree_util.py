@@ -31,7 +31,7 @@ import numbers
 import os
 import time
 import weakref
-from typing import Any, Iterable, List, Optional, Sequence, Tuple
+from typing import Any, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -43,7 +43,7 @@ __all__ = [
     "tree_weight", "tree_inverse_weight", "tree_zeros_like", "tree_add", "tree_sum",
     "tree_mean", "tree_size", "tree_l2_squared", "tree_l2_norm", "tree_clip_by_global_norm",
     "tree_l2_norms", "tree_mean_with_l2_norms", "WeightedTree", "PendingSum", "set_deferred_sums",
-    "set_lazy_norms", "set_bf16_semantics", "bf16_semantics",
+    "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -206,7 +206,7 @@ def _leaf_rule(dt: torch.dtype, kinds: Sequence[int], scaled_kind: Optional[int]
 def _fold(rows, weights, *, scale=None,
           out: Optional[List[torch.Tensor]] = None, accumulate: bool = False,
           nontemporal: Optional[bool] = None, validated: bool = False,
-          l2sq: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+          l2sq: Optional[torch.Tensor] = None, clip=None) -> List[torch.Tensor]:
     """y_l = [out_l +] sum_k fl(rows[k][l] * w_k) [* scale] for every leaf l, one
     kernel launch per (input, fold, output) dtype group. ``out`` gives the
     destination tensors (fresh ones otherwise); ``accumulate`` folds into them.
@@ -214,11 +214,15 @@ def _fold(rows, weights, *, scale=None,
     pointer table). ``weights``: host weights, or a :class:`_Weights` (already packed).
     ``validated``: rows come from _client_rows / _client_table (shapes and dtypes
     already checked). ``l2sq`` (float32 [K]): also write every client's squared l2 norm
-    over all leaves, from the same pass (fjagg_wsum_l2_ptrs; float leaves of one dtype)."""
+    over all leaves, from the same pass (fjagg_wsum_l2_ptrs; float leaves of one dtype).
+    ``clip`` = (c, l2sq_clipped): the clipped fold (fjagg_wsum_clip_ptrs; float32 leaves): client
+    k's elements are multiplied by the device factor c[k] (float32 [K]) before its weight, and
+    l2sq_clipped (float32 [K] or None) receives the squared norms of those products."""
     if accumulate and out is None:
         raise ValueError("accumulate needs out")
     table = rows if isinstance(rows, _Table) else None
-    if (table is not None and nontemporal is None and isinstance(weights, _Weights) and table.row0):
+    if (clip is None and table is not None and nontemporal is None and isinstance(weights, _Weights)
+            and table.row0):
         outs = _native_fold(table, weights, scale, out, accumulate, l2sq)
         if outs is not None:
             return outs
@@ -260,11 +264,22 @@ def _fold(rows, weights, *, scale=None,
             raise TypeError("fused l2 norms need float leaves of one dtype and a float fold")
         if l2sq.dtype != torch.float32 or l2sq.numel() != K or l2sq.device != device:
             raise ValueError(f"l2sq must be a float32 [{K}] tensor on {device}")
+    if clip is not None:
+        if l2sq is not None:
+            raise ValueError("clip and l2sq are separate folds")
+        if list(groups) != [(_lib.F32, _lib.F32, _lib.F32)]:
+            raise TypeError("the clipped fold needs float32 leaves and a float32 fold")
+        for t in clip:
+            if t is not None and (t.dtype != torch.float32 or t.numel() != K or t.device != device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"clip factors and clipped norms must be contiguous float32 [{K}] tensors on {device}")
     for (in_c, acc_c, out_c), ls in groups.items():
         leaf_n = np.array([rows[0][l].numel() for l in ls], dtype=np.int64)
         if not leaf_n.any():
             if l2sq is not None:
                 l2sq.zero_()
+            if clip is not None and clip[1] is not None:
+                clip[1].zero_()
             continue
         if table is not None:
             in_ptrs = table.ptrs if len(ls) == L else table.ptrs[:, ls]
@@ -273,7 +288,7 @@ def _fold(rows, weights, *, scale=None,
         else:
             in_ptrs = np.array([[rows[k][l].data_ptr() for l in ls] for k in range(K)], dtype=np.int64)
         out_ptrs = np.array([outs[l].data_ptr() for l in ls], dtype=np.int64)
-        narrow = _narrow(K, leaf_n, in_c) and l2sq is None
+        narrow = _narrow(K, leaf_n, in_c) and l2sq is None and clip is None
         svar = 0
         if narrow:
             # k_ptrs_stripe when every pointer is 16-byte aligned (k_ptrs_narrow otherwise)
@@ -301,7 +316,14 @@ def _fold(rows, weights, *, scale=None,
         nblk = len(blocks) // 2
         sc = float(np.float32(scale) if scale is not None else 1.0)
         stream = torch.cuda.current_stream(device).cuda_stream
-        if l2sq is None:
+        if clip is not None:
+            c_dev, sq_dev = clip
+            need = int(_lib.load().fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)) if sq_dev is not None else 0
+            ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+            _lib.call("fjagg_wsum_clip_ptrs", in_c, image_dev.data_ptr(), len(ls), K, nblk, w_dev_ptr,
+                      c_dev.data_ptr(), sc, None if sq_dev is None else sq_dev.data_ptr(), flags, ws.data_ptr(),
+                      ws.numel(), stream)
+        elif l2sq is None:
             _lib.call("fjagg_wsum_ptrs", in_c, acc_c, out_c, image_dev.data_ptr(), len(ls), K, nblk,
                       w_dev_ptr, sc, flags, stream)
         else:
@@ -1747,3 +1769,72 @@ def tree_clip_by_global_norm(pytree_: PyTree, max_norm: float) -> PyTree:
     with np.errstate(divide="ignore", invalid="ignore"):
         scale = np.minimum(np.float32(1), np.float32(max_norm) / norm)
     return _eager(tree_weight(pytree_, np.float32(scale)))
+
+
+class ClippedMean(NamedTuple):
+    """Result of a clipped weighted mean (:func:`tree_clipped_mean`,
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.clipped_mean`): the mean pytree and, per client in
+    input order, the pre-clip l2 norm (float32 [K]), the norm after clipping (float32 [K]) and
+    whether the client was clipped (bool [K]) — the diagnostics of mime_lite.py:139-146."""
+    mean: Any
+    norms: Any
+    clipped_norms: Any
+    clipped: Any
+
+
+def _l2sq_table(ptrs: np.ndarray, leaf_n: np.ndarray, device: torch.device) -> torch.Tensor:
+    """Squared l2 norms (float32 [K]) of K clients' float32 leaves given as a [K, L] pointer
+    table: the fjagg_l2sq_rows route of :func:`tree_l2_norms`, keeping the squares."""
+    K, L = ptrs.shape
+    out = torch.empty(K, dtype=torch.float32, device=device)
+    max_n = int(leaf_n.max()) if leaf_n.size else 0
+    step = max(1, 65535 // L)  # fjagg_l2sq_rows takes up to 65535 rows per call
+    stream = torch.cuda.current_stream(device).cuda_stream
+    for k0 in range(0, K, step):
+        k1 = min(K, k0 + step)
+        image = np.concatenate([ptrs[k0:k1].ravel(), np.tile(leaf_n, k1 - k0)])
+        image_dev = _lib.upload(torch.from_numpy(image), device)
+        R = (k1 - k0) * L
+        need = int(_lib.load().fjagg_l2sq_rows_workspace_bytes(R, max_n))
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+        _lib.call("fjagg_l2sq_rows", _lib.F32, image_dev.data_ptr(), R, max_n, L, 0,
+                  out.data_ptr() + 4 * k0, ws.data_ptr(), ws.numel(), stream)
+    return out
+
+
+def tree_clipped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], max_norm: float) -> ClippedMean:
+    """Weighted mean of client pytrees, each clipped to l2 norm ``max_norm`` first — the
+    running-sum loop of fedjax/algorithms/mime_lite.py:131-149 for a whole round::
+
+        for delta, w in pairs:
+            norm = tree_l2_norm(delta)
+            clipped = tree_clip_by_global_norm(delta, max_norm)   # tree_util.py:117-133
+            clipped_norm = tree_l2_norm(clipped)
+            sum = tree_add(sum, tree_weight(clipped, w))
+        mean = tree_inverse_weight(sum, W)                        # the unclipped W
+
+    in two passes over the deltas (squared norms, then one fold that applies each client's
+    factor before its weight) with the factors formed on the device: no host synchronisation
+    and no clipped copies. The mean is bitwise the reference's sequence given the norms.
+    Float32 leaves, K <= 4096. Returns :class:`ClippedMean`; all-``None`` for no clients."""
+    trees, weights, sum_weight = _collect_pairs(pytrees_and_weights)
+    if not trees:
+        return ClippedMean(None, None, None, None)
+    K = len(trees)
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        z = torch.zeros(K, dtype=torch.float32, device=_default_device())
+        return ClippedMean(pytree.unflatten(td, []), z, z.clone(), torch.zeros_like(z, dtype=torch.bool))
+    if any(x.dtype != torch.float32 for x in rows[0]):
+        raise TypeError("tree_clipped_mean needs float32 leaves (got "
+                        f"{sorted({str(x.dtype) for x in rows[0]})})")
+    if K > _L2_MAX_CLIENTS:
+        raise ValueError(f"tree_clipped_mean supports up to {_L2_MAX_CLIENTS} clients, got {K}")
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    l2sq = _l2sq_table(_ptr_table(rows), leaf_n, device)
+    norms, c = kernels.clip_scales(l2sq, max_norm)
+    l2sq_clipped = torch.empty_like(l2sq)
+    outs = _fold(rows, weights, scale=_inverse(sum_weight), validated=True, clip=(c, l2sq_clipped))
+    clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+    return ClippedMean(pytree.unflatten(td, outs), norms, clipped_norms, clipped)

@@ -14,6 +14,7 @@
  *     tree_sum       tree_util.py:64-73             fjagg_wsum_* with unit weights
  *     tree_add       tree_util.py:47-50             fjagg_wsum_* K=2, unit weights
  *     tree_l2_squared tree_util.py:105-108          fjagg_l2sq_*
+ *     tree_clip_by_global_norm tree_util.py:117-133 fjagg_clip_scales + fjagg_wsum_clip_*
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -48,7 +49,7 @@
 extern "C" {
 #endif
 
-#define FJAGG_ABI_VERSION 3
+#define FJAGG_ABI_VERSION 4
 
 /* element types */
 enum fjagg_dtype {
@@ -314,6 +315,53 @@ int64_t fjagg_l2sq_rows_workspace_bytes(int64_t R, int64_t max_n);
 int fjagg_l2sq_rows(int in_dtype, const int64_t* image_dev, int64_t R, int64_t max_n,
                     int64_t rows_per_group, int take_sqrt, float* out_dev, void* ws_dev,
                     int64_t ws_bytes, void* stream);
+
+/*
+ * Clipped weighted mean: per-client norm clipping inside the fold. Replaces the running-sum
+ * loop of fedjax/algorithms/mime_lite.py:131-149 — tree_l2_norm(delta), tree_clip_by_global_norm
+ * (fedjax/core/tree_util.py:117-133), the clipped norm and flag, then weight and add — for a
+ * whole round, with no host synchronisation and no clipped copies: two passes over the deltas
+ * (squared norms by fjagg_l2sq_*, then the fold). Float32 deltas, fold and output.
+ * With C = f32(max_norm) and q_k client k's squared l2 norm:
+ *     n_k = sqrt_rn(q_k)                          correctly rounded (tree_util.py:111-114)
+ *     r_k = div_rn(C, n_k)                        correctly rounded
+ *     c_k = isnan(r_k) ? r_k : (r_k < 1 ? r_k : 1)   jnp.minimum(1, r): NaN propagates; n = 0 -> 1
+ *     t_k = fl(fl(c_k * x_k[p]) * w_k)            two roundings, no FMA (tree_util.py:133, then :32)
+ *     s_0 = t_0 (fl(out[p] + t_0) with FJAGG_ACCUMULATE); s_k = fl(s_{k-1} + t_k) in client order
+ *     out[p] = fl(s_{K-1} * scale) with FJAGG_SCALE
+ * (fl(fl(c x) w) is not fl(x fl(c w)): the factor cannot be merged into the weight bitwise.)
+ * Flags: FJAGG_SCALE, FJAGG_ACCUMULATE, FJAGG_NONTEMPORAL and, on the pytree path,
+ * FJAGG_UNALIGNED. FJAGG_NARROW, FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, a FJAGG_VARIANT byte,
+ * other dtypes, and K > 4096 with norms return FJAGG_EUNSUPPORTED with nothing launched.
+ */
+/* norm_dev[k] = n_k (norm_dev may be NULL) and c_dev[k] = c_k from l2sq_dev[k] = q_k: one small
+ * launch. Replaces tree_util.py:131-132 for K clients. */
+int fjagg_clip_scales(const float* l2sq_dev, int64_t K, float max_norm, float* norm_dev, float* c_dev,
+                      void* stream);
+/* The dense exact fold of fjagg_wsum_dense with the per-client device factor c_dev[k] applied
+ * before the weight (c_dev is any device vector, not necessarily fjagg_clip_scales'). With
+ * l2sq_clipped_dev (nullable) also l2sq_clipped_dev[k] = sum_p fl(c_k x_k[p])^2, in the
+ * reduction order of fjagg_wsum_l2_dense, its workgroup partials added by a separate combine
+ * launch; ws_dev of fjagg_wsum_clip_workspace_bytes(K, P) bytes is needed only then.
+ * Replaces tree_util.py:133 + :32 + :47-54 inside the loop of mime_lite.py:131-149. */
+int64_t fjagg_wsum_clip_workspace_bytes(int64_t K, int64_t P);
+int fjagg_wsum_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                          const float* w_dev, const float* c_dev, float scale, void* out_dev,
+                          float* l2sq_clipped_dev, int flags, void* ws_dev, int64_t ws_bytes, void* stream);
+/* The same fold on the pytree path: the plan image and blocks of fjagg_ptrs_plan_leaves as
+ * fjagg_wsum_ptrs takes them (per-leaf element units for misaligned leaves included); w_dev
+ * and c_dev are float[K]. ws_dev of fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk) bytes with
+ * l2sq_clipped_dev. Replaces the same reference lines as fjagg_wsum_clip_dense. */
+int64_t fjagg_wsum_clip_ptrs_workspace_bytes(int64_t K, int64_t nblk);
+int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                         const float* w_dev, const float* c_dev, float scale, float* l2sq_clipped_dev,
+                         int flags, void* ws_dev, int64_t ws_bytes, void* stream);
+/* The round's diagnostics (mime_lite.py:139-146): clipped_dev[k] = (c_k != 1), true for NaN as
+ * jnp.not_equal of two NaN norms is; clipped_norm_dev[k] = (c_k == 1) ? norm_dev[k] :
+ * sqrt_rn(l2sq_clipped_dev[k]) — an unclipped client's norm verbatim, so clipped_norm == norm
+ * bit for bit whenever nothing was clipped. Either output may be NULL, not both. */
+int fjagg_clip_finish(const float* norm_dev, const float* c_dev, const float* l2sq_clipped_dev, int64_t K,
+                      float* clipped_norm_dev, uint8_t* clipped_dev, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
