@@ -164,6 +164,18 @@ __device__ __forceinline__ void clip_unit(T (&t)[V], float ck, bool valid) {
   }
 }
 
+// ---------------------------------------------------------------- init policy
+// Where the sum starts. FromFirst (every fold but the grouped one): s_0 = t_0, tree_mean's copy
+// of the first weighted pytree (tree_util.py:89-91); nothing is emitted. FromZero (the grouped
+// fold, fjagg_wsum_group_*): s_0 = fl(+0 + t_0), the first tree_add onto tree_zeros_like
+// (hyp_cluster.py:278-281,289-291) — a product of -0 becomes +0 — with no read of the output.
+struct FromFirst {
+  static constexpr bool kZero = false;
+};
+struct FromZero {
+  static constexpr bool kZero = true;
+};
+
 // ----------------------------------------------------------------- epilogues
 // PlainEpi: the fold's result goes to the output (tree_mean). OptEpi: the mean
 // y = fl(s * scale) feeds the server optimizer step of the round in registers
@@ -243,14 +255,15 @@ struct OptEpi {
 // The output of the unit at input byte offset off is at obase + off / sizeof(IN) *
 // sizeof(OUT) (same element index); valid[j] == false skips unit j's store.
 // CLIP (default NoClip): the per-client factor applied before the weight (clip policy above).
+// INIT (default FromFirst): where the sum starts (init policy above).
 template <int IN, class ACC, int OUT, int V, int E, int U, bool NT, bool BURST = true, class RowFn,
-          class NORM = NoNorm, class EPI = PlainEpi, class CLIP = NoClip>
+          class NORM = NoNorm, class EPI = PlainEpi, class CLIP = NoClip, class INIT = FromFirst>
 __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
                                      const uint32_t (&off)[E],
                                      uint8_t* __restrict__ obase, const bool (&valid)[E],
                                      const typename ACC::T* __restrict__ w, bool do_scale,
                                      float scale, bool accumulate, NORM nrm = NORM(),
-                                     const EPI& epi = EPI(), CLIP clip = CLIP()) {
+                                     const EPI& epi = EPI(), CLIP clip = CLIP(), INIT = INIT()) {
   constexpr int IB = Elem<IN>::B, OB = Elem<OUT>::B;
   auto outp = [&](int j) { return obase + (size_t)(off[j] / IB) * OB; };
   using T = typename ACC::T;
@@ -278,7 +291,10 @@ __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
       clip_unit<CLIP, NORM::kOn>(t, c0, valid[j]);
       if constexpr (NORM::kOn) sq_acc<T, V>(t, q[0]);
 #pragma unroll
-      for (int i = 0; i < V; ++i) acc[j][i] = ACC::mul(t[i], w0);
+      for (int i = 0; i < V; ++i) {
+        acc[j][i] = ACC::mul(t[i], w0);
+        if constexpr (INIT::kZero) acc[j][i] = ACC::add(T(0), acc[j][i]);
+      }
     }
     nrm.template commit<1>(q, 0);
     if (accumulate) {
@@ -834,10 +850,11 @@ __global__ __launch_bounds__(kThreads) void k_dense_opt(
 // when the range gives a lane more than one unit, else in groups of kThreads units
 // (E=1, U=8).
 template <int IN, class ACC, int OUT, int VV, bool NT, bool BURST, class RowFn, class NORM, class EPI,
-          class CLIP = NoClip>
+          class CLIP = NoClip, class INIT = FromFirst>
 __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_t K, int64_t u0, int64_t u1,
                                            uint8_t* ob, const typename ACC::T* __restrict__ w, bool dsc,
-                                           float scale, bool acm, NORM nrm, const EPI& epi, CLIP clip = CLIP()) {
+                                           float scale, bool acm, NORM nrm, const EPI& epi, CLIP clip = CLIP(),
+                                           INIT init = INIT()) {
   constexpr int IB = Elem<IN>::B;
   const int tid = threadIdx.x;
   if (u1 - u0 > (int64_t)kThreads) {
@@ -851,7 +868,8 @@ __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_
         if (!valid[j]) u = u1 - 1;
         off[j] = (uint32_t)(u * (VV * IB));
       }
-      fold<IN, ACC, OUT, VV, 8, 4, NT, BURST>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip);
+      fold<IN, ACC, OUT, VV, 8, 4, NT, BURST>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip,
+                                              init);
     }
     return;
   }
@@ -860,7 +878,7 @@ __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_
     const bool valid[1] = {u < u1};
     if (!valid[0]) u = u1 - 1;
     const uint32_t off[1] = {(uint32_t)(u * (VV * IB))};
-    fold<IN, ACC, OUT, VV, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip);
+    fold<IN, ACC, OUT, VV, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip, init);
   }
 }
 
@@ -998,6 +1016,130 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip(const int64_t* __restric
                                            clip);
   }
   if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
+}
+
+// Grouped fold (fjagg_wsum_group_*; hyp_cluster.py:268-303): every client belongs to at most one
+// of G groups and each group gets the exact sequential fold of its own members, from +0
+// (FromZero). blockIdx.y is a slot; slot y folds group g = gorder[y] (the host orders the slots
+// by descending member count, so the long workgroups are dispatched first; gorder == nullptr:
+// g = y). Device tables: order[M] the members' client indices sorted stably by group, seg[G+1]
+// the groups' offsets into it, wperm[M] the weights in member order, gscale[G].
+// Returns false when the slot has nothing to do (an empty group, or a slot outside [0, G)).
+struct GroupSlot {
+  int g;
+  int64_t m0, n;  // first member, member count
+};
+__device__ __forceinline__ bool group_slot(const int* __restrict__ gorder, const int* __restrict__ seg, int G,
+                                           GroupSlot& s) {
+  s.g = gorder ? gorder[blockIdx.y] : (int)blockIdx.y;
+  if ((unsigned)s.g >= (unsigned)G) return false;
+  s.m0 = seg[s.g];
+  s.n = seg[s.g + 1] - s.m0;
+  return s.n > 0;
+}
+
+// The dense grouped fold: k_dense's unit layout over the parameter axis (block 0 of every slot
+// folds the tail), member j of the group is the slab row order[m0 + j], the output row is
+// out + g * out_stride_bytes. A workgroup of an empty group returns at once and writes nothing.
+// Every slot has the same grid of shares of S units (see launch_dense_group_t).
+template <int V, int E, int U, bool NT, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_dense_group(
+    const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t nunits, int tail_n, const int* __restrict__ order,
+    const int* __restrict__ seg, const float* __restrict__ wperm, const float* __restrict__ gscale,
+    const int* __restrict__ gorder, int G, int do_scale, uint8_t* __restrict__ out, int64_t out_stride_bytes,
+    int64_t S) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  const int tid = threadIdx.x;
+  GroupSlot gs;
+  if (!group_slot(gorder, seg, G, gs)) return;
+  const int* ord = order + gs.m0;
+  const float* w = wperm + gs.m0;
+  const float scale = do_scale ? gscale[gs.g] : 1.0f;
+  uint8_t* ob = out + (int64_t)gs.g * out_stride_bytes;
+  auto row = [=](int64_t j) { return x + (int64_t)ord[j] * ld_bytes; };
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  if (tail_n > 0) {
+    if (b == 0) {
+      if (tid < tail_n) {
+        const int64_t e = nunits * V + tid;
+        const uint32_t off[1] = {(uint32_t)(e * IB)};
+        const bool valid[1] = {true};
+        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, gs.n, off, ob, valid, w, do_scale != 0, scale, false,
+                                         NoNorm(), PlainEpi(), NoClip(), FromZero());
+      }
+      return;
+    }
+    b -= 1;
+  }
+  const int64_t u_begin = b * S;
+  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+    uint32_t off[E];
+    bool valid[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      int64_t u = g + j * kThreads + tid;
+      valid[j] = u < u_end;
+      if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the store is skipped
+      off[j] = (uint32_t)(u * (V * IB));
+    }
+    fold<IN, AccF, OUT, V, E, U, NT, BURST>(row, row_bytes, gs.n, off, ob, valid, w, do_scale != 0, scale, false,
+                                            NoNorm(), PlainEpi(), NoClip(), FromZero());
+  }
+}
+
+// The grouped fold on the pytree path: k_ptrs's plan image and block words (restated, as
+// k_ptrs_clip restates them, so that k_ptrs compiles to the code it always did), one leaf plan
+// for every group. image = in_ptrs[M*L] in member order | out_ptrs[G*L] | leaf_n[L] |
+// blocks[2*nblk]; group g's members start at in_ptrs + seg[g]*L, its outputs are
+// out_ptrs[g*L + leaf]. xcd != 0: the XCD remap of k_ptrs (xcd_plan_index) within the slot.
+template <int V, bool NT, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_ptrs_group(const int64_t* __restrict__ img, int L, int64_t M,
+                                                         const int* __restrict__ seg,
+                                                         const float* __restrict__ wperm,
+                                                         const float* __restrict__ gscale,
+                                                         const int* __restrict__ gorder, int G, int do_scale,
+                                                         int xcd) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  using ACC = AccF;
+  const int tid = threadIdx.x;
+  GroupSlot gs;
+  if (!group_slot(gorder, seg, G, gs)) return;
+  const int64_t* in_ptrs = img + gs.m0 * L;
+  const int64_t* out_ptrs = img + M * L + (int64_t)gs.g * L;
+  const int64_t* leaf_n = img + M * L + (int64_t)G * L;
+  const float* w = wperm + gs.m0;
+  const float scale = do_scale ? gscale[gs.g] : 1.0f;
+  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1);
+  const int64_t u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t nunits = n / V;
+  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);  // rebased as in k_ptrs
+  uint8_t* ob = reinterpret_cast<uint8_t*>(out_ptrs[leaf]) + e_base * Elem<OUT>::B;
+  auto row = [=](int64_t j) { return reinterpret_cast<const uint8_t*>(in_ptrs[j * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((n - e_base) * IB);
+  const bool dsc = do_scale != 0;
+  if (tail) {
+    if (tid < n - nunits * V) {
+      const uint32_t off[1] = {(uint32_t)(tid * IB)};
+      const bool valid[1] = {true};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, gs.n, off, ob, valid, w, dsc, scale, false, NoNorm(),
+                                      PlainEpi(), NoClip(), FromZero());
+    }
+  } else if (V > 1 && elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, ob, w, dsc, scale, false, NoNorm(),
+                                           PlainEpi(), NoClip(), FromZero());
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, ob, w, dsc, scale, false, NoNorm(),
+                                           PlainEpi(), NoClip(), FromZero());
+  }
 }
 
 // Pytree path + server optimizer step in the epilogue (fjagg_server_update_ptrs): the
@@ -2671,6 +2813,205 @@ int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t 
   const L2Out l2{nullptr, nullptr, 0, nullptr};
   return vec ? launch_ptrs_clip<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s)
              : launch_ptrs_clip<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s);
+}
+
+// ------------------------------------------------- grouped weighted mean (fjagg.h)
+namespace {
+// The flags a grouped fold takes; everything else is refused before any launch.
+int group_flags_check(int in_dtype, int flags, int allowed) {
+  if (in_dtype != FJAGG_F32)
+    return fail(FJAGG_EUNSUPPORTED, "grouped fold: float32 deltas, fold and output only");
+  if (flags & FJAGG_NARROW) return fail(FJAGG_EUNSUPPORTED, "grouped fold: no FJAGG_NARROW plans");
+  if (flags & FJAGG_HOST_TABLES)
+    return fail(FJAGG_EUNSUPPORTED, "grouped fold: device tables only (no FJAGG_HOST_TABLES)");
+  if (flags & FJAGG_ZEROED_WS) return fail(FJAGG_EUNSUPPORTED, "grouped fold: no norms (no FJAGG_ZEROED_WS)");
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "grouped fold: every group's sum starts from +0 (no FJAGG_ACCUMULATE)");
+  if (flags & FJAGG_UNBALANCED) return fail(FJAGG_EUNSUPPORTED, "grouped fold: balanced grids only");
+  if (flags & 0xff00) return fail(FJAGG_EUNSUPPORTED, "grouped fold: no kernel variants");
+  if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "grouped fold: unsupported flags 0x%x", flags & ~allowed);
+  return FJAGG_OK;
+}
+
+// The host copies of the member tables, checked before any HIP call: seg[0] = 0, monotone,
+// seg[G] = M, and every member a client of [0, K). *nonempty / *largest: the groups with members
+// and the longest member list (they size the grid and pick the kernel shape).
+int group_tables_check(int64_t K, int64_t M, int64_t G, const int32_t* order_host, const int32_t* seg_host,
+                       int64_t* nonempty, int64_t* largest) {
+  if (G < 1) return fail(FJAGG_EINVAL, "G must be >= 1 (got %lld)", (long long)G);
+  if (G > 65535) return fail(FJAGG_EUNSUPPORTED, "grouped fold: G <= 65535 (got %lld)", (long long)G);
+  if (K < 1 || M < 0 || M > K) return fail(FJAGG_EINVAL, "need K >= 1 and 0 <= M <= K (K=%lld, M=%lld)", (long long)K, (long long)M);
+  if (K > 0x7fffffffll) return fail(FJAGG_EUNSUPPORTED, "grouped fold: K < 2^31");
+  if (!seg_host) return fail(FJAGG_EINVAL, "null host table");
+  if (seg_host[0] != 0) return fail(FJAGG_EINVAL, "seg[0] must be 0 (got %d)", seg_host[0]);
+  *nonempty = *largest = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t n = (int64_t)seg_host[g + 1] - seg_host[g];
+    if (n < 0) return fail(FJAGG_EINVAL, "seg is not monotone at group %lld", (long long)g);
+    *nonempty += n > 0;
+    if (n > *largest) *largest = n;
+  }
+  if (seg_host[G] != M) return fail(FJAGG_EINVAL, "seg[G] = %d, expected M = %lld", seg_host[G], (long long)M);
+  for (int64_t i = 0; order_host && i < M; ++i)  // (the pytree entry has no order table)
+    if (order_host[i] < 0 || order_host[i] >= K)
+      return fail(FJAGG_EINVAL, "order[%lld] = %d is outside [0, %lld)", (long long)i, order_host[i], (long long)K);
+  return FJAGG_OK;
+}
+
+// pick_variant's three shapes, chosen from the parameter axis and the MEAN member count of the
+// non-empty groups (a launch has one shape; its folds are as long as the groups). The client
+// threshold is lower than pick_variant's 32: a slot's workgroups share the chip with the other
+// slots', so a group of 8 members already has G x its own workgroups behind it, and U = 4 needs
+// 1 + 4 members to reach its unrolled loop at all.
+int pick_group_variant(int64_t nunits, int64_t mean_members) {
+  if (mean_members < 8 || nunits < 131072) return 2;  // E=1 x U=8
+  if (nunits < 262144) return 5;                      // E=4 x U=4
+  return 12;                                          // E=8 x U=4
+}
+
+struct GroupArgs {
+  const uint8_t* x;
+  int64_t ld_bytes, nunits;
+  int tail_n;
+  const int32_t *order, *seg, *gorder;
+  const float *wperm, *gscale;
+  int G, do_scale;
+  uint8_t* out;
+  int64_t out_stride;
+  int64_t nonempty;
+};
+
+// The shape a dense grouped fold runs with: 0 = element units (x, out or a row stride is not
+// 16-byte aligned, or P < 4: E=1 x U=8 over single elements), else pick_group_variant's 2 / 5 / 12
+// over 16-byte units. Pure: fjagg_wsum_group_dense launches what this says
+// (fjagg_group_dense_shape reports it).
+int group_dense_shape(const void* x, int64_t ld, int64_t P, int64_t M, int64_t nonempty, int64_t G, const void* y,
+                      int64_t out_ld) {
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0) &&
+                   ((ld * 4) % 16 == 0) && ((out_ld * 4) % 16 == 0 || G == 1) && P >= 4;
+  if (!vec) return 0;
+  return pick_group_variant(P / 4, nonempty > 0 ? M / nonempty : 0);
+}
+
+extern "C++" {
+// The balanced grid of ONE group over the whole chip (S units per workgroup), times G slots: the
+// largest group's workgroups are dispatched first (gorder) and fill every CU; the shorter groups'
+// workgroups take the CUs as they free up.
+template <int V, int E, int U, bool NT, bool BURST>
+int launch_dense_group_t(const GroupArgs& a, hipStream_t s) {
+  auto kern = k_dense_group<V, E, U, NT, BURST>;
+  int64_t S = (int64_t)kThreads * E, nblk = 0;
+  balanced_grid(residency(reinterpret_cast<const void*>(kern)), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
+  if (a.nunits == 0) nblk = 0;
+  const dim3 grid((unsigned)(nblk + (a.tail_n > 0 ? 1 : 0)), (unsigned)a.G);
+  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
+                     a.gscale, a.gorder, a.G, a.do_scale, a.out, a.out_stride, S);
+  return check_launch("k_dense_group");
+}
+
+template <bool NT>
+int launch_dense_group(bool vec, int variant, const GroupArgs& a, hipStream_t s) {
+  if (!vec) return launch_dense_group_t<1, 1, 8, NT, false>(a, s);
+  if (variant == 12) {
+    // the schedule rule of k_dense's E=8 shape, over every slot's tiles
+    const int64_t ntiles = (a.nunits + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
+    if (ntiles * a.nonempty >= 2 * (int64_t)cu_count()) return launch_dense_group_t<4, 8, 4, NT, false>(a, s);
+    return launch_dense_group_t<4, 8, 4, NT, true>(a, s);
+  }
+  if (variant == 5) return launch_dense_group_t<4, 4, 4, NT, false>(a, s);
+  return launch_dense_group_t<4, 1, 8, NT, false>(a, s);
+}
+
+template <int V, bool NT>
+int launch_ptrs_group(const int64_t* img, int L, int64_t M, int64_t nblk, const int32_t* seg, const float* wperm,
+                      const float* gscale, const int32_t* gorder, int G, int ds, int64_t nonempty, hipStream_t s) {
+  const dim3 grid((unsigned)nblk, (unsigned)G), block(kThreads);
+  const int xcd = xcd_remap_bit() ? 1 : 0;
+  if (nblk * nonempty < 2 * (int64_t)cu_count())  // the schedule rule of launch_ptrs_t
+    hipLaunchKernelGGL((k_ptrs_group<V, NT, true>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G, ds,
+                       xcd);
+  else
+    hipLaunchKernelGGL((k_ptrs_group<V, NT, false>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G, ds,
+                       xcd);
+  return check_launch("k_ptrs_group");
+}
+}  // extern "C++"
+}  // namespace
+
+/* per-group exact folds of a slab in one launch (fjagg.h; hyp_cluster.py:268-303) */
+int fjagg_wsum_group_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M, int64_t G,
+                           const int32_t* order_dev, const int32_t* seg_dev, const float* wperm_dev,
+                           const float* gscale_dev, const int32_t* gorder_dev, const int32_t* order_host,
+                           const int32_t* seg_host, void* out_dev, int64_t out_ld, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (M > 0 && !order_host) return fail(FJAGG_EINVAL, "null host table");
+  int64_t nonempty = 0, largest = 0;
+  if (int rc = group_tables_check(K, M, G, order_host, seg_host, &nonempty, &largest)) return rc;
+  if (P < 1 || ld < P || out_ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld and P <= out_ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "grouped fold: rows <= 1 GiB");
+  if (M == 0) return FJAGG_OK;  // every group is empty: nothing is written
+  if (!x_dev || !out_dev || !order_dev || !seg_dev || !wperm_dev || ((flags & FJAGG_SCALE) && !gscale_dev))
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  uint8_t* y = reinterpret_cast<uint8_t*>(out_dev);
+  const int variant = group_dense_shape(x, ld, P, M, nonempty, G, y, out_ld);
+  const bool vec = variant != 0;
+  const int V = vec ? 4 : 1;
+  GroupArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.order = order_dev;
+  a.seg = seg_dev;
+  a.gorder = gorder_dev;
+  a.wperm = wperm_dev;
+  a.gscale = gscale_dev;
+  a.G = (int)G;
+  a.do_scale = (flags & FJAGG_SCALE) ? 1 : 0;
+  a.out = y;
+  a.out_stride = out_ld * 4;
+  a.nonempty = nonempty;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group<true>(vec, variant, a, s)
+                                     : launch_dense_group<false>(vec, variant, a, s);
+}
+
+/* the kernel shape fjagg_wsum_group_dense picks for these arguments (fjagg.h); launches nothing */
+int fjagg_group_dense_shape(const void* x_dev, int64_t ld, int64_t P, int64_t M, int64_t nonempty, int64_t G,
+                            const void* out_dev, int64_t out_ld) {
+  g_err[0] = 0;
+  if (P < 1 || ld < P || out_ld < P || G < 1 || M < 0 || nonempty < 0 || nonempty > G)
+    return fail(FJAGG_EINVAL, "bad shape");
+  return group_dense_shape(x_dev, ld, P, M, nonempty, G, out_dev, out_ld);
+}
+
+/* the same on the pytree path: one launch over every leaf of every group (fjagg.h) */
+int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M, int64_t G,
+                          int64_t nblk, const int32_t* seg_dev, const float* wperm_dev, const float* gscale_dev,
+                          const int32_t* gorder_dev, const int32_t* seg_host, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  int64_t nonempty = 0, largest = 0;
+  // the members are rows of the image here (0 .. M-1 in member order): there is no order table
+  if (int rc = group_tables_check(K, M, G, nullptr, seg_host, &nonempty, &largest)) return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1) return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (M == 0) return FJAGG_OK;
+  if (!image_dev || !seg_dev || !wperm_dev || ((flags & FJAGG_SCALE) && !gscale_dev))
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, g = (int)G;
+  if (vec)
+    return nt ? launch_ptrs_group<4, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
+                                           nonempty, s)
+              : launch_ptrs_group<4, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
+                                            nonempty, s);
+  return nt ? launch_ptrs_group<1, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
+                                         nonempty, s)
+            : launch_ptrs_group<1, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
+                                          nonempty, s);
 }
 
 int fjagg_fill_synth(int dtype, void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t k0,

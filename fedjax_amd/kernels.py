@@ -359,6 +359,123 @@ def clip_finish(norms: torch.Tensor, c: torch.Tensor, l2sq_clipped: torch.Tensor
     return clipped_norms, clipped
 
 
+def check_group_ids(group_ids, K: int, num_groups: int) -> np.ndarray:
+    """``group_ids`` as an int64 [K] array of ids in ``{-1} | [0, num_groups)``; ValueError for
+    anything else (a wrong length, non-integers, ids out of range)."""
+    G = int(num_groups)
+    if G < 1:
+        raise ValueError(f"num_groups must be >= 1, got {num_groups}")
+    ids = np.asarray(group_ids)
+    if ids.ndim != 1 or ids.shape[0] != K:
+        raise ValueError(f"group_ids must hold one id per client ({K}), got shape {ids.shape}")
+    if K and ids.dtype.kind not in "iu":
+        raise ValueError(f"group_ids must be integers, got {ids.dtype}")
+    ids = ids.astype(np.int64)
+    if K and (ids.min() < -1 or ids.max() >= G):
+        raise ValueError(f"group_ids must be -1 or in [0, {G})")
+    return ids
+
+
+class GroupTables:
+    """The member tables of a grouped fold (include/fjagg.h, fjagg_wsum_group_*), built on the
+    host with one stable sort and held on the device as ONE buffer
+    ``order[M] | seg[G+1] | gorder[G] | wperm[M] | gscale[G]`` (4-byte words).
+
+    ``order`` lists the members (clients whose id is not -1) sorted stably by group, so in
+    client order within a group; ``gorder`` lists the groups by descending member count."""
+
+    def __init__(self, w: np.ndarray, ids: np.ndarray, num_groups: int, scales: Optional[np.ndarray]):
+        G = int(num_groups)
+        members = np.flatnonzero(ids >= 0)
+        order = members[np.argsort(ids[members], kind="stable")].astype(np.int32)
+        counts = np.bincount(ids[members], minlength=G)
+        seg = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        gorder = np.argsort(-counts, kind="stable").astype(np.int32)
+        wperm = np.ascontiguousarray(w, dtype=np.float32)[order]
+        gscale = np.ones(G, dtype=np.float32) if scales is None else np.ascontiguousarray(scales, dtype=np.float32)
+        if gscale.shape != (G,):
+            raise ValueError(f"scales must have shape ({G},), got {gscale.shape}")
+        self.G, self.M, self.scaled = G, int(order.size), scales is not None
+        self.order, self.seg, self.gorder = order, seg, gorder
+        self.host = np.concatenate([order, seg, gorder, wperm.view(np.int32), gscale.view(np.int32)])
+        self.dev: Optional[torch.Tensor] = None
+
+    def upload(self, device) -> "GroupTables":
+        """One pinned upload, ordered on the current stream (not capturable: :func:`_lib.upload`)."""
+        if self.dev is None:
+            self.dev = _lib.upload(torch.from_numpy(self.host), device)
+        return self
+
+    def ptrs(self):
+        """Device addresses of (order, seg, gorder, wperm, gscale)."""
+        p, M, G = self.dev.data_ptr(), self.M, self.G
+        return p, p + 4 * M, p + 4 * (M + G + 1), p + 4 * (M + 2 * G + 1), p + 4 * (2 * M + 2 * G + 1)
+
+
+def grouped_sum_dense(x: torch.Tensor, w, group_ids, num_groups: int, *, scales=None,
+                      out: Optional[torch.Tensor] = None, nontemporal: bool = False,
+                      tables: Optional[GroupTables] = None) -> torch.Tensor:
+    """Per-group exact folds of a float32 slab ``x[K, P]`` in ONE launch that reads every member
+    row once (fjagg_wsum_group_dense; the per-cluster sums of hyp_cluster.py:268-303): client k
+    belongs to group ``group_ids[k]`` in ``[0, num_groups)`` or, with -1, to none. Returns
+    ``out[G, P]`` (row stride ``out.stride(0)``) with, for group g's members in client order,
+
+        out[g] = fl(fl(+0 + x_m0 * w_m0) + x_m1 * w_m1 + ...) [* scales[g]]
+
+    ``w``: host float32 weights [K]; ``scales``: host float32 [G] or None. The row of a group
+    without members is NOT written; a client in no group is never loaded. The result allocated
+    here has its rows padded to 16 bytes (a [G, P] view of it is returned); an ``out`` or ``x``
+    whose base or row stride is not 16-byte aligned makes the whole launch walk single elements
+    (:func:`grouped_dense_shape` tells). The member tables go
+    up as one pinned upload (:class:`GroupTables`); pass ``tables`` (already uploaded, built
+    from the same ``w``, ``group_ids`` and ``scales``) to launch without one."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the grouped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    G = int(num_groups)
+    dev = _require_device(x)
+    if tables is None:
+        ids = check_group_ids(group_ids, K, G)
+        if isinstance(w, torch.Tensor):
+            w = w.detach().cpu().numpy()
+        w = np.asarray(w)
+        if w.shape != (K,) or w.dtype != np.float32:
+            raise TypeError(f"w must be host float32 weights of shape ({K},)")
+        tables = GroupTables(w, ids, G, scales)
+    elif tables.G != G or tables.dev is None or (tables.M and int(tables.order.max()) >= K):
+        raise ValueError("tables were built for another grouped fold")
+    if out is None:  # rows padded to 16 bytes, so that the result never forces element units
+        out = torch.empty(G, (P + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :P]
+    if out.dim() != 2 or tuple(out.shape) != (G, P) or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise ValueError(f"out must be a float32 [{G}, {P}] tensor with unit column stride")
+    _require_device(x, out)
+    if tables.M == 0:
+        return out  # every group is empty: nothing to launch, nothing written
+    order_p, seg_p, gorder_p, wperm_p, gscale_p = tables.upload(dev).ptrs()
+    flags = (_lib.SCALE if tables.scaled else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    ld = x.stride(0) if K > 1 else P
+    out_ld = out.stride(0) if G > 1 else P
+    _lib.call("fjagg_wsum_group_dense", _lib.F32, x.data_ptr(), ld, K, P, tables.M, G, order_p, seg_p, wperm_p,
+              gscale_p, gorder_p, tables.order.ctypes.data, tables.seg.ctypes.data, out.data_ptr(), out_ld, flags,
+              _stream_handle(dev))
+    return out
+
+
+def grouped_dense_shape(x: torch.Tensor, out: torch.Tensor, tables: GroupTables) -> int:
+    """The kernel shape :func:`grouped_sum_dense` runs with for ``x`` [K, P], ``out`` [G, P] and
+    these tables (fjagg_group_dense_shape; nothing is launched): 0 = single-element units, else
+    16-byte units with 2 = E=1 x U=8, 5 = E=4 x U=4, 12 = E=8 x U=4."""
+    K, P = x.shape
+    nonempty = int((np.diff(tables.seg) > 0).sum())
+    rc = _lib.load().fjagg_group_dense_shape(x.data_ptr(), x.stride(0) if K > 1 else P, P, tables.M, nonempty,
+                                             tables.G, out.data_ptr(), out.stride(0) if tables.G > 1 else P)
+    if rc < 0:
+        _lib.check(rc, "fjagg_group_dense_shape")
+    return rc
+
+
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:
     """Synthetic deltas x[k, p] = amp * u(seed, k0 + k, p) (tests/bench only)."""
     if x.dim() != 2 or x.stride(1) != 1:

@@ -164,6 +164,64 @@ class ClientDeltaSlab:
         clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
         return tree_util.ClippedMean(self.unflatten(flat), norms, clipped_norms, clipped)
 
+    def grouped_mean(self, weights: Sequence, group_ids: Sequence[int], num_groups: int, *,
+                     out: Optional[torch.Tensor] = None) -> list:
+        """Per-group weighted means of the rows in ONE pass over the slab: the expectation step
+        of fedjax/algorithms/hyp_cluster.py:268-303. Client k belongs to group ``group_ids[k]``
+        in ``[0, num_groups)``, or to none with -1 (a dropped or unsampled client: its row is
+        never loaded, so its inf or NaN touch nothing). For each group, in client order,
+
+            W_g = sum of its members' weights; s = +0; s = s + x_m * w_m; mean_g = s * f32(1/W_g)
+
+        the reference's running sum onto ``tree_zeros_like`` (so a sum of -0 products is +0).
+        Returns a list of ``num_groups`` pytrees of the template's structure — views into one
+        ``[G, row_stride]`` result (``out`` if given) — with ``None`` for every group whose total
+        weight is not > 0 (no members, a zero, negative or NaN total; hyp_cluster.py:298-302);
+        such a group's row of the result is not written. A float32 slab; no host synchronisation.
+
+        The member tables travel as one pinned upload, which a graph capture cannot record
+        safely; the tables of the latest call stay on the device, so a capture of the SAME
+        weights and ids (after one eager call) launches without an upload and replays with
+        rewritten deltas; any other capture is refused. A later call on another stream waits
+        for the upload through an event; a capture cannot wait on an event recorded outside
+        it, so the upload must be complete when the capture begins (``torch.cuda.graph``
+        synchronises the device on entry; with ``CUDAGraph.capture_begin`` synchronise first)."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"grouped_mean needs a float32 slab, not {self.dtype}")
+        K, G = self.num_clients, int(num_groups)
+        ids = kernels.check_group_ids(group_ids, K, G)
+        w = self.host_weights(weights)
+        totals = [0] * G  # W_g summed as hyp_cluster.py:282,292 does, from the int 0
+        for k in np.flatnonzero(ids >= 0):
+            totals[ids[k]] += tree_util._host_weight(weights[k])
+        alive = np.array([bool(W > 0) for W in totals])
+        ids = np.where((ids >= 0) & alive[np.maximum(ids, 0)], ids, -1)  # a group without a mean is not folded
+        scales = np.array([np.float32(tree_util._inverse(W)) if a else 0 for W, a in zip(totals, alive)], np.float32)
+        key = (w.tobytes(), ids.tobytes(), scales.tobytes())
+        cached = getattr(self, "_group_tables", None)
+        capturing = torch.cuda.is_current_stream_capturing()
+        stream = torch.cuda.current_stream(self.device)
+        if cached is not None and cached[0] == key:
+            tables, up_stream, uploaded = cached[1:]
+            if capturing:  # the graph reads this buffer on every replay: it lives as long as the slab
+                self._captured_tables = getattr(self, "_captured_tables", []) + [tables]
+            elif stream != up_stream:  # uploaded on another stream: this one waits for the copy
+                stream.wait_event(uploaded)
+        else:
+            tables = kernels.GroupTables(w, ids, G, scales).upload(self.device)  # (refused under capture)
+            uploaded = torch.cuda.Event()
+            uploaded.record(stream)
+            self._group_tables = (key, tables, stream, uploaded)
+        if out is None:
+            out = torch.empty(G, self.row_stride, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != (G, self.row_stride) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 [{G}, {self.row_stride}] tensor")
+        rows = self.rows
+        nbytes = tables.M * self.num_params * 4
+        kernels.grouped_sum_dense(rows, w, ids, G, out=out[:, : self.num_params], tables=tables,
+                                  nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return [self.unflatten(out[g]) if alive[g] else None for g in range(G)]
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

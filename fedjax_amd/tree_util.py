@@ -44,6 +44,7 @@ __all__ = [
     "tree_mean", "tree_size", "tree_l2_squared", "tree_l2_norm", "tree_clip_by_global_norm",
     "tree_l2_norms", "tree_mean_with_l2_norms", "WeightedTree", "PendingSum", "set_deferred_sums",
     "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
+    "tree_grouped_mean",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -1838,3 +1839,67 @@ def tree_clipped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], max_n
     outs = _fold(rows, weights, scale=_inverse(sum_weight), validated=True, clip=(c, l2sq_clipped))
     clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
     return ClippedMean(pytree.unflatten(td, outs), norms, clipped_norms, clipped)
+
+
+def tree_grouped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], group_ids: Sequence[int],
+                      num_groups: int) -> List[Optional[PyTree]]:
+    """Per-group weighted means of client pytrees — the expectation step of
+    fedjax/algorithms/hyp_cluster.py:268-303, one running sum per cluster::
+
+        sums = [tree_zeros_like(params) for _ in range(G)]; totals = [0] * G
+        for (delta, w), g in zip(pairs, group_ids):
+            sums[g] = tree_add(sums[g], tree_weight(delta, w)); totals[g] += w
+        [tree_inverse_weight(s, W) if W > 0 else None for s, W in zip(sums, totals)]
+
+    in ONE launch over every leaf of every group, reading each member's leaves once.
+    ``group_ids[k]`` is client k's group in ``[0, num_groups)``, or -1 for a client in no group
+    (never loaded). Each sum starts from +0 as the reference's does, so it is not always
+    ``tree_mean`` of the group's members: products that are all -0 sum to +0. Returns a list of
+    ``num_groups`` pytrees, ``None`` for every group whose total weight is not > 0 (no members,
+    a zero, negative or NaN total). Float32 leaves. No clients: ``[None] * num_groups``."""
+    pairs = pytrees_and_weights if type(pytrees_and_weights) is list else list(pytrees_and_weights)
+    trees = [tree for tree, _ in pairs]
+    hw = [_host_weight(weight) for _, weight in pairs]
+    K = len(trees)
+    ids = kernels.check_group_ids(group_ids, K, num_groups)
+    G = int(num_groups)
+    if not trees:
+        return [None] * G
+    td, rows = _client_table(trees)
+    if any(x.dtype != torch.float32 for x in rows[0]):
+        raise TypeError("tree_grouped_mean needs float32 leaves (got "
+                        f"{sorted({str(x.dtype) for x in rows[0]})})")
+    totals = [0] * G  # hyp_cluster.py:282,292
+    for k in np.flatnonzero(ids >= 0):
+        totals[ids[k]] += hw[k]
+    alive = [bool(W > 0) for W in totals]
+    if not rows[0]:
+        return [pytree.unflatten(td, []) if a else None for a in alive]
+    ids = np.where((ids >= 0) & np.array(alive)[np.maximum(ids, 0)], ids, -1)  # no mean: not folded
+    scales = np.array([np.float32(_inverse(W)) if a else 0 for W, a in zip(totals, alive)], np.float32)
+    tables = kernels.GroupTables(np.array([np.float32(w) for w in hw], np.float32), ids, G, scales)
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    L, M = len(leaf_n), tables.M
+    # one [G, row] result: every leaf of every group at a 16-byte aligned offset of its row
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)])
+    flat = torch.empty(G, max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = [pytree.unflatten(td, [flat[g, o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+              if alive[g] else None for g in range(G)]
+    if M == 0 or not leaf_n.any():
+        return result
+    in_ptrs = _ptr_table(rows)[tables.order]  # [M, L] in member order
+    out_ptrs = flat.data_ptr() + 4 * (np.arange(G, dtype=np.int64)[:, None] * flat.stride(0) + offs[None, :-1])
+    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)
+    t32 = tables.host[M:]  # seg | gorder | wperm | gscale (the members are rows of the image: no order table)
+    words = np.zeros((t32.size + 1) // 2, dtype=np.int64)
+    words.view(np.int32)[: t32.size] = t32
+    image = np.concatenate([in_ptrs.ravel(), out_ptrs.ravel(), leaf_n, blocks, words])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    seg_p = image_dev.data_ptr() + 8 * (image.size - words.size)
+    gorder_p, wperm_p, gscale_p = seg_p + 4 * (G + 1), seg_p + 4 * (2 * G + 1), seg_p + 4 * (2 * G + 1 + M)
+    nt = int(leaf_n.sum()) * M * 4 >= NONTEMPORAL_MIN_BYTES
+    _lib.call("fjagg_wsum_group_ptrs", _lib.F32, image_dev.data_ptr(), L, K, M, G, len(blocks) // 2, seg_p, wperm_p,
+              gscale_p, gorder_p, tables.seg.ctypes.data, _lib.SCALE | (_lib.NONTEMPORAL if nt else 0),
+              torch.cuda.current_stream(device).cuda_stream)
+    return result

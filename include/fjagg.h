@@ -15,6 +15,7 @@
  *     tree_add       tree_util.py:47-50             fjagg_wsum_* K=2, unit weights
  *     tree_l2_squared tree_util.py:105-108          fjagg_l2sq_*
  *     tree_clip_by_global_norm tree_util.py:117-133 fjagg_clip_scales + fjagg_wsum_clip_*
+ *     expectation_step algorithms/hyp_cluster.py:268-303  fjagg_wsum_group_* (per-cluster means)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -362,6 +363,59 @@ int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t 
  * bit for bit whenever nothing was clipped. Either output may be NULL, not both. */
 int fjagg_clip_finish(const float* norm_dev, const float* c_dev, const float* l2sq_clipped_dev, int64_t K,
                       float* clipped_norm_dev, uint8_t* clipped_dev, void* stream);
+
+/*
+ * Grouped weighted mean: the per-cluster means of HypCluster's expectation step in one fold.
+ * Replaces the G interleaved running sums of fedjax/algorithms/hyp_cluster.py:268-303 —
+ * tree_zeros_like per cluster (:278-281), tree_add(sum[c], tree_weight(delta, n)) per client
+ * (:289-291), tree_inverse_weight per cluster (:300) — with one launch that reads every
+ * member's delta once. Float32 deltas, fold and output. Each of the K clients belongs to at
+ * most one of G groups; the M <= K members are listed in member order (sorted stably by group,
+ * so client order within a group):
+ *     order[M]   the members' client indices        seg[G+1]  group g's members are
+ *     wperm[M]   f32 weights in member order                  order[seg[g] .. seg[g+1])
+ *     gscale[G]  f32(1 / W_g), read with FJAGG_SCALE gorder[G] optional: slot y of the grid folds
+ *                                                             group gorder[y] (a permutation of
+ *                                                             [0, G), longest groups first)
+ * For group g with members m_0 < m_1 < ... and every element p:
+ *     s = +0;  s = fl(s + fl(x_m[p] * w_m)) for each member in order (no FMA)
+ *     out_g[p] = fl(s * gscale[g]) with FJAGG_SCALE, else s
+ * The sum starts from +0 (tree_zeros_like), so a group whose products are all -0 gives +0 where
+ * fjagg_wsum_* over the same members gives -0; the output is never read. A group without
+ * members writes nothing, and a client in no group is never loaded. Whether a group has a mean
+ * at all (hyp_cluster.py:298-302: only when its total weight is > 0) is the caller's decision:
+ * leave such a group's segment empty.
+ * Tables: the device copies are what the kernels read; the entries also take the HOST copies of
+ * seg (and, dense, order) and check them before any HIP call — FJAGG_EINVAL when G < 1, seg[0]
+ * != 0, seg is not monotone, seg[G] != M, or an order entry is outside [0, K). The caller keeps
+ * the two copies equal (fedjax_amd builds both from one array).
+ * Flags: FJAGG_SCALE, FJAGG_NONTEMPORAL and, on the pytree path, FJAGG_UNALIGNED. FJAGG_NARROW,
+ * FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, FJAGG_ACCUMULATE, FJAGG_UNBALANCED, a FJAGG_VARIANT byte
+ * and other dtypes return FJAGG_EUNSUPPORTED with nothing launched. G <= 65535.
+ */
+/* Dense: client k's row at x_dev + k*ld elements, group g's result at out_dev + g*out_ld. */
+int fjagg_wsum_group_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M,
+                           int64_t G, const int32_t* order_dev, const int32_t* seg_dev,
+                           const float* wperm_dev, const float* gscale_dev, const int32_t* gorder_dev,
+                           const int32_t* order_host, const int32_t* seg_host, void* out_dev,
+                           int64_t out_ld, int flags, void* stream);
+/* The kernel shape fjagg_wsum_group_dense runs with for these arguments (nothing is launched;
+ * M members in `nonempty` non-empty groups): 0 = single-element units, E=1 x U=8 — x_dev, out_dev
+ * or a row stride (ld; out_ld when G > 1) is not 16-byte aligned, or P < 4 — else 16-byte units
+ * with the FJAGG_VARIANT number of the shape: 2 (E=1 x U=8: fewer than 8 members per group on
+ * average, or fewer than 128 Ki units), 5 (E=4 x U=4: below 256 Ki units), 12 (E=8 x U=4).
+ * A caller that wants the 16-byte path pads its row strides to 4 elements. The shapes serve the
+ * same lines of hyp_cluster.py:268-303; negative FJAGG_E* on a bad shape. */
+int fjagg_group_dense_shape(const void* x_dev, int64_t ld, int64_t P, int64_t M, int64_t nonempty, int64_t G,
+                            const void* out_dev, int64_t out_ld);
+/* Pytree path (the same lines of hyp_cluster.py:268-303 over separate leaves): the image is
+ *     in_ptrs[M*L] member i, leaf l at i*L + l | out_ptrs[G*L] | leaf_n[L] | blocks[2*nblk]
+ * with the blocks of fjagg_ptrs_plan_leaves (one leaf plan serves every group; mark a leaf
+ * unaligned when any member's or any group's pointer to it is). K only bounds M. */
+int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M, int64_t G,
+                          int64_t nblk, const int32_t* seg_dev, const float* wperm_dev,
+                          const float* gscale_dev, const int32_t* gorder_dev, const int32_t* seg_host,
+                          int flags, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
