@@ -1458,7 +1458,19 @@ __global__ __launch_bounds__(kThreads) void k_l2sq_rows(const int64_t* __restric
   const int64_t e0 = (int64_t)blockIdx.x * per;
   const int64_t e1 = (e0 + per < n) ? e0 + per : n;
   float s = 0.f;
-  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
+  int64_t e = e0 + threadIdx.x;
+  // eight loads in flight per lane; the squares are added in the same (ascending) order as the
+  // one-element loop below, so the sum has the same bits
+  constexpr int kAhead = 8;
+  for (; e + (kAhead - 1) * (int64_t)kThreads < e1; e += kAhead * (int64_t)kThreads) {
+    float t[kAhead][1];
+#pragma unroll
+    for (int j = 0; j < kAhead; ++j)
+      decode<IN, AccF, 1>(load_unit_ptr<IN, 1, false>(x + (e + j * (int64_t)kThreads) * IB), t[j]);
+#pragma unroll
+    for (int j = 0; j < kAhead; ++j) s = __fadd_rn(s, __fmul_rn(t[j][0], t[j][0]));
+  }
+  for (; e < e1; e += kThreads) {
     float t[1];
     decode<IN, AccF, 1>(load_unit_ptr<IN, 1, false>(x + e * IB), t);
     s = __fadd_rn(s, __fmul_rn(t[0], t[0]));
@@ -2592,9 +2604,10 @@ int fjagg_l2sq_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int
 }
 
 int64_t fjagg_l2sq_rows_workspace_bytes(int64_t R, int64_t max_n) {
-  if (R < 1 || max_n < 1) return 0;
+  if (R < 1 || max_n < 0) return 0;
   const int64_t per = 64 * 1024;
-  return R * ((max_n + per - 1) / per) * 4;
+  // rows that are all empty (max_n == 0) still take one partial each: fjagg_l2sq_rows's own need
+  return R * (max_n > 0 ? (max_n + per - 1) / per : 1) * 4;
 }
 
 int fjagg_l2sq_rows(int in_dtype, const int64_t* image_dev, int64_t R, int64_t max_n,

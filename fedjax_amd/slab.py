@@ -142,7 +142,9 @@ class ClientDeltaSlab:
         whole round, with the reference's W and f32(1/W) — clipping does not change W.
 
         Two passes over the slab and three small launches, no host synchronisation and no
-        clipped copy: the squared norms, the clip factors ``c = min(1, max_norm / norm)`` on
+        clipped copy: the squared norms (summed leaf by leaf, in :func:`tree_util.tree_clipped_mean`'s
+        order, so that both routes form the same norms, factors and mean bit for bit over the
+        same deltas), the clip factors ``c = min(1, max_norm / norm)`` on
         the device, the fold ``fl(fl(c_k x) w_k)`` with the clipped squares from the same
         pass, their combine, and the diagnostics. Returns a
         :class:`~fedjax_amd.tree_util.ClippedMean`; a float32 slab of up to 4096 clients."""
@@ -155,8 +157,20 @@ class ClientDeltaSlab:
             W += tree_util._host_weight(x)
         scale = tree_util._inverse(W)
         rows = self.rows
+        if self.num_params == 0:  # a template of empty leaves: every norm is 0, nothing to fold
+            if len(weights) != self.num_clients:
+                raise ValueError(f"need {self.num_clients} weights, got {len(weights)}")
+            zeros = torch.zeros(self.num_clients, dtype=torch.float32, device=self.device)
+            norms, c = kernels.clip_scales(zeros, max_norm)
+            clipped_norms, clipped = kernels.clip_finish(norms, c, zeros)
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            return tree_util.ClippedMean(self.unflatten(flat), norms, clipped_norms, clipped)
         w_dev = self.weight_vector(weights)
-        norms, c = kernels.clip_scales(kernels.l2_squared_dense(rows), max_norm)
+        # every leaf of every row as a row of fjagg_l2sq_rows: the pytree route's reduction order
+        leaf_ptrs = self.storage.data_ptr() + 4 * (np.arange(self.num_clients, dtype=np.int64)[:, None] * self.row_stride
+                                                   + self.offsets[None, :-1])
+        l2sq = tree_util._l2sq_table(leaf_ptrs, np.array(self.sizes, dtype=np.int64), self.device)
+        norms, c = kernels.clip_scales(l2sq, max_norm)
         nbytes = rows.numel() * rows.element_size()
         flat, l2sq_clipped = kernels.clipped_sum_dense(
             rows, w_dev, c, scale=float(np.float32(scale)), out=out,
@@ -218,8 +232,9 @@ class ClientDeltaSlab:
             raise ValueError(f"out must be a contiguous float32 [{G}, {self.row_stride}] tensor")
         rows = self.rows
         nbytes = tables.M * self.num_params * 4
-        kernels.grouped_sum_dense(rows, w, ids, G, out=out[:, : self.num_params], tables=tables,
-                                  nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        if self.num_params:  # (a template of empty leaves: the means are empty too, nothing to fold)
+            kernels.grouped_sum_dense(rows, w, ids, G, out=out[:, : self.num_params], tables=tables,
+                                      nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return [self.unflatten(out[g]) if alive[g] else None for g in range(G)]
 
     def l2_norms(self) -> torch.Tensor:

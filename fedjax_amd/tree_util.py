@@ -1673,15 +1673,18 @@ def _l2_rows(rows: List[List[torch.Tensor]], take_sqrt: bool) -> torch.Tensor:
                 raise TypeError(f"l2 norms support float32/bfloat16 leaves, not {x.dtype}")
     if any(x.dtype != rows[0][0].dtype for row in rows for x in row):
         raise TypeError("l2 norms need one leaf dtype across the tree")
-    ptrs = np.array([x.data_ptr() for row in rows for x in row], dtype=np.int64)
-    ns = np.array([x.numel() for row in rows for x in row], dtype=np.int64)
-    image_dev = _lib.upload(torch.from_numpy(np.concatenate([ptrs, ns])), device)
-    max_n = int(ns.max()) if ns.size else 0
-    need = int(_lib.load().fjagg_l2sq_rows_workspace_bytes(K * L, max_n))
-    ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
-    _lib.call("fjagg_l2sq_rows", kernels.dtype_code(rows[0][0].dtype), image_dev.data_ptr(), K * L,
-              max_n, L, 1 if take_sqrt else 0, out.data_ptr(), ws.data_ptr(), ws.numel(),
-              torch.cuda.current_stream(device).cuda_stream)
+    step = max(1, 65535 // L)  # fjagg_l2sq_rows takes up to 65535 rows per call
+    for k0 in range(0, K, step):
+        part = rows[k0:k0 + step]
+        ptrs = np.array([x.data_ptr() for row in part for x in row], dtype=np.int64)
+        ns = np.array([x.numel() for row in part for x in row], dtype=np.int64)
+        image_dev = _lib.upload(torch.from_numpy(np.concatenate([ptrs, ns])), device)
+        max_n = int(ns.max()) if ns.size else 0
+        need = int(_lib.load().fjagg_l2sq_rows_workspace_bytes(len(part) * L, max_n))
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+        _lib.call("fjagg_l2sq_rows", kernels.dtype_code(rows[0][0].dtype), image_dev.data_ptr(), len(part) * L,
+                  max_n, L, 1 if take_sqrt else 0, out.data_ptr() + 4 * k0, ws.data_ptr(), ws.numel(),
+                  torch.cuda.current_stream(device).cuda_stream)
     return out
 
 
