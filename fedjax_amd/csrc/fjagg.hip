@@ -1142,6 +1142,126 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_group(const int64_t* __restri
   }
 }
 
+// Grouped fold + the server optimizer step of every cluster in the epilogue
+// (fjagg_server_update_group_*; hyp_cluster.py:107-128): group g's mean stays in registers and
+// updates g's OWN params and moments with g's OWN descriptor opts[g] (the clusters' step counts
+// differ once a cluster has sat out a round, so their bias corrections and scheduled learning
+// rates do). The descriptor and the state addresses are wave-uniform loads indexed by the
+// slot's group; nothing is written through them but OptEpi::apply's per-element stores.
+// k_dense_group's unit layout, slot order, tables and FromZero start (restated, as k_ptrs_clip
+// restates k_ptrs, so that k_dense_group compiles to the code it always did).
+// state[4G]: params | m | v | mean address of group g at state[4g ..] (0 where absent). A slot
+// without members, or whose params address is 0, returns at once: nothing of it is read or
+// written.
+__device__ __forceinline__ float* f32_at(int64_t addr, int64_t e) {
+  return addr ? reinterpret_cast<float*>(addr) + e : nullptr;
+}
+
+template <int V, int E, int U, bool NT, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_dense_group_opt(
+    const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t nunits, int tail_n, const int* __restrict__ order,
+    const int* __restrict__ seg, const float* __restrict__ wperm, const float* __restrict__ gscale,
+    const int* __restrict__ gorder, int G, int64_t S, const fjagg_server_opt* __restrict__ opts,
+    const int64_t* __restrict__ state) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  const int tid = threadIdx.x;
+  GroupSlot gs;
+  if (!group_slot(gorder, seg, G, gs)) return;
+  const int64_t* st = state + 4 * (int64_t)gs.g;
+  if (st[0] == 0) return;
+  const OptEpi epi{opts[gs.g], f32_at(st[0], 0), f32_at(st[1], 0), f32_at(st[2], 0), f32_at(st[3], 0)};
+  const int* ord = order + gs.m0;
+  const float* w = wperm + gs.m0;
+  const float scale = gscale[gs.g];
+  auto row = [=](int64_t j) { return x + (int64_t)ord[j] * ld_bytes; };
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  if (tail_n > 0) {
+    if (b == 0) {
+      if (tid < tail_n) {
+        const int64_t e = nunits * V + tid;
+        const uint32_t off[1] = {(uint32_t)(e * IB)};
+        const bool valid[1] = {true};
+        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false, NoNorm(),
+                                         epi, NoClip(), FromZero());
+      }
+      return;
+    }
+    b -= 1;
+  }
+  const int64_t u_begin = b * S;
+  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+    uint32_t off[E];
+    bool valid[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      int64_t u = g + j * kThreads + tid;
+      valid[j] = u < u_end;
+      if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the epilogue is skipped
+      off[j] = (uint32_t)(u * (V * IB));
+    }
+    fold<IN, AccF, OUT, V, E, U, NT, BURST>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false,
+                                            NoNorm(), epi, NoClip(), FromZero());
+  }
+}
+
+// The same on the pytree path: k_ptrs_group's image with out_ptrs[G*L] = the clusters' params
+// leaves, and state[G*3*L] = per group m | v | mean leaf addresses as k_ptrs_opt lays out
+// state[3L] (0 where absent). Each workgroup owns one leaf's unit range of one group, so its
+// OptEpi points at that group's leaf and indexes it by the element within the leaf.
+template <int V, bool NT, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_ptrs_group_opt(const int64_t* __restrict__ img, int L, int64_t M,
+                                                             const int* __restrict__ seg,
+                                                             const float* __restrict__ wperm,
+                                                             const float* __restrict__ gscale,
+                                                             const int* __restrict__ gorder, int G, int xcd,
+                                                             const fjagg_server_opt* __restrict__ opts,
+                                                             const int64_t* __restrict__ state) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  using ACC = AccF;
+  const int tid = threadIdx.x;
+  GroupSlot gs;
+  if (!group_slot(gorder, seg, G, gs)) return;
+  const int64_t* in_ptrs = img + gs.m0 * L;
+  const int64_t* out_ptrs = img + M * L + (int64_t)gs.g * L;
+  const int64_t* leaf_n = img + M * L + (int64_t)G * L;
+  const int64_t* st = state + (int64_t)gs.g * 3 * L;
+  const float* w = wperm + gs.m0;
+  const float scale = gscale[gs.g];
+  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1);
+  const int64_t u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t nunits = n / V;
+  // rebased at the workgroup's first element, as in k_ptrs (the epilogue's element index too)
+  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);
+  if (out_ptrs[leaf] == 0) return;
+  const OptEpi epi{opts[gs.g], f32_at(out_ptrs[leaf], e_base), f32_at(st[leaf], e_base),
+                   f32_at(st[L + leaf], e_base), f32_at(st[2 * L + leaf], e_base)};
+  auto row = [=](int64_t j) { return reinterpret_cast<const uint8_t*>(in_ptrs[j * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((n - e_base) * IB);
+  if (tail) {
+    if (tid < n - nunits * V) {
+      const uint32_t off[1] = {(uint32_t)(tid * IB)};
+      const bool valid[1] = {true};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false, NoNorm(), epi,
+                                      NoClip(), FromZero());
+    }
+  } else if (V > 1 && elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, nullptr, w, true, scale, false, NoNorm(),
+                                           epi, NoClip(), FromZero());
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, nullptr, w, true, scale, false, NoNorm(),
+                                           epi, NoClip(), FromZero());
+  }
+}
+
 // Pytree path + server optimizer step in the epilogue (fjagg_server_update_ptrs): the
 // plan image of k_ptrs with out_ptrs[L] = the params leaves; state[3L] = m | v | mean leaf
 // pointers (0 where absent). Each workgroup owns one leaf's unit range, so its OptEpi
@@ -3025,6 +3145,163 @@ int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t
                                          nonempty, s)
             : launch_ptrs_group<1, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
                                           nonempty, s);
+}
+
+// ------------------------- grouped fold + per-cluster server step (fjagg.h; hyp_cluster.py:107-128)
+namespace {
+extern "C++" {
+// What both entries refuse before any HIP call, beyond group_flags_check: a fold without the
+// scale (the step needs the mean), and for every group that will be folded a bad descriptor, a
+// null params address (params(g, l) over l < nl), or a null m / v the rule reads.
+template <class ParamsFn, class StateFn>
+int group_opt_check(int64_t G, const int32_t* seg_host, const fjagg_server_opt* opts_host, int flags, int64_t nl,
+                    ParamsFn params, StateFn state) {
+  if (!(flags & FJAGG_SCALE)) return fail(FJAGG_EINVAL, "grouped server update: FJAGG_SCALE is mandatory (the step takes the mean)");
+  if (!opts_host) return fail(FJAGG_EINVAL, "null host table");
+  for (int64_t g = 0; g < G; ++g) {
+    if (seg_host[g + 1] <= seg_host[g]) continue;  // not folded: nothing of it is read
+    const fjagg_server_opt& o = opts_host[g];
+    if (!opt_valid(&o)) return fail(FJAGG_EINVAL, "grouped server update: bad optimizer descriptor of group %lld", (long long)g);
+    for (int64_t l = 0; l < nl; ++l) {
+      if (!params(g, l)) return fail(FJAGG_EINVAL, "grouped server update: group %lld has a null params address", (long long)g);
+      if (opt_needs_m(o) && !state(g, 0, l)) return fail(FJAGG_EINVAL, "grouped server update: group %lld: optimizer state m is null", (long long)g);
+      if (opt_needs_v(o) && !state(g, 1, l)) return fail(FJAGG_EINVAL, "grouped server update: group %lld: optimizer state v is null", (long long)g);
+    }
+  }
+  return FJAGG_OK;
+}
+
+// launch_dense_group_t's grid: the balanced grid of one group times G slots
+template <int V, int E, int U, bool NT, bool BURST>
+int launch_dense_group_opt_t(const GroupArgs& a, const fjagg_server_opt* opts, const int64_t* state, hipStream_t s) {
+  auto kern = k_dense_group_opt<V, E, U, NT, BURST>;
+  int64_t S = (int64_t)kThreads * E, nblk = 0;
+  balanced_grid(residency(reinterpret_cast<const void*>(kern)), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
+  if (a.nunits == 0) nblk = 0;
+  const dim3 grid((unsigned)(nblk + (a.tail_n > 0 ? 1 : 0)), (unsigned)a.G);
+  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
+                     a.gscale, a.gorder, a.G, S, opts, state);
+  return check_launch("k_dense_group_opt");
+}
+
+// launch_dense_group's shapes and E=8 schedule rule
+template <bool NT>
+int launch_dense_group_opt(bool vec, int variant, const GroupArgs& a, const fjagg_server_opt* opts,
+                           const int64_t* state, hipStream_t s) {
+  if (!vec) return launch_dense_group_opt_t<1, 1, 8, NT, false>(a, opts, state, s);
+  if (variant == 12) {
+    const int64_t ntiles = (a.nunits + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
+    if (ntiles * a.nonempty >= 2 * (int64_t)cu_count())
+      return launch_dense_group_opt_t<4, 8, 4, NT, false>(a, opts, state, s);
+    return launch_dense_group_opt_t<4, 8, 4, NT, true>(a, opts, state, s);
+  }
+  if (variant == 5) return launch_dense_group_opt_t<4, 4, 4, NT, false>(a, opts, state, s);
+  return launch_dense_group_opt_t<4, 1, 8, NT, false>(a, opts, state, s);
+}
+
+// launch_ptrs_group's schedule rule
+template <int V, bool NT>
+int launch_ptrs_group_opt(const int64_t* img, int L, int64_t M, int64_t nblk, const int32_t* seg, const float* wperm,
+                          const float* gscale, const int32_t* gorder, int G, int64_t nonempty,
+                          const fjagg_server_opt* opts, const int64_t* state, hipStream_t s) {
+  const dim3 grid((unsigned)nblk, (unsigned)G), block(kThreads);
+  const int xcd = xcd_remap_bit() ? 1 : 0;
+  if (nblk * nonempty < 2 * (int64_t)cu_count())
+    hipLaunchKernelGGL((k_ptrs_group_opt<V, NT, true>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G,
+                       xcd, opts, state);
+  else
+    hipLaunchKernelGGL((k_ptrs_group_opt<V, NT, false>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G,
+                       xcd, opts, state);
+  return check_launch("k_ptrs_group_opt");
+}
+}  // extern "C++"
+}  // namespace
+
+/* one HypCluster round of a slab per launch: per-group folds + each cluster's server step (fjagg.h) */
+int fjagg_server_update_group_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M,
+                                    int64_t G, const int32_t* order_dev, const int32_t* seg_dev,
+                                    const float* wperm_dev, const float* gscale_dev, const int32_t* gorder_dev,
+                                    const int32_t* order_host, const int32_t* seg_host,
+                                    const fjagg_server_opt* opts_dev, const int64_t* state_dev,
+                                    const fjagg_server_opt* opts_host, const int64_t* state_host, int flags,
+                                    void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (M > 0 && !order_host) return fail(FJAGG_EINVAL, "null host table");
+  int64_t nonempty = 0, largest = 0;
+  if (int rc = group_tables_check(K, M, G, order_host, seg_host, &nonempty, &largest)) return rc;
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "grouped fold: rows <= 1 GiB");
+  if (!state_host) return fail(FJAGG_EINVAL, "null host table");
+  if (int rc = group_opt_check(G, seg_host, opts_host, flags, 1,
+                               [=](int64_t g, int64_t) { return state_host[4 * g]; },
+                               [=](int64_t g, int which, int64_t) { return state_host[4 * g + 1 + which]; }))
+    return rc;
+  if (M == 0) return FJAGG_OK;  // every group is empty: nothing is read or written
+  if (!x_dev || !order_dev || !seg_dev || !wperm_dev || !gscale_dev || !opts_dev || !state_dev)
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  // (the epilogue stores single elements: the params and moments need no alignment)
+  const int variant = group_dense_shape(x, ld, P, M, nonempty, G, nullptr, 0);
+  const bool vec = variant != 0;
+  const int V = vec ? 4 : 1;
+  GroupArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.order = order_dev;
+  a.seg = seg_dev;
+  a.gorder = gorder_dev;
+  a.wperm = wperm_dev;
+  a.gscale = gscale_dev;
+  a.G = (int)G;
+  a.do_scale = 1;
+  a.out = nullptr;
+  a.out_stride = 0;
+  a.nonempty = nonempty;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group_opt<true>(vec, variant, a, opts_dev, state_dev, s)
+                                     : launch_dense_group_opt<false>(vec, variant, a, opts_dev, state_dev, s);
+}
+
+/* the same on the pytree path (fjagg.h) */
+int fjagg_server_update_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M, int64_t G,
+                                   int64_t nblk, const int32_t* seg_dev, const float* wperm_dev,
+                                   const float* gscale_dev, const int32_t* gorder_dev, const int32_t* seg_host,
+                                   const fjagg_server_opt* opts_dev, const int64_t* state_dev,
+                                   const fjagg_server_opt* opts_host, const int64_t* state_host,
+                                   const int64_t* params_host, const int64_t* leaf_n_host, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  int64_t nonempty = 0, largest = 0;
+  if (int rc = group_tables_check(K, M, G, nullptr, seg_host, &nonempty, &largest)) return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1) return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!state_host || !params_host || !leaf_n_host) return fail(FJAGG_EINVAL, "null host table");
+  const int64_t L64 = L;
+  // a leaf without elements has no workgroups (a frozen leaf): its addresses are never read
+  if (int rc = group_opt_check(
+          G, seg_host, opts_host, flags, L64,
+          [=](int64_t g, int64_t l) { return leaf_n_host[l] > 0 ? params_host[g * L64 + l] : (int64_t)1; },
+          [=](int64_t g, int which, int64_t l) {
+            return leaf_n_host[l] > 0 ? state_host[(g * 3 + which) * L64 + l] : (int64_t)1;
+          }))
+    return rc;
+  if (M == 0) return FJAGG_OK;
+  if (!image_dev || !seg_dev || !wperm_dev || !gscale_dev || !opts_dev || !state_dev)
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  const int g = (int)G;
+  if (vec)
+    return nt ? launch_ptrs_group_opt<4, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
+                                               nonempty, opts_dev, state_dev, s)
+              : launch_ptrs_group_opt<4, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
+                                                nonempty, opts_dev, state_dev, s);
+  return nt ? launch_ptrs_group_opt<1, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
+                                             nonempty, opts_dev, state_dev, s)
+            : launch_ptrs_group_opt<1, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
+                                              nonempty, opts_dev, state_dev, s);
 }
 
 int fjagg_fill_synth(int dtype, void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t k0,

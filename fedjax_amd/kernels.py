@@ -9,6 +9,7 @@ deltas, an unsupported dtype or a missing library raise.
 
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional, Sequence
 
@@ -410,6 +411,89 @@ class GroupTables:
         """Device addresses of (order, seg, gorder, wperm, gscale)."""
         p, M, G = self.dev.data_ptr(), self.M, self.G
         return p, p + 4 * M, p + 4 * (M + G + 1), p + 4 * (M + 2 * G + 1), p + 4 * (2 * M + 2 * G + 1)
+
+
+def pack_server_opts(descs: Sequence) -> np.ndarray:
+    """``opts[G]`` of struct fjagg_server_opt as int32 words; ``None`` (a group that is not
+    folded: its descriptor is never read) packs as zeros."""
+    words = ctypes.sizeof(_lib.ServerOpt) // 4
+    out = np.zeros((len(descs), words), dtype=np.int32)
+    for g, d in enumerate(descs):
+        if d is not None:
+            out[g] = np.frombuffer(bytes(d), dtype=np.int32)
+    return out.reshape(-1)
+
+
+class GroupUpdateTables:
+    """What a grouped fold with the per-cluster server step reads beside the deltas
+    (include/fjagg.h, fjagg_server_update_group_*), as ONE buffer and one pinned upload::
+
+        GroupTables' words | opts[G] (struct fjagg_server_opt) | pad to 8 bytes | addrs (int64)
+
+    ``descs``: one descriptor per group (``None`` where the group is not folded); ``addrs``: R
+    int64 address tables as an [R, n] array (dense: one [G, 4] table per run of trainable
+    columns; pytree: the one [G, 3, L] table). ``tables.dev`` is set to the uploaded buffer,
+    whose head is the GroupTables layout, so :meth:`GroupTables.ptrs` and every call that takes
+    ``tables`` work on it. The host copies stay here for the entries' checks."""
+
+    def __init__(self, tables: GroupTables, descs: Sequence, addrs: np.ndarray):
+        self.tables = tables
+        self.opts = pack_server_opts(descs)
+        self.addrs = np.ascontiguousarray(addrs, dtype=np.int64)
+        if self.addrs.ndim != 2 or len(descs) != tables.G:
+            raise ValueError("need one descriptor per group and an [R, n] array of address tables")
+        head = tables.host.size + self.opts.size
+        self._addr_word = head + (head & 1)
+        self.host = np.concatenate([tables.host, self.opts, np.zeros(head & 1, np.int32),
+                                    self.addrs.reshape(-1).view(np.int32)])
+
+    def upload(self, device) -> "GroupUpdateTables":
+        if self.tables.dev is None:
+            self.tables.dev = _lib.upload(torch.from_numpy(self.host), device)
+        return self
+
+    def opts_ptr(self) -> int:
+        return self.tables.dev.data_ptr() + 4 * self.tables.host.size
+
+    def addrs_ptr(self, run: int = 0) -> int:
+        """Device address of address table ``run``."""
+        return self.tables.dev.data_ptr() + 4 * self._addr_word + 8 * self.addrs.shape[1] * run
+
+
+def grouped_update_dense(x: torch.Tensor, up: GroupUpdateTables, run: int = 0, *, nontemporal: bool = False) -> None:
+    """One launch of fjagg_server_update_group_dense over the float32 slab columns ``x[K, P]``:
+    every folded group's mean and, in the epilogue, its server step through address table
+    ``run`` of ``up`` (uploaded). Nothing is returned: the params and moments behind the
+    addresses are updated in place."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the grouped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    t = up.tables
+    dev = _require_device(x)
+    if t.dev is None or not t.scaled or (t.M and int(t.order.max()) >= K):
+        raise ValueError("tables were built for another grouped fold")
+    if t.M == 0:
+        return
+    order_p, seg_p, gorder_p, wperm_p, gscale_p = t.ptrs()
+    st = up.addrs[run]
+    _lib.call("fjagg_server_update_group_dense", _lib.F32, x.data_ptr(), x.stride(0) if K > 1 else P, K, P, t.M, t.G,
+              order_p, seg_p, wperm_p, gscale_p, gorder_p, t.order.ctypes.data, t.seg.ctypes.data, up.opts_ptr(),
+              up.addrs_ptr(run), up.opts.ctypes.data, st.ctypes.data,
+              _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), _stream_handle(dev))
+
+
+def grouped_update_dense_shape(x: torch.Tensor, tables: GroupTables) -> int:
+    """The kernel shape :func:`grouped_update_dense` runs with for ``x`` [K, P] and these tables
+    (fjagg_group_dense_shape without an output: the params and moments need no alignment)."""
+    K, P = x.shape
+    nonempty = int((np.diff(tables.seg) > 0).sum())
+    rc = _lib.load().fjagg_group_dense_shape(x.data_ptr(), x.stride(0) if K > 1 else P, P, tables.M, nonempty,
+                                             tables.G, None, (P + 3) // 4 * 4)
+    if rc < 0:
+        _lib.check(rc, "fjagg_group_dense_shape")
+    return rc
 
 
 def grouped_sum_dense(x: torch.Tensor, w, group_ids, num_groups: int, *, scales=None,

@@ -357,6 +357,227 @@ def fused_tree_mean_update(pytrees_and_weights, opt: ServerOptimizer, params, st
     return new
 
 
+# ------------------------------------------------------- HypCluster: per-cluster server steps
+def _group_alive(host_weights: Sequence, ids: np.ndarray, G: int):
+    """``(ids with the members of groups without a mean set to -1, alive [G], scales [G])``:
+    W_g summed from the int 0 in client order as hyp_cluster.py:282,292 does (exactly as
+    ``grouped_mean`` sums it); a group has a mean, and takes a step, only when ``W_g > 0``
+    (:298-302, :121-123)."""
+    totals = [0] * G
+    for k in np.flatnonzero(ids >= 0):
+        totals[ids[k]] += host_weights[k]
+    alive = np.array([bool(W > 0) for W in totals], dtype=bool)
+    masked = np.where((ids >= 0) & alive[np.maximum(ids, 0)], ids, -1)
+    scales = np.array([np.float32(tree_util._inverse(W)) if a else 0 for W, a in zip(totals, alive)], np.float32)
+    return masked, alive, scales
+
+
+def _advance(states: Sequence[dict], alive) -> Tuple[List[dict], List[bool]]:
+    """The reference's ``opt_states`` after the round: a copy with the count incremented for a
+    cluster that took a step, the state itself for one that did not."""
+    return ([dict(s, count=s["count"] + 1) if a else s for s, a in zip(states, alive)], [bool(a) for a in alive])
+
+
+def fused_grouped_mean_update(slab: ClientDeltaSlab, weights: Sequence, group_ids: Sequence[int], num_groups: int,
+                              opt: ServerOptimizer, params, states: Sequence[dict], *,
+                              mean_out: Optional[torch.Tensor] = None,
+                              nontemporal: Optional[bool] = None) -> Tuple[List[dict], List[bool]]:
+    """One HypCluster round on a slab in ONE launch: the per-cluster means of the expectation
+    step (fedjax/algorithms/hyp_cluster.py:268-303, :meth:`ClientDeltaSlab.grouped_mean` bit
+    for bit) and, in the same kernel, ``server_optimizer.apply(delta_params, opt_state,
+    params)`` on every cluster that has a mean (hyp_cluster.py:107-128). The G means stay in
+    registers (``fjagg_server_update_group_dense``).
+
+    ``group_ids[k]`` is client k's cluster in ``[0, num_groups)`` or -1 for none. ``params`` is
+    a sequence of G flat float32 ``[slab.num_params]`` device tensors or one contiguous
+    ``[G, num_params]`` tensor, updated in place; ``states`` a list of G dicts as
+    ``opt.init(params[g])`` gives them (the reference's ``opt_states``), each with its OWN step
+    count: cluster g's step uses ``opt.descriptor(states[g]["count"] + 1)``. A cluster whose
+    total weight is not > 0 (no members, a zero, negative or NaN total) takes no step: its
+    params, moments and row of ``mean_out`` are neither read nor written and its count does not
+    advance (hyp_cluster.py:121-123). Returns ``(new_states, updated)``: ``new_states[g]`` has
+    the count incremented where ``updated[g]``, else it is ``states[g]`` itself. ``mean_out``
+    (optional float32 ``[G, num_params]``) receives the means of the updated clusters.
+
+    The weights and descriptors change every round, so the tables go up with every call: a
+    graph capture of this call is refused at capture time (:func:`_lib.upload`)."""
+    if slab.dtype != torch.float32:
+        raise TypeError(f"the grouped server step takes a float32 slab, not {slab.dtype}")
+    K, G, P, dev = slab.num_clients, int(num_groups), slab.num_params, slab.storage.device
+    ids = kernels.check_group_ids(group_ids, K, G)
+
+    def flat(t, what):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                and t.device == dev and tuple(t.shape) == (P,)):
+            raise ValueError(f"{what} must be a contiguous float32 [{P}] tensor on {dev}")
+        return t
+
+    if isinstance(params, torch.Tensor):
+        if params.dim() != 2 or params.shape[0] != G or not params.is_contiguous():
+            raise ValueError(f"params must be a contiguous float32 [{G}, {P}] tensor or {G} flat tensors")
+        prow = [flat(params[g], "params") for g in range(G)]
+    else:
+        prow = [flat(p, "params") for p in params]
+    states = list(states)
+    if len(prow) != G or len(states) != G:
+        raise ValueError(f"need {G} params and {G} states, got {len(prow)} and {len(states)}")
+    if mean_out is not None and not (isinstance(mean_out, torch.Tensor) and mean_out.dtype == torch.float32
+                                     and tuple(mean_out.shape) == (G, P) and (P == 0 or mean_out.stride(1) == 1)
+                                     and mean_out.device == dev):
+        raise ValueError(f"mean_out must be a float32 [{G}, {P}] tensor on {dev} with unit column stride")
+    w = slab.host_weights(weights)
+    masked, alive, scales = _group_alive([tree_util._host_weight(x) for x in weights], ids, G)
+    if isinstance(opt, Adafactor):  # needs whole-leaf reductions: the grouped mean first, then the steps
+        means = slab.grouped_mean(weights, group_ids, G)
+        new = list(states)
+        for g in np.flatnonzero(alive):
+            if mean_out is not None:
+                for dst, src in zip(pytree.leaves_of(slab.unflatten(mean_out[g])), pytree.leaves_of(means[g])):
+                    dst.copy_(src)
+            new[g] = opt.apply(means[g], states[g], slab.unflatten(prow[g]))[0]
+        return new, [bool(a) for a in alive]
+    descs: List[Optional[_lib.ServerOpt]] = [None] * G
+    moments = np.zeros((G, 2), dtype=np.int64)
+    for g in np.flatnonzero(alive):
+        _require_state(opt, states[g])
+        for i, key in enumerate(("m", "v")):
+            if states[g].get(key) is not None:
+                moments[g, i] = flat(states[g][key], f"state {key!r} of cluster {g}").data_ptr()
+        descs[g] = opt.descriptor(states[g]["count"] + 1)  # optax safe_int32_increment, per cluster
+    # ignore_grads_haiku: one launch per maximal run of trainable columns, as fused_mean_update
+    frozen = _frozen_leaves(opt, slab.unflatten(prow[0]), slab.treedef) if G else np.zeros(0, dtype=bool)
+    runs, l0 = [], 0
+    for l in range(len(frozen) + 1):
+        if l == len(frozen) or frozen[l]:
+            if l > l0 and slab.offsets[l] > slab.offsets[l0]:
+                runs.append((int(slab.offsets[l0]), int(slab.offsets[l])))
+            l0 = l + 1
+    tables = kernels.GroupTables(w, masked, G, scales)
+    if tables.M == 0 or P == 0:
+        return _advance(states, alive)
+    addrs = np.zeros((len(runs), G, 4), dtype=np.int64)
+    for r, (c0, _) in enumerate(runs):
+        for g in np.flatnonzero(alive):
+            addrs[r, g, 0] = prow[g].data_ptr() + 4 * c0
+            addrs[r, g, 1:3] = np.where(moments[g] != 0, moments[g] + 4 * c0, 0)
+            if mean_out is not None:
+                addrs[r, g, 3] = mean_out[g].data_ptr() + 4 * c0
+    up = kernels.GroupUpdateTables(tables, descs, addrs.reshape(len(runs), 4 * G)).upload(dev)
+    rows = slab.rows
+    nt = tables.M * P * 4 >= tree_util.NONTEMPORAL_MIN_BYTES if nontemporal is None else bool(nontemporal)
+    for r, (c0, c1) in enumerate(runs):
+        kernels.grouped_update_dense(rows[:, c0:c1], up, r, nontemporal=nt)
+    if mean_out is not None:  # the means of frozen leaves too (no update consumes them)
+        for l in np.flatnonzero(frozen):
+            c0, c1 = int(slab.offsets[l]), int(slab.offsets[l + 1])
+            if c1 > c0:
+                kernels.grouped_sum_dense(rows[:, c0:c1], w, masked, G, out=mean_out[:, c0:c1], tables=tables,
+                                          nontemporal=nt)
+    return _advance(states, alive)
+
+
+def fused_tree_grouped_mean_update(pytrees_and_weights, group_ids: Sequence[int], opt: ServerOptimizer,
+                                   cluster_params: Sequence, states: Sequence[dict], *, mean_out=None,
+                                   nontemporal: Optional[bool] = None) -> Tuple[List[dict], List[bool]]:
+    """:func:`fused_grouped_mean_update` on separate pytrees: ``tree_grouped_mean`` of the
+    clients' delta pytrees and every cluster's server step in ONE kernel
+    (``fjagg_server_update_group_ptrs``; hyp_cluster.py:107-128). ``cluster_params`` is a
+    sequence of G pytrees of float32 device leaves with the deltas' structure and shapes,
+    updated in place (``num_groups = len(cluster_params)``); ``states[g]`` is
+    ``opt.init(cluster_params[g])``; ``mean_out`` an optional sequence of G such pytrees.
+    Returns ``(new_states, updated)`` as the slab form does. The plan image carries the member
+    tables, the descriptors and the state addresses: one upload, not capturable."""
+    pairs = pytrees_and_weights if type(pytrees_and_weights) is list else list(pytrees_and_weights)
+    cluster_params, states = list(cluster_params), list(states)
+    G = len(cluster_params)
+    if len(states) != G or (mean_out is not None and len(mean_out) != G):
+        raise ValueError(f"need one state (and one mean_out tree) per cluster ({G})")
+    trees = [tree for tree, _ in pairs]
+    hw = [tree_util._host_weight(weight) for _, weight in pairs]
+    K = len(trees)
+    ids = kernels.check_group_ids(group_ids, K, G)
+    masked, alive, scales = _group_alive(hw, ids, G)
+    if not trees:
+        return _advance(states, alive)
+    if isinstance(opt, Adafactor):  # needs whole-leaf reductions: the grouped mean first, then the steps
+        means = tree_util.tree_grouped_mean(pairs, group_ids, G)
+        new = list(states)
+        for g in np.flatnonzero(alive):
+            if mean_out is not None:
+                for dst, src in zip(pytree.leaves_of(mean_out[g]), pytree.leaves_of(means[g])):
+                    dst.copy_(src)
+            new[g] = opt.apply(means[g], states[g], cluster_params[g])[0]
+        return new, [bool(a) for a in alive]
+    td, rows = tree_util._client_table(trees)
+    row0 = rows[0]
+    L = len(row0)
+    if L == 0:
+        return _advance(states, alive)
+    if any(x.dtype != torch.float32 for x in row0):
+        raise TypeError("the grouped server step takes float32 deltas (got "
+                        f"{sorted({str(x.dtype) for x in row0})})")
+    device = row0[0].device
+
+    def leaves(tree, what):
+        ls = pytree.flatten_as(td, tree)
+        for x, d in zip(ls, row0):
+            if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_contiguous()
+                    and x.device == device and x.shape == d.shape):
+                raise ValueError(f"{what} leaves must be contiguous float32 device tensors shaped like the deltas")
+        return ls
+
+    out_ptrs = np.zeros((G, L), dtype=np.int64)
+    st = np.zeros((G, 3, L), dtype=np.int64)
+    descs: List[Optional[_lib.ServerOpt]] = [None] * G
+    mo = [None] * G
+    for g in range(G):
+        p = leaves(cluster_params[g], f"params of cluster {g}")
+        if mean_out is not None:
+            mo[g] = leaves(mean_out[g], f"mean_out of cluster {g}")
+        if not alive[g]:
+            continue  # no step: nothing of this cluster is read or written (its addresses stay 0)
+        _require_state(opt, states[g])
+        out_ptrs[g] = [x.data_ptr() for x in p]
+        for i, key in enumerate(("m", "v")):
+            if states[g].get(key) is not None:
+                st[g, i] = [x.data_ptr() for x in leaves(states[g][key], f"state {key!r} of cluster {g}")]
+        if mo[g] is not None:
+            st[g, 2] = [x.data_ptr() for x in mo[g]]
+        descs[g] = opt.descriptor(states[g]["count"] + 1)  # optax safe_int32_increment, per cluster
+    # ignore_grads_haiku: a frozen leaf gets no workgroups (leaf_n 0 in the plan), in any cluster
+    frozen = _frozen_leaves(opt, cluster_params[0], td)
+    leaf_n = np.array([0 if f else x.numel() for x, f in zip(row0, frozen)], dtype=np.int64)
+    tables = kernels.GroupTables(np.array([np.float32(w) for w in hw], np.float32), masked, G, scales)
+    M = tables.M
+    if M == 0:
+        return _advance(states, alive)
+    in_ptrs = tree_util._ptr_table(rows)[tables.order]  # [M, L] in member order
+    blocks, _ = tree_util._leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, st.reshape(3 * G, L), device)
+    opts = kernels.pack_server_opts(descs)
+    t32 = np.concatenate([tables.host[M:], opts])  # seg | gorder | wperm | gscale | opts[G]
+    words = np.zeros((t32.size + 1) // 2, dtype=np.int64)
+    words.view(np.int32)[: t32.size] = t32
+    image = np.concatenate([in_ptrs.ravel(), out_ptrs.ravel(), leaf_n, blocks, words, st.ravel()])
+    if blocks.size:
+        image_dev = _lib.upload(torch.from_numpy(image), device)
+        seg_p = image_dev.data_ptr() + 8 * (in_ptrs.size + out_ptrs.size + L + blocks.size)
+        gorder_p, wperm_p, gscale_p = seg_p + 4 * (G + 1), seg_p + 4 * (2 * G + 1), seg_p + 4 * (2 * G + 1 + M)
+        opts_p, st_p = seg_p + 4 * (3 * G + 1 + M), seg_p + 8 * words.size
+        nt = int(leaf_n.sum()) * M * 4 >= tree_util.NONTEMPORAL_MIN_BYTES if nontemporal is None else bool(nontemporal)
+        _lib.call("fjagg_server_update_group_ptrs", _lib.F32, image_dev.data_ptr(), L, K, M, G, blocks.size // 2,
+                  seg_p, wperm_p, gscale_p, gorder_p, tables.seg.ctypes.data, opts_p, st_p, opts.ctypes.data,
+                  st.ctypes.data, out_ptrs.ctypes.data, leaf_n.ctypes.data,
+                  _lib.SCALE | (_lib.NONTEMPORAL if nt else 0), torch.cuda.current_stream(device).cuda_stream)
+    if mean_out is not None and frozen.any():  # the means of frozen leaves too (no update consumes them)
+        idx = np.flatnonzero(frozen)
+        sub = [([pytree.flatten_as(td, t)[i] for i in idx], w) for t, w in pairs]
+        for g, mean in enumerate(tree_util.tree_grouped_mean(sub, group_ids, G)):
+            if mean is not None:
+                for i, src in zip(idx, mean):
+                    mo[g][i].copy_(src)
+    return _advance(states, alive)
+
+
 # --------------------------------------------------------------------------- adafactor
 def _factored_dims(shape, factored: bool, min_dim_size_to_factor: int):
     """optax factorized._factored_dims: (d1, d0) = the second-largest and the largest axis
@@ -559,5 +780,5 @@ def adafactor(learning_rate, min_dim_size_to_factor: int = 128, decay_rate: floa
                      weight_decay_mask)
 
 
-__all__ = ["Adafactor", "ServerOptimizer", "adafactor", "adagrad", "adam", "fused_mean_update",
-           "fused_tree_mean_update", "ignore_grads_haiku", "rmsprop", "sgd", "yogi"]
+__all__ = ["Adafactor", "ServerOptimizer", "adafactor", "adagrad", "adam", "fused_grouped_mean_update",
+           "fused_mean_update", "fused_tree_grouped_mean_update", "fused_tree_mean_update", "ignore_grads_haiku", "rmsprop", "sgd", "yogi"]

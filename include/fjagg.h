@@ -16,6 +16,7 @@
  *     tree_l2_squared tree_util.py:105-108          fjagg_l2sq_*
  *     tree_clip_by_global_norm tree_util.py:117-133 fjagg_clip_scales + fjagg_wsum_clip_*
  *     expectation_step algorithms/hyp_cluster.py:268-303  fjagg_wsum_group_* (per-cluster means)
+ *     per-cluster apply algorithms/hyp_cluster.py:107-128 fjagg_server_update_group_* (means + steps)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -416,6 +417,50 @@ int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t
                           int64_t nblk, const int32_t* seg_dev, const float* wperm_dev,
                           const float* gscale_dev, const int32_t* gorder_dev, const int32_t* seg_host,
                           int flags, void* stream);
+
+/*
+ * Grouped fold with each cluster's server step in its epilogue: one HypCluster round per launch.
+ * Replaces, after the expectation step, the per-cluster loop of
+ * fedjax/algorithms/hyp_cluster.py:107-128 — server_optimizer.apply(delta_params, opt_state,
+ * params) on every cluster whose mean is not None — so the G means never go to HBM. Float32
+ * deltas, fold and state. For every group g with members (seg[g+1] > seg[g]):
+ *     y[p] = the grouped mean above, bit for bit (from +0, members in order, * gscale[g])
+ *     (params_g, m_g, v_g)[p] <- the update rules of fjagg_server_update_dense with opts[g]
+ * opts[G] holds one descriptor PER GROUP: the clusters' step counts differ once a cluster has sat
+ * out a round, so bc1 / bc2 and a scheduled neg_lr do. Of a group without members nothing is
+ * read or written — not its params, moments, mean or descriptor; which groups have a mean
+ * (W_g > 0) and whose counts advance is the caller's decision, as for fjagg_wsum_group_*.
+ * Both entries take the group tables of fjagg_wsum_group_* (device and HOST copies) and also the
+ * device and HOST copies of opts and of the address tables, and check the host copies before any
+ * HIP call. FJAGG_EINVAL: what fjagg_wsum_group_* returns it for; flags without FJAGG_SCALE (the
+ * step takes the mean); for a group that will be folded, a descriptor that is not valid (kind
+ * outside 1..6, unknown flags), a params address of 0, or an m / v address of 0 that the rule
+ * reads. FJAGG_EUNSUPPORTED: what fjagg_wsum_group_* returns it for (FJAGG_ACCUMULATE included).
+ * Flags: FJAGG_SCALE (mandatory), FJAGG_NONTEMPORAL and, on the pytree path, FJAGG_UNALIGNED.
+ */
+/* Dense (hyp_cluster.py:107-128 on a slab): fjagg_wsum_group_dense's arguments without the output;
+ * state[4*G] int64 = group g's params | m | v | mean address at state[4g ..] (float32[P] each; 0
+ * where absent; mean optional: it also receives y). The kernel shape is
+ * fjagg_group_dense_shape(x_dev, ld, P, M, nonempty, G, NULL, round_up(P, 4)): the state needs no
+ * alignment. */
+int fjagg_server_update_group_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M,
+                                    int64_t G, const int32_t* order_dev, const int32_t* seg_dev,
+                                    const float* wperm_dev, const float* gscale_dev, const int32_t* gorder_dev,
+                                    const int32_t* order_host, const int32_t* seg_host,
+                                    const fjagg_server_opt* opts_dev, const int64_t* state_dev,
+                                    const fjagg_server_opt* opts_host, const int64_t* state_host, int flags,
+                                    void* stream);
+/* Pytree path (hyp_cluster.py:107-128 over separate leaves): fjagg_wsum_group_ptrs's arguments
+ * with out_ptrs[G*L] of the image = the clusters' params leaves, and state[G*3*L] int64 = per group
+ * m leaves | v leaves | mean leaves, as fjagg_server_update_ptrs lays out state[3*L]. params_host
+ * [G*L] and leaf_n_host[L] are the host copies of the image's out_ptrs and leaf_n; a leaf with
+ * leaf_n 0 has no blocks (a frozen leaf), and its addresses are not checked or read. */
+int fjagg_server_update_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M, int64_t G,
+                                   int64_t nblk, const int32_t* seg_dev, const float* wperm_dev,
+                                   const float* gscale_dev, const int32_t* gorder_dev, const int32_t* seg_host,
+                                   const fjagg_server_opt* opts_dev, const int64_t* state_dev,
+                                   const fjagg_server_opt* opts_host, const int64_t* state_host,
+                                   const int64_t* params_host, const int64_t* leaf_n_host, int flags, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
