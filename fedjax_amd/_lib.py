@@ -79,6 +79,10 @@ _SIGNATURES = {
     "fjagg_wsum_clip_ptrs_workspace_bytes": (_i64, [_i64, _i64]),
     "fjagg_wsum_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _i32, _vp, _i64, _vp]),
     "fjagg_clip_finish": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "fjagg_server_update_clip_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _i32, _vp, _i64, _vp]),
+    "fjagg_server_update_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp,
+                                             _i64, _vp]),
     "fjagg_wsum_group_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _i64, _i32, _vp]),
     "fjagg_group_dense_shape": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64]),

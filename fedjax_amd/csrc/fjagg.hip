@@ -1307,6 +1307,128 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_opt(const int64_t* __restrict
                                                  NoNorm(), epi);
 }
 
+// The clipped fold with the server optimizer step in its epilogue (fjagg_server_update_clip_dense;
+// mime_lite.py:131-149, then :162-167): k_dense_clip's unit layout, grid, tail block, LdsNorm rows
+// and partial rows (restated here rather than shared, so that k_dense_clip and k_dense_opt compile
+// to the code they always did), folding with DevClip and OptEpi together. The clipped mean
+// y = fl(s * scale) stays in registers; only params, moments and (optionally) epi.mean are written.
+// L2: in the tail block every lane joins the per-client wave reductions (k_dense_opt's early
+// return for lanes past tail_n would leave them out); the epilogue skips invalid units.
+template <int V, int E, int U, bool NT, bool L2>
+__global__ __launch_bounds__(kThreads) void k_dense_clip_opt(
+    const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
+    const float* __restrict__ w, const float* __restrict__ c, float scale, int64_t S, OptEpi epi,
+    float* __restrict__ ws, const L2Out l2out) {
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  const int tid = threadIdx.x;
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  const DevClip clip{c};
+  auto row = [=](int64_t k) { return x + k * ld_bytes; };
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  bool is_tail = false;
+  if (tail_n > 0) {
+    if (b == 0) {
+      is_tail = true;
+      const bool active = tid < tail_n;
+      if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+        const int64_t e = nunits * V + (active ? tid : 0);
+        const uint32_t off[1] = {(uint32_t)(e * IB)};
+        const bool valid[1] = {active};
+        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false, nrm, epi,
+                                         clip);
+      }
+    }
+    b -= 1;
+  }
+  if (!is_tail) {
+    const int64_t u_begin = b * S;
+    const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+      uint32_t off[E];
+      bool valid[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        int64_t u = g + j * kThreads + tid;
+        valid[j] = u < u_end;
+        if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the epilogue is skipped
+        off[j] = (uint32_t)(u * (V * IB));
+      }
+      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false, nrm, epi,
+                                       clip);
+    }
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+}
+
+// The same on the pytree path (fjagg_server_update_clip_ptrs): k_ptrs_clip's plan image, block
+// words, XCD remap and unit walk with out_ptrs[L] = the params leaves and state[3L] = m | v | mean
+// leaf pointers as k_ptrs_opt lays them out (0 where absent). Each workgroup owns one leaf's unit
+// range, so its OptEpi points at that leaf and indexes it by the element within the range. No
+// workgroup returns before the norm epilogue's barriers.
+template <int V, bool NT, bool L2, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_ptrs_clip_opt(const int64_t* __restrict__ img, int L, int64_t K,
+                                                            const float* __restrict__ w,
+                                                            const float* __restrict__ c, float scale, int xcd,
+                                                            fjagg_server_opt opt,
+                                                            const int64_t* __restrict__ state,
+                                                            float* __restrict__ ws, const L2Out l2out) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  using ACC = AccF;
+  const int tid = threadIdx.x;
+  const DevClip clip{c};
+  const int64_t* in_ptrs = img;
+  const int64_t* out_ptrs = img + K * L;
+  const int64_t* leaf_n = out_ptrs + L;
+  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1);
+  const int64_t u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t nunits = n / V;
+  // rebased at the workgroup's first element, as in k_ptrs (the epilogue's element index too)
+  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);
+  const OptEpi epi{opt, f32_at(out_ptrs[leaf], e_base), f32_at(state[leaf], e_base),
+                   f32_at(state[L + leaf], e_base), f32_at(state[2 * L + leaf], e_base)};
+  auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((n - e_base) * IB);
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  if (tail) {
+    const bool active = tid < n - nunits * V;
+    if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+      const int64_t e = active ? tid : 0;
+      const uint32_t off[1] = {(uint32_t)(e * IB)};
+      const bool valid[1] = {active};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false, nrm, epi, clip);
+    }
+  } else if (V > 1 && elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, K, 0, u1 - u0, nullptr, w, true, scale, false, nrm, epi,
+                                           clip);
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, u1 - u0, nullptr, w, true, scale, false, nrm, epi,
+                                           clip);
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
+}
+
 // Narrow parameter axis, many clients (exact mode). The exact fold walks the clients in
 // order per element, so the only parallelism is the parameter axis: at 16 Ki-128 Ki f32
 // params the 16-byte-unit kernels above have 4 K-32 K lanes for the whole chip and keep
@@ -2946,6 +3068,172 @@ int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t 
   const L2Out l2{nullptr, nullptr, 0, nullptr};
   return vec ? launch_ptrs_clip<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s)
              : launch_ptrs_clip<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s);
+}
+
+// ------------------------- clipped weighted mean + server step in the fold's epilogue (fjagg.h)
+namespace {
+extern "C++" {
+template <int V, int E, int U, bool NT, bool L2>
+int launch_dense_clip_opt_t(const DenseArgs& a, const float* c, const OptEpi& epi, float* ws, int64_t ws_floats,
+                            L2Out l2, hipStream_t s) {
+  auto kern = k_dense_clip_opt<V, E, U, NT, L2>;
+  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
+  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  // With L2 the partition of the parameter axis fixes the order the clipped squares are added
+  // in, so the grid is sized by k_dense_clip's residency, not this kernel's: the same partial
+  // rows, the same clipped norms bit for bit as fjagg_wsum_clip_dense on the same slab.
+  const void* sized_by = L2 ? reinterpret_cast<const void*>(k_dense_clip<V, E, U, NT, true>)
+                            : reinterpret_cast<const void*>(kern);
+  int64_t S = (int64_t)kThreads * E, nblk = 0;
+  balanced_grid(residency(sized_by, smem), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
+  if (a.nunits == 0) nblk = 0;
+  const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
+  if (L2 && grid * a.K > ws_floats)
+    return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
+                (long long)a.K);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
+                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, S, epi, ws, l2);
+  if (int rc = check_launch("k_dense_clip_opt")) return rc;
+  return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
+}
+
+// the shapes of launch_dense_clip: E=8 x U=4 where pick_variant says so, else E=1 x U=8
+template <bool L2>
+int launch_dense_clip_opt(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, const OptEpi& epi,
+                          float* ws, int64_t ws_floats, L2Out l2, hipStream_t s) {
+  if (!vec)
+    return nt ? launch_dense_clip_opt_t<1, 1, 8, true, L2>(a, c, epi, ws, ws_floats, l2, s)
+              : launch_dense_clip_opt_t<1, 1, 8, false, L2>(a, c, epi, ws, ws_floats, l2, s);
+  if (variant == 12)
+    return nt ? launch_dense_clip_opt_t<4, 8, 4, true, L2>(a, c, epi, ws, ws_floats, l2, s)
+              : launch_dense_clip_opt_t<4, 8, 4, false, L2>(a, c, epi, ws, ws_floats, l2, s);
+  return nt ? launch_dense_clip_opt_t<4, 1, 8, true, L2>(a, c, epi, ws, ws_floats, l2, s)
+            : launch_dense_clip_opt_t<4, 1, 8, false, L2>(a, c, epi, ws, ws_floats, l2, s);
+}
+
+// launch_ptrs_clip's rule: with norms always the burst schedule, else launch_ptrs_t's
+template <int V, bool L2>
+int launch_ptrs_clip_opt(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w, const float* c,
+                         float scale, const fjagg_server_opt& opt, const int64_t* state, float* ws, L2Out l2,
+                         hipStream_t s) {
+  const dim3 grid((unsigned)nblk), block(kThreads);
+  const int xcd = xcd_remap_bit() ? 1 : 0;
+  if constexpr (L2) {
+    const size_t smem = l2_smem(K, l2);
+    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip_opt<V, true, true, true>)
+                        : reinterpret_cast<const void*>(k_ptrs_clip_opt<V, false, true, true>);
+    if (int rc = allow_lds(kf, smem)) return rc;
+    if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
+                         opt, state, ws, l2);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
+                         opt, state, ws, l2);
+    if (int rc = check_launch("k_ptrs_clip_opt (l2)")) return rc;
+    return launch_l2_combine(ws, nblk, K, l2, s);
+  } else {
+    const bool burst = nblk < 2 * (int64_t)cu_count();
+    if (nt && burst)
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd, opt,
+                         state, nullptr, l2);
+    else if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         opt, state, nullptr, l2);
+    else if (burst)
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         opt, state, nullptr, l2);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         opt, state, nullptr, l2);
+    return check_launch("k_ptrs_clip_opt");
+  }
+}
+}  // extern "C++"
+}  // namespace
+
+int fjagg_server_update_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                                   const float* w_dev, const float* c_dev, float scale,
+                                   const fjagg_server_opt* opt, float* params_dev, float* m_dev, float* v_dev,
+                                   float* mean_dev, float* l2sq_clipped_dev, int flags, void* ws_dev,
+                                   int64_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "clipped server update: the step consumes the mean (no FJAGG_ACCUMULATE)");
+  if (int rc = clip_flags_check(in_dtype, flags, FJAGG_NONTEMPORAL)) return rc;
+  if (!opt_valid(opt)) return fail(FJAGG_EINVAL, "clipped server update: bad optimizer descriptor");
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "clipped server update: rows <= 1 GiB");
+  if (!x_dev || !w_dev || !c_dev || !params_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  if (opt_needs_m(*opt) && !m_dev) return fail(FJAGG_EINVAL, "optimizer state m is null");
+  if (opt_needs_v(*opt) && !v_dev) return fail(FJAGG_EINVAL, "optimizer state v is null");
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < fjagg_wsum_clip_workspace_bytes(K, P)))
+    return fail(FJAGG_EINVAL, "clip workspace too small (need %lld bytes)",
+                (long long)fjagg_wsum_clip_workspace_bytes(K, P));
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  const bool vec = (reinterpret_cast<uintptr_t>(x) % 16 == 0) && ((ld * 4) % 16 == 0) && P >= 4;
+  const int V = vec ? 4 : 1;
+  DenseArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.K = K;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.w = w_dev;
+  a.scale = scale;
+  a.do_scale = 1;
+  a.accumulate = 0;
+  a.out = nullptr;
+  a.kchunk = K;
+  a.out_ystride = 0;
+  a.balanced = true;
+  a.host_w = false;
+  const OptEpi epi{*opt, params_dev, m_dev, v_dev, mean_dev};
+  const int variant = pick_variant(a.nunits, K);
+  const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (l2sq_clipped_dev)
+    return launch_dense_clip_opt<true>(vec, nt, variant, a, c_dev, epi, reinterpret_cast<float*>(ws_dev),
+                                       ws_bytes / 4, L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_dense_clip_opt<false>(vec, nt, variant, a, c_dev, epi, nullptr, 0,
+                                      L2Out{nullptr, nullptr, 0, nullptr}, s);
+}
+
+int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                                  const float* w_dev, const float* c_dev, float scale,
+                                  const fjagg_server_opt* opt, const int64_t* state_dev,
+                                  float* l2sq_clipped_dev, int flags, void* ws_dev, int64_t ws_bytes,
+                                  void* stream) {
+  g_err[0] = 0;
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "clipped server update: the step consumes the mean (no FJAGG_ACCUMULATE)");
+  if (int rc = clip_flags_check(in_dtype, flags, FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (!opt_valid(opt)) return fail(FJAGG_EINVAL, "clipped server update: bad optimizer descriptor");
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (nblk < 1 || nblk > 0x7fffffff || !image_dev || !w_dev || !c_dev || !state_dev || L < 1)
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)))
+    return fail(FJAGG_EINVAL, "clip workspace too small (need %lld bytes)",
+                (long long)fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  float* ws = reinterpret_cast<float*>(ws_dev);
+  if (l2sq_clipped_dev) {
+    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
+    return vec ? launch_ptrs_clip_opt<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev, ws,
+                                               l2, s)
+               : launch_ptrs_clip_opt<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev, ws,
+                                               l2, s);
+  }
+  const L2Out l2{nullptr, nullptr, 0, nullptr};
+  return vec ? launch_ptrs_clip_opt<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev,
+                                              nullptr, l2, s)
+             : launch_ptrs_clip_opt<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev,
+                                              nullptr, l2, s);
 }
 
 // ------------------------------------------------- grouped weighted mean (fjagg.h)

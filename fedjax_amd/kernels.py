@@ -360,6 +360,55 @@ def clip_finish(norms: torch.Tensor, c: torch.Tensor, l2sq_clipped: torch.Tensor
     return clipped_norms, clipped
 
 
+def clip_flags(c: torch.Tensor) -> torch.Tensor:
+    """``clipped = (c != 1)`` (bool [K]; true for a NaN factor) alone: :func:`clip_finish` for a
+    fold that formed no clipped squares (``fjagg_clip_finish`` with a null clipped-norm output)."""
+    K = c.numel()
+    _f32_vector("c", c, K)
+    dev = _require_device(c)
+    clipped = torch.empty(K, dtype=torch.bool, device=dev)
+    _lib.call("fjagg_clip_finish", None, c.data_ptr(), None, K, None, clipped.data_ptr(), _stream_handle(dev))
+    return clipped
+
+
+def clipped_update_dense(x: torch.Tensor, w: torch.Tensor, c: torch.Tensor, scale: float, desc, params: torch.Tensor,
+                         m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                         mean_out: Optional[torch.Tensor] = None, *, nontemporal: bool = False,
+                         with_clipped_l2sq: bool = True) -> Optional[torch.Tensor]:
+    """The clipped fold of :func:`clipped_sum_dense` over a float32 slab ``x[K, P]`` with the
+    server optimizer step in its epilogue (``fjagg_server_update_clip_dense``): the clipped mean
+    ``fl(sum_k fl(fl(c_k x_k) w_k) * scale)`` stays in registers and steps ``params`` (and the
+    moments ``m`` / ``v`` the rule of descriptor ``desc`` reads) in place; ``mean_out`` also
+    receives it. All tensors are contiguous float32 on the device, ``params`` / ``m`` / ``v`` /
+    ``mean_out`` of P elements. Returns ``l2sq_clipped`` (float32 [K], the bits
+    :func:`clipped_sum_dense` gives on the same slab; K <= 4096), or None without
+    ``with_clipped_l2sq`` (no workspace, no combine launch)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the clipped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    _f32_vector("w", w, K)
+    _f32_vector("c", c, K)
+    state = [t for t in (params, m, v, mean_out) if t is not None]
+    for t in state:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != P or not t.is_contiguous():
+            raise ValueError(f"params, moments and mean_out must be contiguous float32 tensors of {P} elements")
+    dev = _require_device(x, w, c, *state)
+    l2sq, ws_ptr, ws_bytes = None, None, 0
+    if with_clipped_l2sq:
+        l2sq = torch.empty(K, dtype=torch.float32, device=dev)
+        ws_bytes = max(int(_lib.load().fjagg_wsum_clip_workspace_bytes(K, P)), 4)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws_ptr = ws.data_ptr()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_server_update_clip_dense", _lib.F32, x.data_ptr(), ld, K, P, w.data_ptr(), c.data_ptr(),
+              float(scale), ctypes.byref(desc), params.data_ptr(), ptr(m), ptr(v), ptr(mean_out), ptr(l2sq),
+              _lib.NONTEMPORAL if nontemporal else 0, ws_ptr, ws_bytes, _stream_handle(dev))
+    return l2sq
+
+
 def check_group_ids(group_ids, K: int, num_groups: int) -> np.ndarray:
     """``group_ids`` as an int64 [K] array of ids in ``{-1} | [0, num_groups)``; ValueError for
     anything else (a wrong length, non-integers, ids out of range)."""

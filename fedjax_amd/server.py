@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -355,6 +355,212 @@ def fused_tree_mean_update(pytrees_and_weights, opt: ServerOptimizer, params, st
     new = dict(state)
     new["count"] = count
     return new
+
+
+# ------------------------------------------------- Mime Lite: the clipped mean's server step
+class ClippedUpdate(NamedTuple):
+    """Result of a clipped round (:func:`fused_clipped_mean_update`,
+    :func:`fused_tree_clipped_mean_update`): the new optimizer state and the per-client
+    diagnostics of :class:`~fedjax_amd.tree_util.ClippedMean` (``clipped_norms`` is ``None``
+    with ``with_clipped_norms=False``)."""
+    state: Any
+    norms: Any
+    clipped_norms: Any
+    clipped: Any
+
+
+def _two_step(opt) -> bool:
+    """Whether a clipped round takes the two-step route (the clipped mean, then the step on it).
+    The clip norm covers the whole delta, frozen leaves included, so a fold that skips the frozen
+    leaves of ignore_grads_haiku cannot form it; adafactor needs whole-leaf reductions."""
+    return isinstance(opt, Adafactor) or bool(opt.frozen)
+
+
+def fused_clipped_mean_update(slab: ClientDeltaSlab, weights: Sequence, max_norm: float, opt: ServerOptimizer,
+                              params: torch.Tensor, state: dict, *, mean_out: Optional[torch.Tensor] = None,
+                              with_clipped_norms: bool = True,
+                              nontemporal: Optional[bool] = None) -> ClippedUpdate:
+    """One clipped server round on a slab: every client's delta clipped to l2 norm ``max_norm``,
+    the weighted mean of the clipped deltas (:meth:`ClientDeltaSlab.clipped_mean` bit for bit;
+    fedjax/algorithms/mime_lite.py:131-149) and, in the fold's epilogue, ``opt``'s update of
+    ``params`` (mime_lite.py:162-167 with ``opt = sgd(server_learning_rate)``; any clipped FedAvg
+    with an adaptive server optimizer). The mean stays in registers
+    (``fjagg_server_update_clip_dense``) unless ``mean_out`` (flat float32 [P]) asks for it.
+
+    ``params`` is the flat float32 [P] server parameter vector in the slab's leaf order, updated
+    in place; ``state`` is ``opt.init(params)`` with the moments updated in place. Returns
+    :class:`ClippedUpdate` ``(state, norms, clipped_norms, clipped)``: the new state (count
+    incremented) and the diagnostics ``clipped_mean`` returns on the same deltas, the same bits.
+    ``with_clipped_norms=False`` skips the clipped squares (no workspace, no combine launch):
+    ``clipped_norms`` is ``None``; ``norms``, ``clipped`` and the params are unchanged. A float32
+    slab of up to 4096 clients.
+
+    :func:`ignore_grads_haiku` optimizers and :func:`adafactor` take the two-step route — the
+    clipped mean, then the fused step (or ``opt.apply``) on that mean with weight 1 — because the
+    clip norm covers the frozen leaves too and adafactor needs whole-leaf reductions. That route
+    has the fused kernel's bits on the trainable leaves; frozen params and state are untouched
+    and their part of ``mean_out`` is filled.
+
+    The weights and the descriptor change every round and travel by upload, so a graph capture of
+    this call is refused at capture time (:func:`_lib.upload`)."""
+    if slab.dtype != torch.float32:
+        raise TypeError(f"the clipped server step takes a float32 slab, not {slab.dtype}")
+    K, P, dev = slab.num_clients, slab.num_params, slab.storage.device
+    if K > tree_util._L2_MAX_CLIENTS:
+        raise ValueError(f"the clipped server step supports up to {tree_util._L2_MAX_CLIENTS} clients, got {K}")
+    if len(weights) != K:
+        raise ValueError(f"need {K} weights, got {len(weights)}")
+
+    def flat(t, what):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                and t.device == dev and t.numel() == P):
+            raise ValueError(f"{what} must be a contiguous float32 tensor of {P} elements on {dev}")
+        return t
+
+    flat(params, "params")
+    if mean_out is not None:
+        flat(mean_out, "mean_out")
+    if _two_step(opt):
+        got = slab.clipped_mean(weights, max_norm, out=mean_out)
+        cn = got.clipped_norms if with_clipped_norms else None
+        if isinstance(opt, Adafactor):
+            new = opt.apply(got.mean, state, slab.unflatten(params))[0]
+        else:
+            _require_state(opt, state)
+            tree_state = {k: (slab.unflatten(flat(v, f"state {k!r}")) if k in ("m", "v") else v)
+                          for k, v in state.items()}
+            new = fused_tree_mean_update([(got.mean, 1.0)], opt, slab.unflatten(params), tree_state,
+                                         nontemporal=nontemporal)
+            new = dict(state, count=new["count"])
+        return ClippedUpdate(new, got.norms, cn, got.clipped)
+    _require_state(opt, state)
+    m = flat(state["m"], "state 'm'") if state.get("m") is not None else None
+    v = flat(state["v"], "state 'v'") if state.get("v") is not None else None
+    W = 0.0
+    for x in weights:
+        W += tree_util._host_weight(x)
+    scale = np.float32(tree_util._inverse(W))
+    count = state["count"] + 1  # optax safe_int32_increment
+    new = dict(state, count=count)
+    if P == 0:  # a template of empty leaves: every norm is 0, nothing to fold or step
+        got = slab.clipped_mean(weights, max_norm)
+        return ClippedUpdate(new, got.norms, got.clipped_norms if with_clipped_norms else None, got.clipped)
+    desc = opt.descriptor(count)
+    rows = slab.rows
+    w_dev = slab.weight_vector(weights)
+    # every leaf of every row as a row of fjagg_l2sq_rows: the pytree route's reduction order
+    leaf_ptrs = slab.storage.data_ptr() + 4 * (np.arange(K, dtype=np.int64)[:, None] * slab.row_stride
+                                               + slab.offsets[None, :-1])
+    l2sq = tree_util._l2sq_table(leaf_ptrs, np.array(slab.sizes, dtype=np.int64), dev)
+    norms, c = kernels.clip_scales(l2sq, max_norm)
+    nbytes = rows.numel() * rows.element_size()
+    nt = nbytes >= tree_util.NONTEMPORAL_MIN_BYTES if nontemporal is None else bool(nontemporal)
+    l2sq_clipped = kernels.clipped_update_dense(rows, w_dev, c, float(scale), desc, params, m, v, mean_out,
+                                                nontemporal=nt, with_clipped_l2sq=with_clipped_norms)
+    if with_clipped_norms:
+        clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+    else:
+        clipped_norms, clipped = None, kernels.clip_flags(c)
+    return ClippedUpdate(new, norms, clipped_norms, clipped)
+
+
+def fused_tree_clipped_mean_update(pytrees_and_weights, max_norm: float, opt: ServerOptimizer, params,
+                                   state: dict, *, mean_out=None, with_clipped_norms: bool = True,
+                                   nontemporal: Optional[bool] = None) -> ClippedUpdate:
+    """:func:`fused_clipped_mean_update` on separate pytrees: ``tree_clipped_mean`` of the
+    clients' delta pytrees (mime_lite.py:131-149) and ``opt``'s update of the ``params`` pytree
+    (float32 device leaves with the deltas' structure and shapes, updated in place) in ONE fold
+    (``fjagg_server_update_clip_ptrs``). ``state`` is ``opt.init(params)``; ``mean_out`` an
+    optional pytree of float32 leaves that also receives the clipped mean. Returns
+    :class:`ClippedUpdate`; the diagnostics are ``tree_clipped_mean``'s bits on the same deltas
+    (the clipped norms when params, moments and ``mean_out`` leaves are 16-byte aligned wherever
+    the deltas' are, as fresh tensors are: a leaf is folded in element units when any pointer to
+    it is not). Float32 leaves, K <= 4096; no clients raise ``ValueError``.
+
+    :func:`ignore_grads_haiku` optimizers and :func:`adafactor` take the two-step route (the
+    clipped mean, then the fused step or ``opt.apply`` on it): the clip norm covers the frozen
+    leaves too. It has the fused kernel's bits. The plan image carries the weights and state
+    addresses and travels by upload with the descriptor: not capturable."""
+    pairs = pytrees_and_weights if type(pytrees_and_weights) is list else list(pytrees_and_weights)
+    trees, weights, W = tree_util._collect_pairs(pairs)
+    if not trees:
+        raise ValueError("no clients to aggregate")
+    td, rows = tree_util._client_table(trees)
+    row0 = rows[0]
+    K, L = len(trees), len(row0)
+    if any(x.dtype != torch.float32 for x in row0):
+        raise TypeError("the clipped server step takes float32 deltas (got "
+                        f"{sorted({str(x.dtype) for x in row0})})")
+    if K > tree_util._L2_MAX_CLIENTS:
+        raise ValueError(f"the clipped server step supports up to {tree_util._L2_MAX_CLIENTS} clients, got {K}")
+    device = row0[0].device if L else None
+
+    def leaves(tree, what):
+        ls = pytree.flatten_as(td, tree)
+        for x, d in zip(ls, row0):
+            if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_contiguous()
+                    and x.device == device and x.shape == d.shape):
+                raise ValueError(f"{what} leaves must be contiguous float32 device tensors shaped like the deltas")
+        return ls
+
+    p = leaves(params, "params")
+    mo = leaves(mean_out, "mean_out") if mean_out is not None else None
+    if _two_step(opt) or L == 0:
+        if not isinstance(opt, Adafactor):
+            _require_state(opt, state)
+        got = tree_util.tree_clipped_mean(pairs, max_norm)
+        if mo is not None:
+            for dst, src in zip(mo, pytree.flatten_as(td, got.mean)):
+                dst.copy_(src)
+        if isinstance(opt, Adafactor):
+            new = opt.apply(got.mean, state, params)[0]
+        else:
+            new = fused_tree_mean_update([(got.mean, 1.0)], opt, params, state, nontemporal=nontemporal)
+        return ClippedUpdate(new, got.norms, got.clipped_norms if with_clipped_norms else None, got.clipped)
+    _require_state(opt, state)
+    m = leaves(state["m"], "state m") if state.get("m") is not None else None
+    v = leaves(state["v"], "state v") if state.get("v") is not None else None
+    count = state["count"] + 1  # optax safe_int32_increment
+    desc = opt.descriptor(count)
+    leaf_n = np.array([x.numel() for x in row0], dtype=np.int64)
+    in_ptrs = tree_util._ptr_table(rows)
+    l2sq = tree_util._l2sq_table(in_ptrs, leaf_n, device)
+    norms, c = kernels.clip_scales(l2sq, max_norm)
+    l2sq_clipped = torch.empty_like(l2sq) if with_clipped_norms else None
+    out_ptrs = np.array([x.data_ptr() for x in p], dtype=np.int64)
+    st = np.zeros(3 * L, dtype=np.int64)
+    for i, ls in enumerate((m, v, mo)):
+        if ls is not None:
+            st[i * L:(i + 1) * L] = [x.data_ptr() for x in ls]
+    blocks, unaligned = tree_util._leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, st.reshape(3, L), device)
+    nblk = blocks.size // 2
+    if not leaf_n.any() or nblk == 0:  # every leaf is empty: nothing to fold or step
+        if l2sq_clipped is not None:
+            l2sq_clipped.zero_()
+    else:
+        w32 = weights.f32 if isinstance(weights, tree_util._Weights) else np.array(
+            [np.float32(w) for w in weights], np.float32)
+        w_words = np.zeros((K + 1) // 2, dtype=np.int64)
+        w_words.view(np.uint8)[:4 * K] = w32.view(np.uint8)
+        image = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, blocks, w_words, st])
+        image_dev = _lib.upload(torch.from_numpy(image), device)
+        base = image_dev.data_ptr()
+        w_ptr = base + 8 * (K * L + 2 * L + blocks.size)
+        st_ptr = w_ptr + 8 * w_words.size
+        nbytes = int(leaf_n.sum()) * K * 4
+        nt = nbytes >= tree_util.NONTEMPORAL_MIN_BYTES if nontemporal is None else bool(nontemporal)
+        flags = (_lib.NONTEMPORAL if nt else 0) | (_lib.UNALIGNED if unaligned else 0)
+        need = int(_lib.load().fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)) if with_clipped_norms else 0
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+        _lib.call("fjagg_server_update_clip_ptrs", _lib.F32, base, L, K, nblk, w_ptr, c.data_ptr(),
+                  float(np.float32(tree_util._inverse(W))), ctypes.byref(desc), st_ptr,
+                  None if l2sq_clipped is None else l2sq_clipped.data_ptr(), flags, ws.data_ptr(), ws.numel(),
+                  torch.cuda.current_stream(device).cuda_stream)
+    if with_clipped_norms:
+        clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+    else:
+        clipped_norms, clipped = None, kernels.clip_flags(c)
+    return ClippedUpdate(dict(state, count=count), norms, clipped_norms, clipped)
 
 
 # ------------------------------------------------------- HypCluster: per-cluster server steps
@@ -780,5 +986,6 @@ def adafactor(learning_rate, min_dim_size_to_factor: int = 128, decay_rate: floa
                      weight_decay_mask)
 
 
-__all__ = ["Adafactor", "ServerOptimizer", "adafactor", "adagrad", "adam", "fused_grouped_mean_update",
-           "fused_mean_update", "fused_tree_grouped_mean_update", "fused_tree_mean_update", "ignore_grads_haiku", "rmsprop", "sgd", "yogi"]
+__all__ = ["Adafactor", "ClippedUpdate", "ServerOptimizer", "adafactor", "adagrad", "adam",
+           "fused_clipped_mean_update", "fused_grouped_mean_update", "fused_mean_update",
+           "fused_tree_clipped_mean_update", "fused_tree_grouped_mean_update", "fused_tree_mean_update", "ignore_grads_haiku", "rmsprop", "sgd", "yogi"]

@@ -17,6 +17,7 @@
  *     tree_clip_by_global_norm tree_util.py:117-133 fjagg_clip_scales + fjagg_wsum_clip_*
  *     expectation_step algorithms/hyp_cluster.py:268-303  fjagg_wsum_group_* (per-cluster means)
  *     per-cluster apply algorithms/hyp_cluster.py:107-128 fjagg_server_update_group_* (means + steps)
+ *     clipped round algorithms/mime_lite.py:131-149,162-167 fjagg_server_update_clip_* (clipped mean + step)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -364,6 +365,38 @@ int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t 
  * bit for bit whenever nothing was clipped. Either output may be NULL, not both. */
 int fjagg_clip_finish(const float* norm_dev, const float* c_dev, const float* l2sq_clipped_dev, int64_t K,
                       float* clipped_norm_dev, uint8_t* clipped_dev, void* stream);
+
+/*
+ * Clipped weighted mean with the server optimizer step in the fold's epilogue: a round that
+ * clips the client deltas and then steps the server model (fedjax/algorithms/mime_lite.py:131-149,
+ * then :162-167, `params = p - server_learning_rate * mean`; any clipped FedAvg with an adaptive
+ * server optimizer) in one launch. Float32 deltas, fold, params and state. For every element p
+ *     y[p] = the clipped mean of fjagg_wsum_clip_* with FJAGG_SCALE, bit for bit
+ *            (t_k = fl(fl(c_k * x_k[p]) * w_k), summed in client order, times scale)
+ *     (params, m, v)[p] <- the update rules of fjagg_server_update_dense with *opt and g = y[p]
+ * The mean stays in registers (mean_dev, optional, also receives it). With FJAGG_OPT_SGD the step
+ * is fl(p + fl(f32(-lr) * y)), the bits of Mime Lite's fl(p - fl(f32(lr) * y)).
+ * l2sq_clipped_dev (nullable) receives the clipped squares exactly as fjagg_wsum_clip_* forms
+ * them on the same deltas (the same workgroup partition, partial rows and combine launch);
+ * ws_dev of fjagg_wsum_clip_workspace_bytes(K, P) / fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)
+ * bytes is needed only then. Flags: FJAGG_NONTEMPORAL and, on the pytree entry, FJAGG_UNALIGNED;
+ * the scale is always applied. Everything fjagg_wsum_clip_* refuses, FJAGG_ACCUMULATE, a bad
+ * descriptor, null x / w / c / params, a null moment the rule reads (dense), K < 1, a bad P, ld
+ * or plan, rows over 1 GiB, K > 4096 with l2sq_clipped_dev and a workspace that is too small
+ * return their status on the host with nothing launched.
+ */
+int fjagg_server_update_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                                   const float* w_dev, const float* c_dev, float scale,
+                                   const fjagg_server_opt* opt, float* params_dev, float* m_dev, float* v_dev,
+                                   float* mean_dev, float* l2sq_clipped_dev, int flags, void* ws_dev,
+                                   int64_t ws_bytes, void* stream);
+/* The same on the pytree path: the plan image and state_dev[3*L] of fjagg_server_update_ptrs
+ * (out_ptrs[L] = the params leaves; m | v | mean leaf addresses, 0 where absent). */
+int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                                  const float* w_dev, const float* c_dev, float scale,
+                                  const fjagg_server_opt* opt, const int64_t* state_dev,
+                                  float* l2sq_clipped_dev, int flags, void* ws_dev, int64_t ws_bytes,
+                                  void* stream);
 
 /*
  * Grouped weighted mean: the per-cluster means of HypCluster's expectation step in one fold.
