@@ -299,22 +299,36 @@ __device__ inline Partial shfl_xor(const Partial& p, int m) {
   return q;
 }
 
+// The shift of a row's sums: its first element when that is finite, else 0. The variance is
+// shift-invariant, and sum((x - c)^2) / n - (sum(x - c) / n)^2 with c inside the data has none of
+// the cancellation of the unshifted form, whose error grows with (mean / sigma)^2: at
+// mean / sigma = 1e5 and n = 147456 the unshifted sigma was off by 4e-6 relative, three times
+// the error of a two-pass f32 std. x - c of two f32 is exact in f64 unless their
+// exponents are more than 29 apart, where its rounding is far below the sums' own.
+__device__ inline double row_shift(const fjcomp_row& row) {
+  const float c = row.n > 0 ? row.ptr[0] : 0.0f;
+  return fabsf(c) <= FLT_MAX ? (double)c : 0.0;
+}
+
 // Per-lane accumulator: min / max / |max| in f32 (exact; NaN tracked by a flag, as the
-// f64 nan_min / nan_max fold it into), sums in f64. v*v of an f32 v is exact in f64, so
-// fma(v, v, s) is the rounding of s + v*v.
+// f64 nan_min / nan_max fold it into), sums in f64 of v = x, or with SHIFT of v = x - c. v*v of
+// an f32 v is exact in f64, so fma(v, v, s) is the rounding of s + v*v. The sum of magnitudes
+// is never shifted.
+template <bool SHIFT>
 struct LaneStats {
   float mn = INFINITY, mx = -INFINITY, amx = -INFINITY;
   double s1 = 0.0, s2 = 0.0, sa = 0.0;
+  double c = 0.0;
   bool nan = false;
   __device__ inline void add(float x) {
     nan |= x != x;
     mn = fminf(mn, x);
     mx = fmaxf(mx, x);
     amx = fmaxf(amx, fabsf(x));
-    const double v = (double)x;
+    const double v = SHIFT ? (double)x - c : (double)x;
     s1 += v;
     s2 = __fma_rn(v, v, s2);
-    sa += fabs(v);  // |double(x)| == double(|x|): the abs is a free source modifier
+    sa += fabs((double)x);  // |double(x)| == double(|x|): the abs is a free source modifier
   }
   __device__ inline Partial partial() const {
     const double qn = __longlong_as_double(0x7ff8000000000000ll);
@@ -393,6 +407,7 @@ struct MinMax {
 // One workgroup per 16 Ki-element chunk of a row: a scalar head up to the first 16-byte
 // boundary, float4 loads eight deep per lane, a scalar tail; then the fixed-order wave
 // butterfly and a per-workgroup combine in wave order (deterministic).
+template <bool SHIFT>
 __global__ __launch_bounds__(kStatsThreads) void k_row_stats(const fjcomp_row* __restrict__ rows,
                                                               const int64_t* __restrict__ prefix, int64_t R,
                                                               Partial* __restrict__ part) {
@@ -406,7 +421,8 @@ __global__ __launch_bounds__(kStatsThreads) void k_row_stats(const fjcomp_row* _
   const bool vec = ((uintptr_t)x & 3) == 0;  // else everything goes through the scalar tail
   const int head = vec ? min(n, (int)(((16 - ((uintptr_t)x & 15)) & 15) >> 2)) : 0;
   const int nv = vec ? (n - head) >> 2 : 0;
-  LaneStats st;
+  LaneStats<SHIFT> st;
+  if (SHIFT) st.c = row_shift(row);
   if ((int)threadIdx.x < head) st.add(x[threadIdx.x]);
   const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + head);
   int i = threadIdx.x;
@@ -444,10 +460,11 @@ __global__ __launch_bounds__(kStatsThreads) void k_row_stats(const fjcomp_row* _
 }
 
 // One wave per row: lane j merges chunks j, j + 64, ... in order, then a fixed butterfly.
+// `shifted`: the partials' sum and sumsq are those of x - row_shift(row) (k_row_stats).
 __global__ __launch_bounds__(256) void k_stats_combine(const fjcomp_row* __restrict__ rows,
                                                         const int64_t* __restrict__ prefix, int64_t R,
                                                         const Partial* __restrict__ part, int method,
-                                                        fjcomp_stats* __restrict__ stats,
+                                                        int shifted, fjcomp_stats* __restrict__ stats,
                                                         fjcomp_qparams* __restrict__ qp) {
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -457,11 +474,17 @@ __global__ __launch_bounds__(256) void k_stats_combine(const fjcomp_row* __restr
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) merge(t, shfl_xor(t, m));
   if (lane != 0) return;
-  stats[r] = fjcomp_stats{t.mn, t.mx, t.amx, t.s1, t.s2, t.sa};
+  if (shifted) {  // report the plain sums: sum x = s1 + n c, sum x^2 = s2 + 2 c s1 + n c^2
+    const double c = row_shift(rows[r]), n = (double)rows[r].n;
+    stats[r] = fjcomp_stats{t.mn, t.mx, t.amx, t.s1 + n * c, t.s2 + 2.0 * c * t.s1 + n * c * c, t.sa};
+  } else {
+    stats[r] = fjcomp_stats{t.mn, t.mx, t.amx, t.s1, t.s2, t.sa};
+  }
   if (!qp) return;
   fjcomp_qparams q;
   if (method == FJCOMP_TERNGRAD) {
-    // jnp.std (ddof 0) in f64, rounded once; thr = f32(2.5) * sigma (compression.py:331-332)
+    // jnp.std (ddof 0) in f64, rounded once; thr = f32(2.5) * sigma (compression.py:331-332).
+    // t.s1, t.s2 are the sums of the shifted values when `shifted`: the variance is the same
     const double n = (double)rows[r].n;
     const double mean = t.s1 / n;
     double var = t.s2 / n - mean * mean;
@@ -1091,10 +1114,17 @@ int fjcomp_row_stats(const fjcomp_row* rows, const int64_t* chunk_prefix, int64_
                 (long long)fjcomp_row_stats_workspace_bytes(nchunks));
   hipStream_t s = as_stream(stream);
   Partial* part = static_cast<Partial*>(ws);
-  hipLaunchKernelGGL(k_row_stats, dim3((unsigned)nchunks), dim3(kStatsThreads), 0, s, rows, chunk_prefix, R, part);
+  // sigma wants shifted sums (row_shift); every other statistic wants the plain ones
+  const int shifted = qparams && method == FJCOMP_TERNGRAD;
+  if (shifted)
+    hipLaunchKernelGGL(k_row_stats<true>, dim3((unsigned)nchunks), dim3(kStatsThreads), 0, s, rows, chunk_prefix, R,
+                       part);
+  else
+    hipLaunchKernelGGL(k_row_stats<false>, dim3((unsigned)nchunks), dim3(kStatsThreads), 0, s, rows, chunk_prefix, R,
+                       part);
   if (int rc = check_launch("k_row_stats")) return rc;
   hipLaunchKernelGGL(k_stats_combine, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, rows, chunk_prefix, R, part,
-                     method, stats, qparams);
+                     method, shifted, stats, qparams);
   return check_launch("k_stats_combine");
 }
 
@@ -1108,7 +1138,7 @@ int fjcomp_stats_combine(const fjcomp_row* rows, const int64_t* part_prefix, int
                 method);
   if (!R) return FJAGG_OK;
   hipLaunchKernelGGL(k_stats_combine, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, as_stream(stream), rows,
-                     part_prefix, R, static_cast<const Partial*>(part), method, stats, qparams);
+                     part_prefix, R, static_cast<const Partial*>(part), method, 0, stats, qparams);
   return check_launch("k_stats_combine");
 }
 

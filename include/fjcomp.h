@@ -124,6 +124,8 @@ int fjcomp_rademacher(const fjcomp_sign_job* jobs, const int64_t* block_prefix, 
 /* Statistics of R rows (f32). chunk_prefix[R+1] (device): running sum of
  * max(1, ceil(n / FJCOMP_STATS_CHUNK)); nchunks its last entry. Writes stats[R] and, when
  * method is FJCOMP_UNIFORM, FJCOMP_BINARY or FJCOMP_TERNGRAD, qparams[R] (may be NULL).
+ * TERNGRAD's sigma comes from the f64 sums of x - x[0] (no cancellation against the mean);
+ * the sum and sumsq reported for such a call are recovered from those.
  * Workspace: fjcomp_row_stats_workspace_bytes(nchunks). */
 #define FJCOMP_STATS_CHUNK 16384
 int64_t fjcomp_row_stats_workspace_bytes(int64_t nchunks);
