@@ -83,6 +83,9 @@ _SIGNATURES = {
                                               _vp, _i32, _vp, _i64, _vp]),
     "fjagg_server_update_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp,
                                              _i64, _vp]),
+    "fjagg_wsum_clip_noise_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp, _i64,
+                                           _vp]),
+    "fjagg_wsum_clip_noise_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _i64, _vp]),
     "fjagg_wsum_group_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _i64, _i32, _vp]),
     "fjagg_group_dense_shape": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64]),
@@ -99,6 +102,8 @@ _SIGNATURES = {
     "fjcomp_prng_sequence": (_i32, [_vp, _i64, _vp]),
     "fjcomp_random_bits": (_i32, [_u32, _u32, _i64, _vp, _vp]),
     "fjcomp_uniform": (_i32, [_u32, _u32, _i64, _vp, _vp]),
+    "fjcomp_normal": (_i32, [_vp, _i64, _vp, _vp]),
+    "fjcomp_normal_from_bits": (_i32, [_vp, _i64, _vp, _vp]),
     "fjcomp_rademacher": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
     "fjcomp_row_stats_workspace_bytes": (_i64, [_i64]),
     "fjcomp_row_stats": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
@@ -150,6 +155,19 @@ class ServerOpt(ctypes.Structure):
                 ("one_minus_b2", ctypes.c_float), ("b2", ctypes.c_float), ("bc1", ctypes.c_float),
                 ("bc2", ctypes.c_float), ("eps", ctypes.c_float), ("eps_root", ctypes.c_float),
                 ("flags", ctypes.c_int)]
+
+
+NOISE_MAX_LEAVES = 64
+
+
+class NoiseLeaf(ctypes.Structure):
+    """struct fjagg_noise_leaf (include/fjagg.h)."""
+    _fields_ = [("begin", _i64), ("n", _i64), ("k0", _u32), ("k1", _u32)]
+
+
+class Noise(ctypes.Structure):
+    """struct fjagg_noise (include/fjagg.h)."""
+    _fields_ = [("stddev", _f32), ("L", ctypes.c_int32), ("leaves", _vp), ("leaves_dev", _vp)]
 
 
 OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP, OPT_YOGI = 1, 2, 3, 4, 5, 6

@@ -5,6 +5,7 @@ from fedjax_amd.aggregators.aggregator import AggregatorState
 from fedjax_amd.aggregators.aggregator import ClippedMeanAggregatorState
 from fedjax_amd.aggregators.aggregator import MeanAggregatorState
 from fedjax_amd.aggregators.aggregator import clipped_mean_aggregator
+from fedjax_amd.aggregators.aggregator import dp_clipped_mean_aggregator
 from fedjax_amd.aggregators.aggregator import mean_aggregator
 from fedjax_amd.aggregators.streaming import RunningMean
 from fedjax_amd.aggregators import compression

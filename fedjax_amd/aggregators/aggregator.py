@@ -9,12 +9,18 @@ Mirror of google/fedjax 0.0.17 ``fedjax/aggregators/aggregator.py``:
   the GPU in one kernel launch per leaf-dtype group;
 * :func:`clipped_mean_aggregator` — the weighted mean of clients each clipped to a maximum
   l2 norm first (the loop of fedjax/algorithms/mime_lite.py:131-149 as an aggregator),
-  :func:`fedjax_amd.tree_util.tree_clipped_mean`.
+  :func:`fedjax_amd.tree_util.tree_clipped_mean`;
+* :func:`dp_clipped_mean_aggregator` — that mean plus Gaussian noise calibrated to the clip norm
+  (DP-FedAvg; no reference counterpart), :func:`fedjax_amd.tree_util.tree_dp_clipped_mean`.
 """
 
-from typing import Any, Callable, Dict, Iterable, Tuple
+import dataclasses as std_dataclasses
+from typing import Any, Callable, Dict, Iterable, Optional, Tuple
+
+import numpy as np
 
 from fedjax_amd import dataclasses
+from fedjax_amd import random as fj_random
 from fedjax_amd import tree_util
 from fedjax_amd.typing import ClientId, Params
 
@@ -80,6 +86,9 @@ class ClippedMeanAggregatorState:
     norms: Dict[ClientId, Any]
     clipped_norms: Dict[ClientId, Any]
     clipped: Dict[ClientId, Any]
+    # dp_clipped_mean_aggregator: the float32 noise standard deviation of the round (else None);
+    # a host number, so structure and not a pytree child
+    noise_stddev: Optional[float] = std_dataclasses.field(default=None, metadata={"pytree_node": False})
 
 
 def clipped_mean_aggregator(max_norm: float) -> Aggregator:
@@ -104,5 +113,56 @@ def clipped_mean_aggregator(max_norm: float) -> Aggregator:
         return got.mean, ClippedMeanAggregatorState(
             dict(zip(ids, got.norms.unbind())), dict(zip(ids, got.clipped_norms.unbind())),
             dict(zip(ids, got.clipped.unbind())))
+
+    return Aggregator(init, apply)
+
+
+def dp_noise_stddev(noise_multiplier: float, max_norm: float, weights) -> float:
+    """``f32(noise_multiplier * max_norm * max_k(w_k) / W)``, in Python floats: the noise scale
+    of a weighted mean whose clients are clipped to ``max_norm``. Replacing one client's update
+    moves the clipped weighted mean by at most ``max_norm * w_k / W`` in l2 norm, its
+    sensitivity; the Gaussian mechanism's standard deviation is ``noise_multiplier`` times that."""
+    ws = [float(tree_util._host_weight(w)) for w in weights]
+    W = 0.0
+    for w in ws:
+        W += w
+    return float(np.float32(float(noise_multiplier) * float(max_norm) * max(ws) / W))
+
+
+def dp_clipped_mean_aggregator(max_norm: float, noise_multiplier: float, rng) -> Aggregator:
+    """Builds the differentially private mean aggregator of DP-FedAvg: every client's params are
+    clipped to l2 norm ``max_norm`` (as :func:`clipped_mean_aggregator`), averaged by weight, and
+    Gaussian noise of standard deviation
+
+        noise_stddev = f32(noise_multiplier * max_norm * max_k(w_k) / W)
+
+    (:func:`dp_noise_stddev`: one client's l2 sensitivity times the multiplier) is added to every
+    coordinate, inside the fold (:func:`fedjax_amd.tree_util.tree_dp_clipped_mean`). ``rng`` is a
+    :class:`fedjax_amd.random.PRNGSequence` or a key (then a sequence over it): each ``apply``
+    takes one fresh key, so no two rounds share noise. The state is a
+    :class:`ClippedMeanAggregatorState` with the round's ``noise_stddev``. Privacy accounting is
+    the caller's. ``apply`` raises under stream capture (a replay would reuse the noise)."""
+    if not isinstance(rng, fj_random.PRNGSequence):
+        rng = fj_random.PRNGSequence(fj_random.strict_key(rng))
+    for name, v in (("max_norm", max_norm), ("noise_multiplier", noise_multiplier)):
+        if not (float(v) >= 0.0 and np.isfinite(float(v))):
+            raise ValueError(f"{name} must be finite and >= 0, got {v}")
+
+    def init():
+        return ClippedMeanAggregatorState({}, {}, {}, None)
+
+    def apply(clients_params_and_weights, state):
+        del state  # each round's diagnostics replace the last round's
+        ids, pairs = [], []
+        for client_id, param, weight in clients_params_and_weights:
+            ids.append(client_id)
+            pairs.append((param, weight))
+        if not pairs:
+            return None, ClippedMeanAggregatorState({}, {}, {}, None)
+        stddev = dp_noise_stddev(noise_multiplier, max_norm, [w for _, w in pairs])
+        got = tree_util.tree_dp_clipped_mean(pairs, max_norm, stddev, next(rng))
+        return got.mean, ClippedMeanAggregatorState(
+            dict(zip(ids, got.norms.unbind())), dict(zip(ids, got.clipped_norms.unbind())),
+            dict(zip(ids, got.clipped.unbind())), stddev)
 
     return Aggregator(init, apply)

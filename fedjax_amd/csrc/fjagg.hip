@@ -19,8 +19,9 @@
 //   * the pytree path walks a device-resident (client, leaf) pointer table with a
 //     workgroup table of unit ranges, so ONE launch covers every leaf of every client;
 //   * epilogue variants: per-client l2 norms accumulated during the same pass
-//     (k_dense_l2), and the server optimizer step consuming the mean in registers
-//     (k_dense_opt);
+//     (k_dense_l2), the server optimizer step consuming the mean in registers
+//     (k_dense_opt), and Gaussian noise drawn per output element onto the clipped mean
+//     (k_dense_clip_noise);
 //   * FJAGG_MODE_SPLIT splits the client axis over blockIdx.y for shapes whose
 //     parameter axis cannot fill 256 CUs, and combines the range sums in order;
 //   * FJAGG_HOST_TABLES: the weights (dense) or the whole plan image + weights
@@ -40,6 +41,7 @@
 
 #include "fjagg.h"
 #include "fjagg_dev.h"
+#include "fjrand_dev.h"
 
 // Shared with fjcomp.hip (same library): the thread-local message behind fjagg_last_error().
 __attribute__((visibility("hidden"))) thread_local char fjagg_g_err[512] = "";
@@ -248,6 +250,59 @@ struct OptEpi {
   }
 };
 
+// NoiseEpi (fjagg_wsum_clip_noise_*): the finished element y = fl(s * scale), the clipped mean,
+// is stored as fl(y + fl(stddev * z)) with z the element's draw of jax.random.normal under its
+// leaf's key (normal_at, fjrand_dev.h): the Gaussian mechanism of DP-FedAvg in the fold's
+// epilogue. One Threefry block and one f64 erfinv per output element, nothing extra in HBM.
+// NoiseLeafEpi (pytree path): the workgroup's elements all belong to one leaf of n elements,
+// the fold's element e is element base + e of that leaf.
+// One draw, out of line: inlined, the E*V copies of the f64 erfinv keep its constants live
+// through the whole fold (hundreds of registers: half the occupancy, or scratch).
+__device__ __noinline__ float noise_draw(uint32_t k0, uint32_t k1, int64_t i, int64_t n) {
+  return normal_at(k0, k1, k0 ^ k1 ^ 0x1BD11BDAu, i, n);
+}
+struct NoiseLeafEpi {
+  float stddev;
+  uint32_t k0, k1;
+  int64_t n, base;
+  __device__ __forceinline__ float apply(int64_t e, float y) const {
+    const float z = noise_draw(k0, k1, base + e, n);
+    return __fadd_rn(y, __fmul_rn(stddev, z));
+  }
+};
+// NoiseTabEpi (dense path): the fold's element e is element e of a slab row; leaf l covers
+// [begin, begin + n) of it (ascending, disjoint; the gaps are padding and get no noise). Only
+// the leaves [lo, hi) can hold an element of this workgroup (wave-uniform, from its unit range),
+// so a lane tests a leaf or two; a 4-element unit may straddle them.
+struct NoiseTabEpi {
+  float stddev;
+  const fjagg_noise_leaf* __restrict__ tab;
+  int lo, hi;
+  __device__ __forceinline__ float apply(int64_t e, float y) const {
+    uint32_t k0 = 0, k1 = 0;
+    int64_t i = 0, n = 0;
+    bool hit = false;
+    for (int l = lo; l < hi; ++l) {
+      const int64_t d = e - tab[l].begin, nl = tab[l].n;
+      if ((uint64_t)d < (uint64_t)nl) {
+        hit = true;
+        i = d;
+        n = nl;
+        k0 = tab[l].k0;
+        k1 = tab[l].k1;
+      }
+    }
+    if (!hit) return y;
+    const float z = noise_draw(k0, k1, i, n);
+    return __fadd_rn(y, __fmul_rn(stddev, z));
+  }
+};
+template <class EPI> struct is_noise_epi : std::false_type {};
+template <> struct is_noise_epi<NoiseLeafEpi> : std::true_type {};
+template <> struct is_noise_epi<NoiseTabEpi> : std::true_type {};
+// the leaf table in the kernel arguments (read in place, see KargWords in fjagg_dev.h)
+struct NoiseTab { fjagg_noise_leaf l[FJAGG_NOISE_MAX_LEAVES]; };
+
 // ------------------------------------------------------------------ fold body
 // Each lane folds E units; unit j of this lane sits at byte offset off[j] of every
 // client row (a 32-bit lane constant) and is written to outp[j]. row(k) returns the
@@ -375,6 +430,14 @@ __device__ __forceinline__ void fold(RowFn row, uint32_t row_bytes, int64_t K,
       const int64_t e0 = off[j] / IB;
 #pragma unroll
       for (int i = 0; i < V; ++i) epi.apply(e0 + i, __uint_as_float(finish<FJAGG_F32, ACC>(acc[j][i], do_scale, scale)));
+    } else if constexpr (is_noise_epi<EPI>::value) {
+      const int64_t e0 = off[j] / IB;
+      unsigned b[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        b[i] = __float_as_uint(epi.apply(e0 + i, __uint_as_float(finish<FJAGG_F32, ACC>(acc[j][i], do_scale, scale))));
+      }
+      store_unit<OUT, V>(outp(j), b);
     } else {
       unsigned b[V];
 #pragma unroll
@@ -1425,6 +1488,139 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip_opt(const int64_t* __res
   } else {
     walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, u1 - u0, nullptr, w, true, scale, false, nrm, epi,
                                            clip);
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
+}
+
+// The clipped fold with Gaussian noise in its epilogue (fjagg_wsum_clip_noise_dense): the second
+// half of DP-FedAvg onto the clipped mean of k_dense_clip. k_dense_clip's unit layout, grid, tail
+// block, LdsNorm rows and partial rows (restated here rather than shared, so that k_dense_clip
+// compiles to the code it always did), folding with DevClip and NoiseTabEpi. The scale is always
+// applied. The leaf table sits in the kernel arguments; each workgroup first narrows it to the
+// leaves its own element range meets (scalar, once).
+template <int V, int E, int U, bool NT, bool L2>
+__global__ __launch_bounds__(kThreads) void k_dense_clip_noise(
+    const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
+    const float* __restrict__ w, const float* __restrict__ c, float scale, uint8_t* __restrict__ out, int64_t S,
+    float* __restrict__ ws, const L2Out l2out, float stddev, int NL, const NoiseTab tab) {
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  const int tid = threadIdx.x;
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  const DevClip clip{c};
+  auto row = [=](int64_t k) { return x + k * ld_bytes; };
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  const bool is_tail = tail_n > 0 && b == 0;
+  if (tail_n > 0) b -= 1;
+  const int64_t u_begin = b * S;
+  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+  // this workgroup's elements [e_lo, e_hi) and the leaves that meet them
+  const int64_t e_lo = is_tail ? nunits * V : u_begin * V, e_hi = is_tail ? nunits * V + tail_n : u_end * V;
+  int lo = NL, hi = 0;
+  for (int l = 0; l < NL; ++l) {
+    const int64_t lb = tab.l[l].begin, ln = tab.l[l].n;
+    if (ln > 0 && lb + ln > e_lo && lb < e_hi) {
+      lo = l < lo ? l : lo;
+      hi = l + 1;
+    }
+  }
+  const NoiseTabEpi epi{stddev, tab.l, lo, hi};
+  if (is_tail) {
+    const bool active = tid < tail_n;
+    if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+      const int64_t e = nunits * V + (active ? tid : 0);
+      const uint32_t off[1] = {(uint32_t)(e * IB)};
+      const bool valid[1] = {active};
+      fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, out, valid, w, true, scale, false, nrm, epi, clip);
+    }
+  } else {
+    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+      uint32_t off[E];
+      bool valid[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        int64_t u = g + j * kThreads + tid;
+        valid[j] = u < u_end;
+        if (!valid[j]) u = u_end - 1;
+        off[j] = (uint32_t)(u * (V * IB));
+      }
+      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, out, valid, w, true, scale, false, nrm, epi, clip);
+    }
+  }
+  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+}
+
+// The same on the pytree path (fjagg_wsum_clip_noise_ptrs): k_ptrs_clip's plan image, block words,
+// XCD remap and unit walk (restated, as k_ptrs_clip restates k_ptrs). Each workgroup owns one
+// leaf's unit range, so its NoiseLeafEpi holds that leaf's key and length (leaf_n of the image)
+// and indexes the draw by the element within the leaf. The keys come from the table in the
+// kernel arguments, or from tab_dev (the same entries on the device) when the tree has more
+// leaves than the arguments hold.
+template <int V, bool NT, bool L2, bool BURST>
+__global__ __launch_bounds__(kThreads) void k_ptrs_clip_noise(const int64_t* __restrict__ img, int L, int64_t K,
+                                                              const float* __restrict__ w,
+                                                              const float* __restrict__ c, float scale, int xcd,
+                                                              float* __restrict__ ws, const L2Out l2out,
+                                                              float stddev,
+                                                              const fjagg_noise_leaf* __restrict__ tab_dev,
+                                                              const NoiseTab tab) {
+  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
+  using ACC = AccF;
+  const int tid = threadIdx.x;
+  const DevClip clip{c};
+  const int64_t* in_ptrs = img;
+  const int64_t* out_ptrs = img + K * L;
+  const int64_t* leaf_n = out_ptrs + L;
+  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1);
+  const int64_t u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t nunits = n / V;
+  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);  // rebased as in k_ptrs
+  uint32_t nk0, nk1;
+  if (tab_dev) {
+    nk0 = tab_dev[leaf].k0;
+    nk1 = tab_dev[leaf].k1;
+  } else {
+    nk0 = tab.l[leaf].k0;
+    nk1 = tab.l[leaf].k1;
+  }
+  const NoiseLeafEpi epi{stddev, nk0, nk1, n, e_base};
+  uint8_t* ob = reinterpret_cast<uint8_t*>(out_ptrs[leaf]) + e_base * Elem<OUT>::B;
+  auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((n - e_base) * IB);
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
+  Norm nrm{};
+  if constexpr (L2) {
+    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
+    __syncthreads();
+    nrm = LdsNorm{l2lds + (tid >> 6) * K};
+  }
+  if (tail) {
+    const bool active = tid < n - nunits * V;
+    if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
+      const int64_t e = active ? tid : 0;
+      const uint32_t off[1] = {(uint32_t)(e * IB)};
+      const bool valid[1] = {active};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, true, scale, false, nrm, epi, clip);
+    }
+  } else if (V > 1 && elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, true, scale, false, nrm, epi, clip);
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, u1 - u0, ob, w, true, scale, false, nrm, epi, clip);
   }
   if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, bid);
 }
@@ -3234,6 +3430,202 @@ int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L,
                                               nullptr, l2, s)
              : launch_ptrs_clip_opt<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev,
                                               nullptr, l2, s);
+}
+
+// ------------------------- clipped weighted mean + Gaussian noise in the fold's epilogue (fjagg.h)
+namespace {
+// The noise descriptor of a DP clipped fold, checked before any launch; *tab receives the
+// kernel-argument table (zeroed past L). dense: the entries are ranges of a P-element row.
+int noise_check(const fjagg_noise* nz, int64_t P, bool dense, NoiseTab* tab) {
+  if (!nz) return fail(FJAGG_EINVAL, "dp clipped fold: null noise descriptor");
+  if (!(nz->stddev >= 0.0f) || nz->stddev > 3.402823466e38f)
+    return fail(FJAGG_EINVAL, "dp clipped fold: stddev must be finite and >= 0");
+  if (nz->L < 1) return fail(FJAGG_EINVAL, "dp clipped fold: L=%d leaves", nz->L);
+  memset(tab, 0, sizeof(*tab));
+  if (nz->L > FJAGG_NOISE_MAX_LEAVES) {
+    if (dense || !nz->leaves_dev)
+      return fail(FJAGG_EUNSUPPORTED, "dp clipped fold: %d leaves, the kernel arguments hold %d", nz->L,
+                  FJAGG_NOISE_MAX_LEAVES);
+    return FJAGG_OK;
+  }
+  if (!nz->leaves) return fail(FJAGG_EINVAL, "dp clipped fold: null leaf table");
+  int64_t end = 0;
+  for (int l = 0; l < nz->L; ++l) {
+    const fjagg_noise_leaf& lf = nz->leaves[l];
+    if (lf.n < 0 || lf.n > (int64_t)UINT32_MAX)
+      return fail(FJAGG_EINVAL, "dp clipped fold: leaf %d has n=%lld outside [0, 2^32)", l, (long long)lf.n);
+    if (dense) {
+      if (lf.begin < end || lf.begin + lf.n > P)
+        return fail(FJAGG_EINVAL, "dp clipped fold: leaf %d [%lld, +%lld) overlaps its predecessor or leaves the row",
+                    l, (long long)lf.begin, (long long)lf.n);
+      end = lf.begin + lf.n;
+    }
+    tab->l[l] = lf;
+  }
+  return FJAGG_OK;
+}
+
+extern "C++" {
+template <int V, int E, int U, bool NT, bool L2>
+int launch_dense_clip_noise_t(const DenseArgs& a, const float* c, float* ws, int64_t ws_floats, L2Out l2,
+                              float stddev, int NL, const NoiseTab& tab, hipStream_t s) {
+  auto kern = k_dense_clip_noise<V, E, U, NT, L2>;
+  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
+  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  // the grid of k_dense_clip (launch_dense_clip_opt_t's rule): the same partial rows, the same
+  // clipped norms bit for bit as fjagg_wsum_clip_dense on the same slab
+  const void* sized_by = L2 ? reinterpret_cast<const void*>(k_dense_clip<V, E, U, NT, true>)
+                            : reinterpret_cast<const void*>(kern);
+  int64_t S = (int64_t)kThreads * E, nblk = 0;
+  balanced_grid(residency(sized_by, smem), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
+  if (a.nunits == 0) nblk = 0;
+  const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
+  if (L2 && grid * a.K > ws_floats)
+    return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
+                (long long)a.K);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
+                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, a.out, S, ws, l2, stddev, NL, tab);
+  if (int rc = check_launch("k_dense_clip_noise")) return rc;
+  return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
+}
+
+// the shapes of launch_dense_clip: E=8 x U=4 where pick_variant says so, else E=1 x U=8
+template <bool L2>
+int launch_dense_clip_noise(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, float* ws,
+                            int64_t ws_floats, L2Out l2, float sd, int NL, const NoiseTab& tab, hipStream_t s) {
+  if (!vec)
+    return nt ? launch_dense_clip_noise_t<1, 1, 8, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
+              : launch_dense_clip_noise_t<1, 1, 8, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
+  if (variant == 12)
+    return nt ? launch_dense_clip_noise_t<4, 8, 4, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
+              : launch_dense_clip_noise_t<4, 8, 4, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
+  return nt ? launch_dense_clip_noise_t<4, 1, 8, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
+            : launch_dense_clip_noise_t<4, 1, 8, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
+}
+
+// launch_ptrs_clip's rule: with norms always the burst schedule, else launch_ptrs_t's
+template <int V, bool L2>
+int launch_ptrs_clip_noise(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w,
+                           const float* c, float scale, float* ws, L2Out l2, float sd,
+                           const fjagg_noise_leaf* tab_dev, const NoiseTab& tab, hipStream_t s) {
+  const dim3 grid((unsigned)nblk), block(kThreads);
+  const int xcd = xcd_remap_bit() ? 1 : 0;
+  if constexpr (L2) {
+    const size_t smem = l2_smem(K, l2);
+    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip_noise<V, true, true, true>)
+                        : reinterpret_cast<const void*>(k_ptrs_clip_noise<V, false, true, true>);
+    if (int rc = allow_lds(kf, smem)) return rc;
+    if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
+                         ws, l2, sd, tab_dev, tab);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
+                         ws, l2, sd, tab_dev, tab);
+    if (int rc = check_launch("k_ptrs_clip_noise (l2)")) return rc;
+    return launch_l2_combine(ws, nblk, K, l2, s);
+  } else {
+    const bool burst = nblk < 2 * (int64_t)cu_count();
+    if (nt && burst)
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         nullptr, l2, sd, tab_dev, tab);
+    else if (nt)
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         nullptr, l2, sd, tab_dev, tab);
+    else if (burst)
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         nullptr, l2, sd, tab_dev, tab);
+    else
+      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
+                         nullptr, l2, sd, tab_dev, tab);
+    return check_launch("k_ptrs_clip_noise");
+  }
+}
+}  // extern "C++"
+}  // namespace
+
+int fjagg_wsum_clip_noise_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                                const float* w_dev, const float* c_dev, float scale, void* out_dev,
+                                float* l2sq_clipped_dev, const fjagg_noise* noise, int flags, void* ws_dev,
+                                int64_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "dp clipped fold: the noise goes onto one mean (no FJAGG_ACCUMULATE)");
+  if (int rc = clip_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "clipped fold: rows <= 1 GiB");
+  if (!x_dev || !w_dev || !c_dev || !out_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < 0)) return fail(FJAGG_EINVAL, "null pointer argument");
+  NoiseTab tab;
+  if (int rc = noise_check(noise, P, true, &tab)) return rc;
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  uint8_t* y = reinterpret_cast<uint8_t*>(out_dev);
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0) &&
+                   ((ld * 4) % 16 == 0) && P >= 4;  // fjagg_wsum_clip_dense's rule
+  const int V = vec ? 4 : 1;
+  DenseArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.K = K;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.w = w_dev;
+  a.scale = scale;
+  a.do_scale = 1;
+  a.accumulate = 0;
+  a.out = y;
+  a.kchunk = K;
+  a.out_ystride = 0;
+  a.balanced = true;
+  a.host_w = false;
+  const int variant = pick_variant(a.nunits, K);
+  const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (l2sq_clipped_dev)
+    return launch_dense_clip_noise<true>(vec, nt, variant, a, c_dev, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
+                                         L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, noise->stddev, noise->L, tab,
+                                         s);
+  return launch_dense_clip_noise<false>(vec, nt, variant, a, c_dev, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr},
+                                        noise->stddev, noise->L, tab, s);
+}
+
+int fjagg_wsum_clip_noise_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                               const float* w_dev, const float* c_dev, float scale, float* l2sq_clipped_dev,
+                               const fjagg_noise* noise, int flags, void* ws_dev, int64_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "dp clipped fold: the noise goes onto one mean (no FJAGG_ACCUMULATE)");
+  if (int rc = clip_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (l2sq_clipped_dev && K > kL2MaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "fused l2 norms support K <= %lld", (long long)kL2MaxClients);
+  if (nblk < 1 || nblk > 0x7fffffff || !image_dev || !w_dev || !c_dev || L < 1)
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (l2sq_clipped_dev && (!ws_dev || ws_bytes < fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)))
+    return fail(FJAGG_EINVAL, "clip workspace too small (need %lld bytes)",
+                (long long)fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk));
+  NoiseTab tab;
+  if (int rc = noise_check(noise, 0, false, &tab)) return rc;
+  if (noise->L != L) return fail(FJAGG_EINVAL, "dp clipped fold: %d noise leaves for a plan of %d", noise->L, L);
+  const fjagg_noise_leaf* tab_dev = L > FJAGG_NOISE_MAX_LEAVES ? noise->leaves_dev : nullptr;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  float* ws = reinterpret_cast<float*>(ws_dev);
+  const float sd = noise->stddev;
+  if (l2sq_clipped_dev) {
+    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
+    return vec ? launch_ptrs_clip_noise<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ws, l2, sd, tab_dev,
+                                                 tab, s)
+               : launch_ptrs_clip_noise<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ws, l2, sd, tab_dev,
+                                                 tab, s);
+  }
+  const L2Out l2{nullptr, nullptr, 0, nullptr};
+  return vec ? launch_ptrs_clip_noise<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, nullptr, l2, sd,
+                                                tab_dev, tab, s)
+             : launch_ptrs_clip_noise<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, nullptr, l2, sd,
+                                                tab_dev, tab, s);
 }
 
 // ------------------------------------------------- grouped weighted mean (fjagg.h)

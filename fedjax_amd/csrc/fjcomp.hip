@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "fjcomp.h"
+#include "fjrand_dev.h"
 
 extern thread_local char fjagg_g_err[512];
 
@@ -71,25 +72,7 @@ int check_launch(const char* what) {
 }
 
 // ------------------------------------------------------------------ threefry2x32-20
-__host__ __device__ inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-#define FJ_TF_ROUND(r) \
-  x0 += x1;            \
-  x1 = rotl32(x1, r);  \
-  x1 ^= x0;
-#define FJ_TF_ROT0 FJ_TF_ROUND(13) FJ_TF_ROUND(15) FJ_TF_ROUND(26) FJ_TF_ROUND(6)
-#define FJ_TF_ROT1 FJ_TF_ROUND(17) FJ_TF_ROUND(29) FJ_TF_ROUND(16) FJ_TF_ROUND(24)
-
-// Threefry-2x32 with 20 rounds and JAX's key schedule (jax/_src/prng.py); k2 = k0 ^ k1 ^ C.
-__host__ __device__ inline void threefry_k(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t& x0, uint32_t& x1) {
-  x0 += k0;
-  x1 += k1;
-  FJ_TF_ROT0 x0 += k1; x1 += k2 + 1u;
-  FJ_TF_ROT1 x0 += k2; x1 += k0 + 2u;
-  FJ_TF_ROT0 x0 += k0; x1 += k1 + 3u;
-  FJ_TF_ROT1 x0 += k1; x1 += k2 + 4u;
-  FJ_TF_ROT0 x0 += k2; x1 += k0 + 5u;
-}
+// (rotl32, the round macros, threefry_k / threefry and bits_to_unit: fjrand_dev.h)
 // Two independent blocks through the same key, round by round (instruction-level parallelism).
 #define FJ_TF_ROUND2(r) \
   a0 += a1; b0 += b1;   \
@@ -107,16 +90,6 @@ __device__ inline void threefry2_k(uint32_t k0, uint32_t k1, uint32_t k2, uint32
   FJ_TF_ROT1_2 a0 += k1; a1 += k2 + 4u; b0 += k1; b1 += k2 + 4u;
   FJ_TF_ROT0_2 a0 += k2; a1 += k0 + 5u; b0 += k2; b1 += k0 + 5u;
 }
-__host__ __device__ inline void threefry(uint32_t k0, uint32_t k1, uint32_t& x0, uint32_t& x1) {
-  threefry_k(k0, k1, k0 ^ k1 ^ 0x1BD11BDAu, x0, x1);
-}
-
-// jax.random.uniform's bits -> [0, 1): bitcast((b >> 9) | 1.0f) - 1
-// ((b >> 9) | 0x3f800000) is one v_alignbit: the low word of (0x7f : b) >> 9.
-__device__ inline float bits_to_unit(uint32_t b) {
-  return __uint_as_float(__builtin_amdgcn_alignbit(0x7fu, b, 9u)) - 1.0f;
-}
-
 // ------------------------------------------------------------------ f32 helpers
 // Branch-free (the branchy forms compiled to exec-mask regions inside the per-element loop).
 // jnp.nan_to_num: NaN -> 0, +-inf -> +-FLT_MAX; med3 of a non-NaN x is exact (keeps -0).
@@ -169,6 +142,24 @@ __global__ __launch_bounds__(256) void k_random_bits(uint32_t k0, uint32_t k1, i
     outf[i] = fmaxf(0.0f, bits_to_unit(x0));
     if (i + h < n) outf[i + h] = fmaxf(0.0f, bits_to_unit(x1));
   }
+}
+
+// ------------------------------------------------------------------ standard normal
+// jax.random.normal(key, (n,), float32): k_random_bits' pairs through normal_from_bits
+// (fjrand_dev.h), or (bits != nullptr) that map alone over given bits, one element a lane.
+__global__ __launch_bounds__(256) void k_normal(uint32_t k0, uint32_t k1, int64_t n, const uint32_t* __restrict__ bits,
+                                                 float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (bits) {
+    if (i < n) out[i] = normal_from_bits(bits[i]);
+    return;
+  }
+  const int64_t h = (n + 1) >> 1;
+  if (i >= h) return;
+  uint32_t x0 = (uint32_t)i, x1 = (uint32_t)(i + h < n ? i + h : 0);
+  threefry(k0, k1, x0, x1);
+  out[i] = normal_from_bits(x0);
+  if (i + h < n) out[i + h] = normal_from_bits(x1);
 }
 
 // ------------------------------------------------------------------ rademacher signs
@@ -1083,6 +1074,31 @@ int fjcomp_random_bits(uint32_t k0, uint32_t k1, int64_t n, uint32_t* out, void*
 
 int fjcomp_uniform(uint32_t k0, uint32_t k1, int64_t n, float* out, void* stream) {
   return random_common(k0, k1, n, nullptr, out, stream);
+}
+
+/* jax.random.normal(key, (n,), float32) (jax/_src/random.py _normal_real; fjrand_dev.h) */
+int fjcomp_normal(const uint32_t key[2], int64_t n, float* out_dev, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (!key) return fail(FJAGG_EINVAL, "normal: null key");
+  if (n < 0 || n > (int64_t)UINT32_MAX) return fail(FJAGG_EINVAL, "normal: n=%lld outside [0, 2^32)", (long long)n);
+  if (n == 0) return FJAGG_OK;
+  if (!out_dev) return fail(FJAGG_EINVAL, "normal: null output");
+  const int64_t h = (n + 1) >> 1;
+  hipLaunchKernelGGL(k_normal, dim3((unsigned)((h + 255) / 256)), dim3(256), 0, as_stream(stream), key[0], key[1], n,
+                     (const uint32_t*)nullptr, out_dev);
+  return check_launch("k_normal");
+}
+
+/* the bits -> z map of fjcomp_normal alone: the uniform on (-1, 1) and sqrt(2) * erfinv */
+int fjcomp_normal_from_bits(const uint32_t* bits_dev, int64_t n, float* out_dev, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (n < 0 || n > (int64_t)UINT32_MAX)
+    return fail(FJAGG_EINVAL, "normal_from_bits: n=%lld outside [0, 2^32)", (long long)n);
+  if (n == 0) return FJAGG_OK;
+  if (!bits_dev || !out_dev) return fail(FJAGG_EINVAL, "normal_from_bits: null pointer argument");
+  hipLaunchKernelGGL(k_normal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), 0u, 0u, n, bits_dev,
+                     out_dev);
+  return check_launch("k_normal (bits)");
 }
 
 int fjcomp_rademacher(const fjcomp_sign_job* jobs, const int64_t* block_prefix, int64_t J, int64_t nblocks,

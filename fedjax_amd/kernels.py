@@ -345,6 +345,85 @@ def clipped_sum_dense(x: torch.Tensor, w: torch.Tensor, c: torch.Tensor, *, scal
     return (out, l2sq) if with_clipped_l2sq else out
 
 
+def check_noise_stddev(noise_stddev) -> float:
+    """``noise_stddev`` as the float32 value the kernels take; negative, NaN and inf raise."""
+    if isinstance(noise_stddev, (bool, str)) or not isinstance(noise_stddev, (int, float, np.integer, np.floating)):
+        raise TypeError(f"noise_stddev must be a real number, not {type(noise_stddev).__name__}")
+    with np.errstate(over="ignore"):
+        sd = float(np.float32(noise_stddev))
+    if not (np.isfinite(sd) and sd >= 0.0 and float(noise_stddev) >= 0.0):
+        raise ValueError(f"noise_stddev must be finite and >= 0 (as float32), got {noise_stddev}")
+    return sd
+
+
+def refuse_capture(what: str) -> None:
+    """The differentially private calls bake the noise key into the kernel arguments: a graph
+    replay would add the SAME noise every time, which voids the privacy guarantee without any
+    visible sign. They raise under stream capture, before anything is recorded."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"fedjax_amd: {what} is not capturable: its noise key is a kernel argument, so a "
+                           "graph replay would reuse the noise and void the privacy guarantee")
+
+
+class NoiseTable:
+    """``struct fjagg_noise`` for a DP clipped fold: ``stddev`` and one ``{begin, n, k0, k1}``
+    entry per leaf (``keys``: uint32 [L, 2], leaf order). More than
+    ``FJAGG_NOISE_MAX_LEAVES`` leaves travel as a device table (pytree route only)."""
+
+    def __init__(self, stddev: float, begins, sizes, keys, device: Optional[torch.device] = None):
+        L = len(sizes)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(L, 2)
+        self.host = (_lib.NoiseLeaf * max(L, 1))()
+        for l in range(L):
+            self.host[l].begin, self.host[l].n = int(begins[l]), int(sizes[l])
+            self.host[l].k0, self.host[l].k1 = int(keys[l, 0]), int(keys[l, 1])
+        self.dev = None
+        if L > _lib.NOISE_MAX_LEAVES and device is not None:
+            raw = np.frombuffer(memoryview(self.host), dtype=np.uint8).copy()
+            self.dev = _lib.upload(torch.from_numpy(raw), device)
+        self.desc = _lib.Noise(float(stddev), L, ctypes.addressof(self.host),
+                               None if self.dev is None else self.dev.data_ptr())
+
+    @property
+    def ref(self):
+        return ctypes.byref(self.desc)
+
+
+def dp_clipped_sum_dense(x: torch.Tensor, w: torch.Tensor, c: torch.Tensor, noise: NoiseTable, *, scale: float,
+                         out: Optional[torch.Tensor] = None, nontemporal: bool = False,
+                         with_clipped_l2sq: bool = False):
+    """:func:`clipped_sum_dense` with ``scale`` applied and Gaussian noise added in the fold's
+    epilogue (``fjagg_wsum_clip_noise_dense``): element ``i`` of leaf ``l`` of the result is
+    ``fl(y + fl(stddev * z_l[i]))``, ``y`` the clipped mean's bits and ``z_l =
+    random.normal(keys[l], n_l)``. Elements of a row outside every leaf get no noise. Raises
+    under stream capture (:func:`refuse_capture`)."""
+    refuse_capture("dp_clipped_sum_dense")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the clipped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    _f32_vector("w", w, K)
+    _f32_vector("c", c, K)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, w, c, out)
+    flags = _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0)
+    l2sq, ws, ws_ptr, ws_bytes = None, None, None, 0
+    if with_clipped_l2sq:
+        l2sq = torch.empty(K, dtype=torch.float32, device=dev)
+        ws_bytes = max(int(_lib.load().fjagg_wsum_clip_workspace_bytes(K, P)), 4)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws_ptr = ws.data_ptr()
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_wsum_clip_noise_dense", _lib.F32, x.data_ptr(), ld, K, P, w.data_ptr(), c.data_ptr(),
+              float(scale), out.data_ptr(), None if l2sq is None else l2sq.data_ptr(), noise.ref, flags, ws_ptr,
+              ws_bytes, _stream_handle(dev))
+    return (out, l2sq) if with_clipped_l2sq else out
+
+
 def clip_finish(norms: torch.Tensor, c: torch.Tensor, l2sq_clipped: torch.Tensor):
     """``(clipped_norms, clipped)`` of a clipped fold: ``clipped = (c != 1)`` (bool [K]; true for
     a NaN factor) and the clipped norms — an unclipped client's norm verbatim, else the

@@ -10,8 +10,9 @@ reference would draw:
 * key algebra (``PRNGKey``, ``split``, ``PRNGSequence``) runs on the host in the C++
   of ``libfjagg.so`` (``fjcomp_random_split`` / ``fjcomp_prng_sequence``): a few
   threefry blocks per client, sequential by nature;
-* the per-element draws (``random_bits``, ``uniform``, ``rademacher``) are HIP
-  kernels writing device tensors (``fjcomp_random_bits`` / ``fjcomp_uniform``).
+* the per-element draws (``random_bits``, ``uniform``, ``rademacher``, ``normal``) are HIP
+  kernels writing device tensors (``fjcomp_random_bits`` / ``fjcomp_uniform`` /
+  ``fjcomp_normal``).
 """
 
 from __future__ import annotations
@@ -33,6 +34,20 @@ def _key(key) -> np.ndarray:
     if k.shape != (2,):
         raise ValueError(f"a PRNG key is two uint32 words, got shape {np.shape(key)}")
     return k
+
+
+def strict_key(key) -> np.ndarray:
+    """``key`` as uint32[2], refusing what is not two uint32 words: another dtype than an
+    integer one, another shape, a word outside [0, 2^32). (The differentially private calls
+    use this: a key silently wrapped or truncated would still draw noise, from the wrong stream.)"""
+    a = np.asarray(key)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"a PRNG key is two uint32 words, got dtype {a.dtype}")
+    if a.shape != (2,):
+        raise ValueError(f"a PRNG key is two uint32 words, got shape {a.shape}")
+    if a.dtype != np.uint32 and ((a < 0).any() or (a > 0xFFFFFFFF).any()):
+        raise ValueError("a PRNG key is two uint32 words, got a word outside [0, 2^32)")
+    return np.ascontiguousarray(a.astype(np.uint32))
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -120,10 +135,39 @@ def uniform(key, shape: Shape = (), device=None) -> torch.Tensor:
     return out
 
 
+def normal(key, shape: Shape = (), device=None) -> torch.Tensor:
+    """``jax.random.normal(key, shape)`` (float32): jax's bits and its uniform on (-1, 1),
+    then ``sqrt(2) * erfinv(u)`` evaluated in float64 and rounded once to float32
+    (``fjcomp_normal``; XLA's own float32 ``erf_inv`` polynomial is not reproduced, so the
+    last step may differ from a JAX run in the last place). Every value is finite."""
+    k = _key(key)
+    shape, n = _size(shape)
+    dev = _device(device)
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    _lib.call("fjcomp_normal", _ptr(k), n, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def normal_from_bits(bits: torch.Tensor) -> torch.Tensor:
+    """The bits -> value map of :func:`normal` alone (``fjcomp_normal_from_bits``):
+    ``normal(key, shape)`` is ``normal_from_bits(random_bits(key, shape))``. ``bits``: a
+    contiguous int32 device tensor holding the 32-bit words, as :func:`random_bits` returns."""
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or not bits.is_contiguous():
+        raise TypeError("bits must be a contiguous int32 tensor (the words of random_bits)")
+    if not bits.is_cuda:
+        raise ValueError("bits must be a device tensor")
+    _size(tuple(bits.shape))
+    out = torch.empty(bits.shape, dtype=torch.float32, device=bits.device)
+    _lib.call("fjcomp_normal_from_bits", bits.data_ptr(), bits.numel(), out.data_ptr(),
+              torch.cuda.current_stream(bits.device).cuda_stream)
+    return out
+
+
 def rademacher(key, shape: Shape = (), device=None) -> torch.Tensor:
     """``jax.random.rademacher(key, shape)``: int32 +-1 (+1 where uniform < 0.5)."""
     u = uniform(key, shape, device)
     return torch.where(u < 0.5, 1, -1).to(torch.int32)
 
 
-__all__ = ["PRNGKey", "PRNGSequence", "rademacher", "random_bits", "split", "split_many", "uniform"]
+__all__ = ["PRNGKey", "PRNGSequence", "normal", "normal_from_bits", "rademacher", "random_bits", "split", "split_many",
+           "strict_key", "uniform"]

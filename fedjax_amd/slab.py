@@ -178,6 +178,59 @@ class ClientDeltaSlab:
         clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
         return tree_util.ClippedMean(self.unflatten(flat), norms, clipped_norms, clipped)
 
+    def dp_clipped_mean(self, weights: Sequence, max_norm: float, noise_stddev: float, key, *,
+                        out: Optional[torch.Tensor] = None) -> "tree_util.ClippedMean":
+        """:meth:`clipped_mean` with Gaussian noise of standard deviation ``noise_stddev`` added to
+        the clipped mean inside the fold — both halves of DP-FedAvg in the passes and launches of
+        ``clipped_mean``. Leaf ``l`` of the mean is, bit for bit,
+
+            clipped_mean(...).mean[l] + f32(noise_stddev) * random.normal(keys[l], shape_l)
+
+        (a float32 multiply, then a float32 add) with ``keys = random.split(key, L)`` in jax leaf
+        order, the schedule of ``uniform_stochastic_quantize_pytree``; the same bits as
+        :func:`tree_util.tree_dp_clipped_mean` over the same deltas. The draw happens in the fold's
+        epilogue: no noise tensor, no second launch. ``norms``, ``clipped_norms`` and ``clipped``
+        are ``clipped_mean``'s. The row padding past ``num_params`` is not written.
+
+        ``key``: two uint32 words (``random.PRNGKey`` / ``split`` / ``PRNGSequence``); use each key
+        once. Calibrating ``noise_stddev`` to ``max_norm`` is the caller's
+        (:func:`fedjax_amd.aggregators.dp_clipped_mean_aggregator` does it for the weighted mean).
+
+        Raises under stream capture: the key is baked into the kernel arguments, so a graph replay
+        would reuse the noise, and that silently voids the privacy guarantee."""
+        from fedjax_amd import random as fj_random
+
+        kernels.refuse_capture("dp_clipped_mean")
+        sd = kernels.check_noise_stddev(noise_stddev)
+        key = fj_random.strict_key(key)
+        if self.dtype != torch.float32:
+            raise TypeError(f"dp_clipped_mean needs a float32 slab, not {self.dtype}")
+        if self.num_clients > tree_util._L2_MAX_CLIENTS:
+            raise ValueError(f"dp_clipped_mean supports up to {tree_util._L2_MAX_CLIENTS} clients")
+        if self.num_params == 0:  # nothing to fold, nothing to draw
+            return self.clipped_mean(weights, max_norm, out=out)
+        L = len(self.sizes)
+        if L > _lib.NOISE_MAX_LEAVES:
+            raise ValueError(f"dp_clipped_mean on a slab takes up to {_lib.NOISE_MAX_LEAVES} leaves (got {L}); "
+                             "use tree_util.tree_dp_clipped_mean over the client views")
+        W = 0.0
+        for x in weights:
+            W += tree_util._host_weight(x)
+        scale = tree_util._inverse(W)
+        rows = self.rows
+        w_dev = self.weight_vector(weights)
+        noise = kernels.NoiseTable(sd, self.offsets[:-1], self.sizes, fj_random.split(key, L))
+        leaf_ptrs = self.storage.data_ptr() + 4 * (np.arange(self.num_clients, dtype=np.int64)[:, None] * self.row_stride
+                                                   + self.offsets[None, :-1])
+        l2sq = tree_util._l2sq_table(leaf_ptrs, np.array(self.sizes, dtype=np.int64), self.device)
+        norms, c = kernels.clip_scales(l2sq, max_norm)
+        nbytes = rows.numel() * rows.element_size()
+        flat, l2sq_clipped = kernels.dp_clipped_sum_dense(
+            rows, w_dev, c, noise, scale=float(np.float32(scale)), out=out,
+            nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES, with_clipped_l2sq=True)
+        clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+        return tree_util.ClippedMean(self.unflatten(flat), norms, clipped_norms, clipped)
+
     def grouped_mean(self, weights: Sequence, group_ids: Sequence[int], num_groups: int, *,
                      out: Optional[torch.Tensor] = None) -> list:
         """Per-group weighted means of the rows in ONE pass over the slab: the expectation step

@@ -44,6 +44,7 @@ __all__ = [
     "tree_mean", "tree_size", "tree_l2_squared", "tree_l2_norm", "tree_clip_by_global_norm",
     "tree_l2_norms", "tree_mean_with_l2_norms", "WeightedTree", "PendingSum", "set_deferred_sums",
     "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
+    "tree_dp_clipped_mean",
     "tree_grouped_mean",
 ]
 
@@ -207,7 +208,7 @@ def _leaf_rule(dt: torch.dtype, kinds: Sequence[int], scaled_kind: Optional[int]
 def _fold(rows, weights, *, scale=None,
           out: Optional[List[torch.Tensor]] = None, accumulate: bool = False,
           nontemporal: Optional[bool] = None, validated: bool = False,
-          l2sq: Optional[torch.Tensor] = None, clip=None) -> List[torch.Tensor]:
+          l2sq: Optional[torch.Tensor] = None, clip=None, noise=None) -> List[torch.Tensor]:
     """y_l = [out_l +] sum_k fl(rows[k][l] * w_k) [* scale] for every leaf l, one
     kernel launch per (input, fold, output) dtype group. ``out`` gives the
     destination tensors (fresh ones otherwise); ``accumulate`` folds into them.
@@ -218,7 +219,9 @@ def _fold(rows, weights, *, scale=None,
     over all leaves, from the same pass (fjagg_wsum_l2_ptrs; float leaves of one dtype).
     ``clip`` = (c, l2sq_clipped): the clipped fold (fjagg_wsum_clip_ptrs; float32 leaves): client
     k's elements are multiplied by the device factor c[k] (float32 [K]) before its weight, and
-    l2sq_clipped (float32 [K] or None) receives the squared norms of those products."""
+    l2sq_clipped (float32 [K] or None) receives the squared norms of those products.
+    ``noise`` = (stddev, keys uint32 [L, 2]) with ``clip``: the DP clipped fold
+    (fjagg_wsum_clip_noise_ptrs), leaf l's elements plus stddev * normal(keys[l]) in the epilogue."""
     if accumulate and out is None:
         raise ValueError("accumulate needs out")
     table = rows if isinstance(rows, _Table) else None
@@ -265,6 +268,8 @@ def _fold(rows, weights, *, scale=None,
             raise TypeError("fused l2 norms need float leaves of one dtype and a float fold")
         if l2sq.dtype != torch.float32 or l2sq.numel() != K or l2sq.device != device:
             raise ValueError(f"l2sq must be a float32 [{K}] tensor on {device}")
+    if noise is not None and (clip is None or accumulate or scale is None):
+        raise ValueError("the noise epilogue belongs to the clipped, scaled fold")
     if clip is not None:
         if l2sq is not None:
             raise ValueError("clip and l2sq are separate folds")
@@ -321,6 +326,13 @@ def _fold(rows, weights, *, scale=None,
             c_dev, sq_dev = clip
             need = int(_lib.load().fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk)) if sq_dev is not None else 0
             ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+            if noise is not None:
+                tab = kernels.NoiseTable(noise[0], np.zeros(len(ls), np.int64), leaf_n, np.asarray(noise[1])[ls],
+                                         device)
+                _lib.call("fjagg_wsum_clip_noise_ptrs", in_c, image_dev.data_ptr(), len(ls), K, nblk, w_dev_ptr,
+                          c_dev.data_ptr(), sc, None if sq_dev is None else sq_dev.data_ptr(), tab.ref, flags,
+                          ws.data_ptr(), ws.numel(), stream)
+                continue
             _lib.call("fjagg_wsum_clip_ptrs", in_c, image_dev.data_ptr(), len(ls), K, nblk, w_dev_ptr,
                       c_dev.data_ptr(), sc, None if sq_dev is None else sq_dev.data_ptr(), flags, ws.data_ptr(),
                       ws.numel(), stream)
@@ -1840,6 +1852,58 @@ def tree_clipped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], max_n
     norms, c = kernels.clip_scales(l2sq, max_norm)
     l2sq_clipped = torch.empty_like(l2sq)
     outs = _fold(rows, weights, scale=_inverse(sum_weight), validated=True, clip=(c, l2sq_clipped))
+    clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
+    return ClippedMean(pytree.unflatten(td, outs), norms, clipped_norms, clipped)
+
+
+def tree_dp_clipped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], max_norm: float, noise_stddev: float,
+                         key) -> ClippedMean:
+    """:func:`tree_clipped_mean` with Gaussian noise of standard deviation ``noise_stddev`` added
+    to the clipped mean inside the fold: both halves of DP-FedAvg (clip every client's update to
+    l2 norm ``max_norm``, average, add N(0, noise_stddev^2) per coordinate) in the passes and
+    launches of ``tree_clipped_mean``. Leaf ``l`` of the mean is, bit for bit,
+
+        tree_clipped_mean(...).mean[l] + f32(noise_stddev) * random.normal(keys[l], shape_l)
+
+    (a float32 multiply, then a float32 add) with ``keys = random.split(key, L)`` in jax leaf
+    order, the schedule of ``uniform_stochastic_quantize_pytree`` (compression.py:105-122); the
+    draws are jax.random's bits (see :func:`fedjax_amd.random.normal` for the last step). The
+    noise is drawn in the fold's epilogue, one Threefry block per output element: no noise tensor
+    in memory and no second launch. ``norms``, ``clipped_norms`` and ``clipped`` are
+    ``tree_clipped_mean``'s. Float32 leaves, K <= 4096; all-``None`` for no clients.
+
+    ``key``: two uint32 words; use each key once. ``noise_stddev`` negative, NaN or inf raises.
+    Raises under stream capture: the key is baked into the kernel arguments, so a graph replay
+    would reuse the noise, and that silently voids the privacy guarantee."""
+    from fedjax_amd import random as fj_random
+
+    kernels.refuse_capture("tree_dp_clipped_mean")
+    sd = kernels.check_noise_stddev(noise_stddev)
+    key = fj_random.strict_key(key)
+    pairs = pytrees_and_weights if type(pytrees_and_weights) is list else list(pytrees_and_weights)
+    trees, weights, sum_weight = _collect_pairs(pairs)
+    if not trees:
+        return ClippedMean(None, None, None, None)
+    K = len(trees)
+    if K > _L2_MAX_CLIENTS:
+        raise ValueError(f"tree_dp_clipped_mean supports up to {_L2_MAX_CLIENTS} clients, got {K}")
+    bad = sorted({str(t.dtype) for t in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(t.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"tree_dp_clipped_mean needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        z = torch.zeros(K, dtype=torch.float32, device=_default_device())
+        return ClippedMean(pytree.unflatten(td, []), z, z.clone(), torch.zeros_like(z, dtype=torch.bool))
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    if not leaf_n.any():  # only empty leaves: nothing to fold, nothing to draw
+        return tree_clipped_mean(pairs, max_norm)
+    keys = fj_random.split(key, len(leaf_n))
+    l2sq = _l2sq_table(_ptr_table(rows), leaf_n, device)
+    norms, c = kernels.clip_scales(l2sq, max_norm)
+    l2sq_clipped = torch.empty_like(l2sq)
+    outs = _fold(rows, weights, scale=_inverse(sum_weight), validated=True, clip=(c, l2sq_clipped), noise=(sd, keys))
     clipped_norms, clipped = kernels.clip_finish(norms, c, l2sq_clipped)
     return ClippedMean(pytree.unflatten(td, outs), norms, clipped_norms, clipped)
 

@@ -18,6 +18,7 @@
  *     expectation_step algorithms/hyp_cluster.py:268-303  fjagg_wsum_group_* (per-cluster means)
  *     per-cluster apply algorithms/hyp_cluster.py:107-128 fjagg_server_update_group_* (means + steps)
  *     clipped round algorithms/mime_lite.py:131-149,162-167 fjagg_server_update_clip_* (clipped mean + step)
+ *     (no reference row) DP-FedAvg's Gaussian mechanism      fjagg_wsum_clip_noise_* (clipped mean + noise)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -397,6 +398,52 @@ int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L,
                                   const fjagg_server_opt* opt, const int64_t* state_dev,
                                   float* l2sq_clipped_dev, int flags, void* ws_dev, int64_t ws_bytes,
                                   void* stream);
+
+/*
+ * Differentially private clipped mean: Gaussian noise in the clipped fold's epilogue, the second
+ * half of DP-FedAvg (McMahan et al. 2018: clip each client's update, average, add N(0, sigma^2));
+ * the reference has the clipping (tree_clip_by_global_norm, tree_util.py:117-133) and no noise
+ * step of its own. Float32 deltas, fold and output. For every element p of leaf l, i its index
+ * inside the leaf,
+ *     y[p]   = the clipped mean of fjagg_wsum_clip_* with FJAGG_SCALE, bit for bit
+ *     out[p] = fl(y[p] + fl(stddev * z_l[i])),   z_l = jax.random.normal(key_l, (n_l,), float32)
+ * with z_l exactly fjcomp_normal's values (fjcomp.h): one Threefry block and one erfinv per
+ * output element in registers, no noise tensor in memory, no second launch. stddev = 0 is not
+ * special-cased (out = fl(y + fl(0 * z))). l2sq_clipped_dev, ws_dev and the workspace sizes are
+ * fjagg_wsum_clip_*'s, the clipped squares the same bits. Flags: FJAGG_SCALE (always applied),
+ * FJAGG_NONTEMPORAL and, on the pytree entry, FJAGG_UNALIGNED. Everything fjagg_wsum_clip_*
+ * refuses, FJAGG_ACCUMULATE, a null or bad descriptor (stddev negative, NaN or inf; L < 1; a leaf
+ * of n < 0 or n >= 2^32; dense leaves that overlap, are not ascending or leave the row) return
+ * their status on the host with nothing launched. The keys are kernel arguments: a captured
+ * launch replays the SAME noise, which voids the privacy guarantee — do not capture these.
+ *
+ * The leaf table travels in the kernel arguments: up to FJAGG_NOISE_MAX_LEAVES entries. The
+ * dense entry refuses more with FJAGG_EUNSUPPORTED; the pytree entry then reads leaves_dev, the
+ * same L entries in device memory (FJAGG_EUNSUPPORTED when that is NULL).
+ */
+#define FJAGG_NOISE_MAX_LEAVES 64
+typedef struct fjagg_noise_leaf {
+  int64_t begin; /* dense: first element of the leaf in a slab row (ascending, disjoint); ptrs: unused */
+  int64_t n;     /* elements of the leaf: the draw's length (ptrs: the plan image's leaf_n is used) */
+  uint32_t k0, k1; /* the leaf's key */
+} fjagg_noise_leaf;
+typedef struct fjagg_noise {
+  float stddev;
+  int32_t L;                         /* leaves (ptrs: the plan's L, in its leaf order) */
+  const fjagg_noise_leaf* leaves;     /* host, L entries (may be NULL when L > FJAGG_NOISE_MAX_LEAVES) */
+  const fjagg_noise_leaf* leaves_dev; /* device, L entries; read by the pytree entry when L > FJAGG_NOISE_MAX_LEAVES */
+} fjagg_noise;
+/* Dense slab (the arguments of fjagg_wsum_clip_dense). Elements of a row outside every leaf
+ * (padding) get no noise: they receive the clipped mean as fjagg_wsum_clip_dense writes it. */
+int fjagg_wsum_clip_noise_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                                const float* w_dev, const float* c_dev, float scale, void* out_dev,
+                                float* l2sq_clipped_dev, const fjagg_noise* noise, int flags, void* ws_dev,
+                                int64_t ws_bytes, void* stream);
+/* Pytree path (the arguments of fjagg_wsum_clip_ptrs): a workgroup of the plan owns one leaf. */
+int fjagg_wsum_clip_noise_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                               const float* w_dev, const float* c_dev, float scale, float* l2sq_clipped_dev,
+                               const fjagg_noise* noise, int flags, void* ws_dev, int64_t ws_bytes,
+                               void* stream);
 
 /*
  * Grouped weighted mean: the per-cluster means of HypCluster's expectation step in one fold.

@@ -18,6 +18,7 @@
  *                         inverse_structured_rotation (and DRIVE) pre/epilogues
  *                         walsh_hadamard.py:25-176, compression.py:269-277
  *   fjcomp_random_bits / fjcomp_uniform   jax.random.bits / uniform of one key
+ *   fjcomp_normal / fjcomp_normal_from_bits   jax.random.normal of one key; its bits -> z map
  *
  * Randomness is jax.random's threefry2x32 (non-partitionable counter layout) and
  * haiku.PRNGSequence; the key schedule runs on the host (fjcomp_random_split,
@@ -111,6 +112,17 @@ int fjcomp_prng_sequence(uint32_t key[2], int64_t n, uint32_t* subkeys);
 /* jax.random.bits(key, (n,), uint32) / jax.random.uniform(key, (n,), float32). */
 int fjcomp_random_bits(uint32_t k0, uint32_t k1, int64_t n, uint32_t* out, void* stream);
 int fjcomp_uniform(uint32_t k0, uint32_t k1, int64_t n, float* out, void* stream);
+/* jax.random.normal(key, (n,), float32) (jax/_src/random.py, _normal_real): the bits of
+ * fjcomp_random_bits, b -> f = bitcast((b >> 9) | 0x3f800000) - 1, the uniform on (-1, 1)
+ *   u = max(lo, fl(fl(f * 2) + lo)),  lo = nextafter(-1f, 0f)   (fl(1 - lo) = 2 exactly)
+ * and z = sqrt(2) * erfinv(u). The bits and u are jax's; the last step is evaluated in f64
+ * (the device erfinv) and rounded once to f32, not XLA's f32 erf_inv polynomial. u is never
+ * +-1, so every z is finite. 0 <= n < 2^32. The DP clipped folds (fjagg_wsum_clip_noise_*,
+ * fjagg.h) draw exactly these values per leaf. */
+int fjcomp_normal(const uint32_t key[2], int64_t n, float* out_dev, void* stream);
+/* The bits -> z map of fjcomp_normal alone over n given words: fjcomp_normal is
+ * fjcomp_random_bits followed by exactly this. */
+int fjcomp_normal_from_bits(const uint32_t* bits_dev, int64_t n, float* out_dev, void* stream);
 
 /* Bit-packed jax.random.rademacher(key, (d,)) for J jobs. A workgroup takes block_pairs
  * (a multiple of 256, at most FJCOMP_SIGN_BLOCK_PAIRS) consecutive element pairs of one job:
