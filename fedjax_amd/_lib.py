@@ -94,6 +94,8 @@ _SIGNATURES = {
                                                _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_server_update_group_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_trim_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i32, _vp]),
+    "fjagg_trim_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

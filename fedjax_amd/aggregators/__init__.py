@@ -4,9 +4,12 @@ from fedjax_amd.aggregators.aggregator import Aggregator
 from fedjax_amd.aggregators.aggregator import AggregatorState
 from fedjax_amd.aggregators.aggregator import ClippedMeanAggregatorState
 from fedjax_amd.aggregators.aggregator import MeanAggregatorState
+from fedjax_amd.aggregators.aggregator import RobustAggregatorState
 from fedjax_amd.aggregators.aggregator import clipped_mean_aggregator
 from fedjax_amd.aggregators.aggregator import dp_clipped_mean_aggregator
 from fedjax_amd.aggregators.aggregator import mean_aggregator
+from fedjax_amd.aggregators.aggregator import median_aggregator
+from fedjax_amd.aggregators.aggregator import trimmed_mean_aggregator
 from fedjax_amd.aggregators.streaming import RunningMean
 from fedjax_amd.aggregators import compression
 from fedjax_amd.aggregators import walsh_hadamard

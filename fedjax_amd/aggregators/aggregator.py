@@ -11,7 +11,10 @@ Mirror of google/fedjax 0.0.17 ``fedjax/aggregators/aggregator.py``:
   l2 norm first (the loop of fedjax/algorithms/mime_lite.py:131-149 as an aggregator),
   :func:`fedjax_amd.tree_util.tree_clipped_mean`;
 * :func:`dp_clipped_mean_aggregator` — that mean plus Gaussian noise calibrated to the clip norm
-  (DP-FedAvg; no reference counterpart), :func:`fedjax_amd.tree_util.tree_dp_clipped_mean`.
+  (DP-FedAvg; no reference counterpart), :func:`fedjax_amd.tree_util.tree_dp_clipped_mean`;
+* :func:`trimmed_mean_aggregator` / :func:`median_aggregator` — the coordinate-wise trimmed mean
+  and median of Yin et al. (ICML 2018; no reference counterpart),
+  :func:`fedjax_amd.tree_util.tree_trimmed_mean` / :func:`fedjax_amd.tree_util.tree_median`.
 """
 
 import dataclasses as std_dataclasses
@@ -164,5 +167,51 @@ def dp_clipped_mean_aggregator(max_norm: float, noise_multiplier: float, rng) ->
         return got.mean, ClippedMeanAggregatorState(
             dict(zip(ids, got.norms.unbind())), dict(zip(ids, got.clipped_norms.unbind())),
             dict(zip(ids, got.clipped.unbind())), stddev)
+
+    return Aggregator(init, apply)
+
+
+@dataclasses.dataclass
+class RobustAggregatorState:
+    """The trimmed-mean and median aggregators are stateless."""
+
+
+def trimmed_mean_aggregator(trim) -> Aggregator:
+    """Builds the coordinate-wise trimmed-mean aggregator (Yin et al., ICML 2018): per coordinate
+    the ``t`` smallest and ``t`` largest client values are dropped and the rest averaged, in one
+    launch (:func:`fedjax_amd.tree_util.tree_trimmed_mean`). ``trim`` is the int count ``t`` or a
+    float fraction ``0 <= beta < 0.5`` of the round's clients (``t = floor(beta * K)``).
+
+    ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
+    client must not be able to scale its own vote in a robust aggregate. Float32 params, at most
+    128 clients a round."""
+    if isinstance(trim, (bool, np.bool_)) or not isinstance(trim, (int, float, np.integer, np.floating)):
+        raise TypeError("trim must be an int count or a float fraction in [0, 0.5)")
+    if isinstance(trim, (float, np.floating)) and not (0.0 <= float(trim) < 0.5):
+        raise ValueError(f"a trim fraction must be in [0, 0.5), got {trim}")
+    if isinstance(trim, (int, np.integer)) and trim < 0:
+        raise ValueError(f"a trim count must be >= 0, got {trim}")
+
+    def init():
+        return RobustAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
+        return tree_util.tree_trimmed_mean(params, trim), state
+
+    return Aggregator(init, apply)
+
+
+def median_aggregator() -> Aggregator:
+    """Builds the coordinate-wise median aggregator (Yin et al., ICML 2018):
+    :func:`fedjax_amd.tree_util.tree_median` of the round's params. ``apply`` takes the usual
+    triples and IGNORES the weights. Float32 params, at most 128 clients a round."""
+
+    def init():
+        return RobustAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
+        return tree_util.tree_median(params), state
 
     return Aggregator(init, apply)

@@ -1,0 +1,200 @@
+// fjrobust.hip — coordinate-wise trimmed mean and median over the client axis
+// (include/fjagg.h: fjagg_trim_dense, fjagg_trim_ptrs; Yin et al., ICML 2018).
+//
+// Not a fold: every coordinate needs two order statistics of its K client values. One lane
+// owns one column (fjrobust_dev.h has the per-column routine and the reasons for its shape):
+// a wave reads 256 contiguous bytes of each client's row with 4-byte loads, so float32's own
+// alignment is all a row needs, and writes one result per lane. The kernels are instantiated
+// for a padded client count N = 16 / 32 / 64 / 128, chosen from K at launch; N = 16 sorts in
+// registers alone, the wider ones stage their keys in N x 256 B of LDS per wave.
+#include <hip/hip_runtime.h>
+
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "fjagg.h"
+#include "fjrobust_dev.h"
+
+// The thread-local message behind fjagg_last_error() (defined in fjagg.hip). Declared __thread:
+// the buffer has a constant initialiser, so no dynamic-initialisation wrapper stands between
+// this file and it.
+extern __attribute__((visibility("hidden"))) __thread char fjagg_g_err[512];
+#define g_err fjagg_g_err
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FJAGG_EHIP, "%s: %s", what, hipGetErrorString(e));
+  return FJAGG_OK;
+}
+
+constexpr int64_t kTrimMaxRowBytes = 1ll << 30;
+constexpr int kTrimMaxClients = 128;
+
+// Workgroup size per width: 256 lanes while the tile stays at 32 KiB, one wave above that
+// (16 KiB at N = 64, 32 KiB at N = 128: five workgroups of a CU's 160 KiB). 256 lanes at every
+// width (a 128 KiB tile at N = 128, one wave a SIMD) measured the same rate: DESIGN 3l.
+template <int N> struct TrimShape { static constexpr int TPB = N <= 32 ? 256 : 64; };
+
+// 4 bytes through a GLOBAL (address space 1) pointer: global_load / global_store, counted in
+// vmcnt only, so the LDS waits of the sort do not wait for them (fjagg_dev.h load16_global).
+typedef __attribute__((address_space(1))) uint32_t gu32;
+template <bool NT>
+__device__ __forceinline__ uint32_t load_bits(const uint32_t* p, uint32_t lane_off) {
+  // p is uniform over the wave (an SGPR base), lane_off the lane's element offset from it: one
+  // offset VGPR serves every client's load
+  const gu32* g = (const gu32*)(reinterpret_cast<uintptr_t>(p)) + lane_off;
+  if constexpr (NT) return __builtin_nontemporal_load(g);
+  else return *g;
+}
+__device__ __forceinline__ void store_bits(uint32_t* p, uint32_t v) { *(gu32*)(reinterpret_cast<uintptr_t>(p)) = v; }
+
+template <int N, int TPB>
+__device__ __forceinline__ fjrobust::KeyPair* lane_tile() {
+  if constexpr (N == 16) {
+    return nullptr;
+  } else {
+    __shared__ fjrobust::KeyPair tile[(N / 2) * TPB];
+    return tile + threadIdx.x;
+  }
+}
+
+// Dense slab: client k's row at x + k*ld, columns [0, P). Lanes past P redo column P-1 and
+// store nothing.
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_dense(const uint32_t* __restrict__ x, int64_t ld, int K,
+                                                                   int64_t P, int t, float scale, int do_scale,
+                                                                   uint32_t* __restrict__ out) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const int64_t col0 = (int64_t)blockIdx.x * TPB, col = col0 + threadIdx.x;
+  const bool valid = col < P;
+  const uint32_t off = valid ? threadIdx.x : (uint32_t)(P - 1 - col0);
+  const uint32_t* base = x + col0;
+  auto load = [=](int k) { return load_bits<NT>(base + (int64_t)k * ld, off); };
+  const uint32_t y = fjrobust::trim_column<N, TPB>(load, K, t, do_scale != 0, scale, lane_tile<N, TPB>());
+  if (valid) store_bits(out + col, y);
+}
+
+// Pytree path over the plan image of fjagg_ptrs_plan_leaves (fjagg.hip k_ptrs: in_ptrs[K*L] |
+// out_ptrs[L] | leaf_n[L] | blocks[2*nblk]). Plan entry blockIdx.x names an element range of one
+// leaf — V-element units (V = 4, or 1 for a plan made with FJAGG_UNALIGNED), single elements
+// with the element flag, or the leaf's tail past its last whole unit — and the 256 / TPB
+// workgroups blockIdx.y of that entry walk it 256 columns at a time, as one 256-lane workgroup
+// of the fold would.
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_ptrs(const int64_t* __restrict__ img, int L, int K, int V,
+                                                                  int t, float scale, int do_scale) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const int64_t* in_ptrs = img;
+  const int64_t* out_ptrs = img + (int64_t)K * L;
+  const int64_t* leaf_n = out_ptrs + L;
+  const int64_t* blk = leaf_n + L + 2 * (int64_t)blockIdx.x;
+  const int64_t be = blk[0];
+  const int leaf = (int)((be >> 40) & 0x3fffff);
+  const bool tail = (be >> 62) & 1;
+  const bool elem = ((uint64_t)be >> 63) != 0;
+  const int64_t u0 = be & ((1ll << 40) - 1), u1 = blk[1];
+  const int64_t n = leaf_n[leaf];
+  const int64_t e0 = tail ? n / V * V : (elem ? u0 : u0 * V);
+  int64_t e1 = tail ? n : (elem ? u1 : u1 * V);
+  if (e1 > n) e1 = n;
+  uint32_t* ob = reinterpret_cast<uint32_t*>(out_ptrs[leaf]);
+  fjrobust::KeyPair* tile = lane_tile<N, TPB>();
+  for (int64_t g = e0 + (int64_t)blockIdx.y * TPB; g < e1; g += 256) {
+    const int64_t col = g + threadIdx.x;
+    const bool valid = col < e1;
+    const uint32_t off = valid ? threadIdx.x : (uint32_t)(e1 - 1 - g);
+    auto load = [=](int k) {
+      return load_bits<NT>(reinterpret_cast<const uint32_t*>(in_ptrs[(int64_t)k * L + leaf]) + g, off);
+    };
+    const uint32_t y = fjrobust::trim_column<N, TPB>(load, K, t, do_scale != 0, scale, tile);
+    if (valid) store_bits(ob + col, y);
+  }
+}
+
+int trim_check(int in_dtype, int64_t K, int64_t t, int flags, int allowed) {
+  if (in_dtype != FJAGG_F32) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: float32 deltas and output only");
+  if (flags & FJAGG_ACCUMULATE)
+    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: order statistics do not accumulate (no FJAGG_ACCUMULATE)");
+  if (flags & FJAGG_NARROW) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no FJAGG_NARROW plans");
+  if (flags & FJAGG_HOST_TABLES)
+    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: device plan only (no FJAGG_HOST_TABLES)");
+  if (flags & FJAGG_ZEROED_WS) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no norms (no FJAGG_ZEROED_WS)");
+  if (flags & FJAGG_UNBALANCED) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no FJAGG_UNBALANCED");
+  if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: unsupported flags 0x%x", flags & ~allowed);
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (K > kTrimMaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: K <= %d clients (got %lld)", kTrimMaxClients, (long long)K);
+  if (t < 0 || 2 * t >= K)
+    return fail(FJAGG_EINVAL, "trimmed mean: need 0 <= 2t < K (t=%lld, K=%lld)", (long long)t, (long long)K);
+  return FJAGG_OK;
+}
+
+template <int N, bool NT>
+int launch_trim_dense(const uint32_t* x, int64_t ld, int K, int64_t P, int t, float scale, int ds, uint32_t* y,
+                      hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)((P + TPB - 1) / TPB));
+  hipLaunchKernelGGL((k_trim_dense<N, NT>), grid, dim3(TPB), 0, s, x, ld, K, P, t, scale, ds, y);
+  return check_launch("k_trim_dense");
+}
+
+template <int N, bool NT>
+int launch_trim_ptrs(const int64_t* img, int L, int K, int64_t nblk, int V, int t, float scale, int ds,
+                     hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)nblk, 256 / TPB);
+  hipLaunchKernelGGL((k_trim_ptrs<N, NT>), grid, dim3(TPB), 0, s, img, L, K, V, t, scale, ds);
+  return check_launch("k_trim_ptrs");
+}
+
+}  // namespace
+
+#define FJ_TRIM_WIDTH(FN, NTV, ...)                    \
+  (K <= 16   ? FN<16, NTV>(__VA_ARGS__)                \
+   : K <= 32 ? FN<32, NTV>(__VA_ARGS__)                \
+   : K <= 64 ? FN<64, NTV>(__VA_ARGS__)                \
+             : FN<128, NTV>(__VA_ARGS__))
+
+extern "C" {
+
+int fjagg_trim_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t t, float scale,
+                     void* out_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = trim_check(in_dtype, K, t, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld (P=%lld, ld=%lld)", (long long)P, (long long)ld);
+  if (P * 4 > kTrimMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: rows <= 1 GiB");
+  if (!x_dev || !out_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(x_dev);
+  uint32_t* y = reinterpret_cast<uint32_t*>(out_dev);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, k = (int)K, tt = (int)t;
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_trim_dense, true, x, ld, k, P, tt, scale, ds, y, s)
+                                     : FJ_TRIM_WIDTH(launch_trim_dense, false, x, ld, k, P, tt, scale, ds, y, s);
+}
+
+int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t, float scale,
+                    int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = trim_check(in_dtype, K, t, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1 || L >= (1 << 22))
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!image_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, k = (int)K, tt = (int)t;
+  const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_trim_ptrs, true, image_dev, L, k, nblk, V, tt, scale, ds, s)
+                                     : FJ_TRIM_WIDTH(launch_trim_ptrs, false, image_dev, L, k, nblk, V, tt, scale, ds, s);
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@ deltas, an unsupported dtype or a missing library raise.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional, Sequence
 
@@ -686,6 +687,89 @@ def grouped_dense_shape(x: torch.Tensor, out: torch.Tensor, tables: GroupTables)
     if rc < 0:
         _lib.check(rc, "fjagg_group_dense_shape")
     return rc
+
+
+TRIM_MAX_CLIENTS = 128  # fjagg_trim_*: a column's K values live in one lane (fjagg.h)
+_MAX_ROW_BYTES = 1 << 30
+
+
+def trim_count(trim, K: int) -> int:
+    """The trim count ``t`` of a trimmed mean over ``K`` clients, checked: ``trim`` is an int count
+    ``t``, or a float fraction ``0 <= beta < 0.5`` giving ``t = floor(beta * K)`` (in double
+    precision: 0.29 of 100 is 28, since 0.29 * 100 < 29). Raises ``TypeError`` for a bool or a
+    non-number, ``ValueError`` for more than 128 clients, a fraction outside [0, 0.5), or a count
+    with ``t < 0`` or ``2t >= K``. Nothing here touches the library."""
+    K = int(K)
+    if isinstance(trim, (bool, np.bool_)):
+        raise TypeError("trim must be an int count or a float fraction in [0, 0.5), not a bool")
+    if K < 1:
+        raise ValueError(f"a trimmed mean needs at least 1 client, got K = {K}")
+    if K > TRIM_MAX_CLIENTS:
+        raise ValueError(f"the trimmed mean and median support K <= {TRIM_MAX_CLIENTS} clients, got K = {K}")
+    if isinstance(trim, (int, np.integer)):
+        t = int(trim)
+    elif isinstance(trim, (float, np.floating)):
+        beta = float(trim)
+        if not (0.0 <= beta < 0.5):
+            raise ValueError(f"a trim fraction must be in [0, 0.5), got {trim}")
+        t = int(math.floor(beta * K))
+    else:
+        raise TypeError(f"trim must be an int count or a float fraction in [0, 0.5), not {type(trim).__name__}")
+    if t < 0 or 2 * t >= K:
+        raise ValueError(f"a trim count needs 0 <= 2t < K: t = {t} leaves no client of K = {K}")
+    return t
+
+
+def trim_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+               nontemporal: bool = False) -> torch.Tensor:
+    """Coordinate-wise trimmed sum of a float32 slab ``x[K, P]`` (row stride ``x.stride(0)``, unit
+    column stride, float32 alignment only): per column the clients of rank ``t .. K-1-t`` in the
+    total order of fjagg.h are added in client order, then multiplied by ``scale`` (the trimmed
+    mean passes f32(1 / (K - 2t))). One launch of ``fjagg_trim_dense``; there are no weights.
+    ``K <= 128``, ``0 <= 2t < K``; everything is checked before the library is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the trimmed mean takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+        raise TypeError("t must be an int trim count")
+    t = trim_count(int(t), K)
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the trimmed mean takes rows of up to 1 GiB")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.dim() != 1 or out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, out)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_trim_dense", _lib.F32, x.data_ptr(), ld, K, P, t, float(scale if scale is not None else 1.0),
+              out.data_ptr(), flags, _stream_handle(dev))
+    return out
+
+
+def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale: Optional[float], *,
+              unaligned: bool = False, nontemporal: bool = False) -> None:
+    """Launch ``fjagg_trim_ptrs`` over a device plan image (``in_ptrs[K*L] | out_ptrs[L] |
+    leaf_n[L] | blocks[2*nblk]``, the blocks of :func:`ptrs_plan` for float32 leaves):
+    :func:`trim_dense`'s arithmetic on every leaf in one launch. ``unaligned`` as the plan was
+    made. Checked before the library is touched."""
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+        raise TypeError("t must be an int trim count")
+    t = trim_count(int(t), K)
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    dev = _require_device(image_dev)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    flags |= _lib.UNALIGNED if unaligned else 0
+    _lib.call("fjagg_trim_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
+              float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:

@@ -290,6 +290,43 @@ class ClientDeltaSlab:
                                       nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return [self.unflatten(out[g]) if alive[g] else None for g in range(G)]
 
+    def trimmed_mean(self, trim, *, out: Optional[torch.Tensor] = None) -> PyTree:
+        """Coordinate-wise trimmed mean of the K rows (Yin et al., ICML 2018): in every coordinate
+        the ``t`` smallest and the ``t`` largest client values are dropped and the rest averaged,
+        so up to ``t`` clients that upload ``inf``, ``NaN`` or huge values in a coordinate do not
+        reach the result. ``trim`` is the int count ``t``, or a float fraction ``0 <= beta < 0.5``
+        giving ``t = floor(beta * K)``; a bool is refused. One launch that reads every delta
+        once, nothing uploaded (graph-capturable), no K x P temporary.
+
+        Values are ranked by the total order ``-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN``
+        (ties by client index); the kept values are added in client order like
+        :meth:`mean` adds and multiplied by f32(1 / (K - 2t)), so ``trim=0`` is bit for bit
+        ``mean([1] * K)``. There are no weights: a robust aggregate that let a client scale its
+        own vote would not be robust. A float32 slab of up to 128 clients. Returns the
+        template's pytree (views into ``out`` if given: float32, ``num_params`` elements)."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"trimmed_mean needs a float32 slab, not {self.dtype}")
+        K = self.num_clients
+        t = kernels.trim_count(trim, K)
+        if self.num_params == 0:  # a template of empty leaves: nothing to launch
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            return self.unflatten(flat)
+        rows = self.rows
+        nbytes = rows.numel() * rows.element_size()
+        flat = kernels.trim_dense(rows, t, scale=float(np.float32(tree_util._inverse(K - 2 * t))), out=out,
+                                  nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return self.unflatten(flat)
+
+    def median(self, *, out: Optional[torch.Tensor] = None) -> PyTree:
+        """Coordinate-wise median of the K rows: :meth:`trimmed_mean` at ``t = (K-1) // 2``. Odd
+        K gives the middle value verbatim, even K ``fl(fl(a + b) * 0.5)`` of the two middle
+        values (a before b in client order); ``np.median``'s bits on finite data. Weights play
+        no part. A float32 slab of up to 128 clients."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"median needs a float32 slab, not {self.dtype}")
+        kernels.trim_count(0, self.num_clients)
+        return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

@@ -45,7 +45,7 @@ __all__ = [
     "tree_l2_norms", "tree_mean_with_l2_norms", "WeightedTree", "PendingSum", "set_deferred_sums",
     "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
     "tree_dp_clipped_mean",
-    "tree_grouped_mean",
+    "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -1970,3 +1970,61 @@ def tree_grouped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], group
               gscale_p, gorder_p, tables.seg.ctypes.data, _lib.SCALE | (_lib.NONTEMPORAL if nt else 0),
               torch.cuda.current_stream(device).cuda_stream)
     return result
+
+
+def tree_trimmed_mean(pytrees: Iterable[PyTree], trim) -> Optional[PyTree]:
+    """Coordinate-wise trimmed mean of client pytrees (Yin et al., ICML 2018): in every coordinate
+    of every leaf the ``t`` smallest and ``t`` largest client values are dropped and the rest
+    averaged — up to ``t`` clients that send ``inf``, ``NaN`` or huge values in a coordinate do not
+    reach the result, which norm clipping cannot promise. ``trim`` is the int count ``t`` or a
+    float fraction ``0 <= beta < 0.5`` giving ``t = floor(beta * K)``; a bool is refused.
+
+    Values are ranked by the total order ``-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN``, ties
+    by client index; the kept values are added in client order as :func:`tree_mean` adds and
+    multiplied by f32(1 / (K - 2t)): ``trim=0`` is bit for bit ``tree_mean`` with unit weights,
+    and the result is bit for bit :meth:`fedjax_amd.slab.ClientDeltaSlab.trimmed_mean` over the
+    same deltas. There are no weights. The structure walk and checks are ``tree_mean``'s; one
+    plan image is uploaded and ONE launch covers every leaf, reading each delta once, with
+    float32 alignment as the only requirement on a leaf. Float32 leaves, ``K <= 128``. The
+    inputs are never written; a one-shot iterable is consumed once; no clients: ``None``.
+    Raises under stream capture (the plan image goes through a pinned staging buffer)."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    K = len(trees)
+    t = kernels.trim_count(trim, K)
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"tree_trimmed_mean needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        return pytree.unflatten(td, [])
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    L = len(leaf_n)
+    # one result row: every leaf at a 16-byte aligned offset
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)])
+    flat = torch.empty(max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = pytree.unflatten(td, [flat[o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+    if not leaf_n.any():
+        return result
+    in_ptrs = _ptr_table(rows)
+    out_ptrs = flat.data_ptr() + 4 * offs[:-1].astype(np.int64)
+    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)
+    image = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, blocks])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    nt = int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES
+    kernels.trim_ptrs(image_dev, L, K, len(blocks) // 2, t, float(np.float32(_inverse(K - 2 * t))), nontemporal=nt)
+    return result
+
+
+def tree_median(pytrees: Iterable[PyTree]) -> Optional[PyTree]:
+    """Coordinate-wise median of client pytrees: :func:`tree_trimmed_mean` at ``t = (K-1) // 2``.
+    Odd K: the middle value verbatim; even K: ``fl(fl(a + b) * 0.5)`` of the two middle values —
+    ``np.median``'s bits on finite data. Float32 leaves, ``K <= 128``; no clients: ``None``."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    kernels.trim_count(0, len(trees))
+    return tree_trimmed_mean(trees, (len(trees) - 1) // 2)

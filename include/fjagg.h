@@ -19,6 +19,7 @@
  *     per-cluster apply algorithms/hyp_cluster.py:107-128 fjagg_server_update_group_* (means + steps)
  *     clipped round algorithms/mime_lite.py:131-149,162-167 fjagg_server_update_clip_* (clipped mean + step)
  *     (no reference row) DP-FedAvg's Gaussian mechanism      fjagg_wsum_clip_noise_* (clipped mean + noise)
+ *     (no reference row) trimmed mean / median (Yin et al. 2018) fjagg_trim_* (order statistics per coordinate)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -541,6 +542,38 @@ int fjagg_server_update_group_ptrs(int in_dtype, const int64_t* image_dev, int L
                                    const fjagg_server_opt* opts_dev, const int64_t* state_dev,
                                    const fjagg_server_opt* opts_host, const int64_t* state_host,
                                    const int64_t* params_host, const int64_t* leaf_n_host, int flags, void* stream);
+
+/*
+ * Coordinate-wise trimmed mean and median over the client axis: the two Byzantine-robust
+ * aggregates of Yin, Chen, Ramchandran and Bartlett, "Byzantine-Robust Distributed Learning:
+ * Towards Optimal Statistical Rates", ICML 2018 (Definitions 1 and 2). The reference has no such
+ * aggregator, so there are no reference lines to cite; the semantics are fixed here.
+ * Not a fold: each coordinate needs order statistics across the K clients. One launch, every delta
+ * read once, no K x P temporary. Float32 deltas and output, 1 <= K <= 128, trim count 0 <= 2t < K.
+ * For every element p, with v_k = x_k[p]:
+ *     key(v) = bits(v) ^ (sign(v) ? 0xFFFFFFFF : 0x80000000), compared as uint32: the total order
+ *              -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN (NaNs by payload)
+ *     the clients are ranked by (key(v_k), k); those of rank t .. K-1-t are kept
+ *     s = the first kept v_k verbatim; s = fl(s + v_k) over the kept clients in CLIENT order (no FMA)
+ *     out[p] = fl(s * scale) with FJAGG_SCALE (the caller passes f32(1 / (K - 2t))), else s
+ * t = 0 is bit for bit fjagg_wsum_dense with unit weights; t = (K-1)/2 is the median (odd K: the
+ * middle value; even K: fl(fl(a + b) * 0.5f) with scale 0.5). A +NaN, +inf or huge value is trimmed
+ * from the top, a -NaN or -inf from the bottom. There are no weights.
+ * Flags: FJAGG_SCALE, FJAGG_NONTEMPORAL and, on the pytree entry, FJAGG_UNALIGNED (the flag the
+ * plan was made with). Refused on the host with nothing launched: a dtype other than FJAGG_F32,
+ * FJAGG_ACCUMULATE, FJAGG_NARROW, FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, FJAGG_UNBALANCED and a
+ * FJAGG_VARIANT byte (FJAGG_EUNSUPPORTED); K > 128 (FJAGG_EUNSUPPORTED); K < 1, t < 0 or 2t >= K,
+ * null pointers, P < 1, ld < P, a bad plan (nblk < 1, L < 1) (FJAGG_EINVAL); rows over 1 GiB
+ * (FJAGG_EUNSUPPORTED). Rows need float32's alignment only.
+ */
+/* Dense slab: client k's row at x_dev + k*ld elements, P elements each; out_dev is float[P]. */
+int fjagg_trim_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t t, float scale,
+                     void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image and blocks of fjagg_ptrs_plan_leaves as fjagg_wsum_ptrs takes them
+ * (in_ptrs[K*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk]; per-leaf element units included), one
+ * launch over all leaves. */
+int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t, float scale,
+                    int flags, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
