@@ -96,6 +96,10 @@ _SIGNATURES = {
                                               _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_trim_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i32, _vp]),
     "fjagg_trim_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
+    "fjagg_gram_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp]),
+    "fjagg_gram_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _i64, _i32, _vp]),
+    "fjagg_gram_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "fjagg_gram_chunk_columns": (_i64, [_i64, _i64]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

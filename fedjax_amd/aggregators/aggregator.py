@@ -14,7 +14,11 @@ Mirror of google/fedjax 0.0.17 ``fedjax/aggregators/aggregator.py``:
   (DP-FedAvg; no reference counterpart), :func:`fedjax_amd.tree_util.tree_dp_clipped_mean`;
 * :func:`trimmed_mean_aggregator` / :func:`median_aggregator` — the coordinate-wise trimmed mean
   and median of Yin et al. (ICML 2018; no reference counterpart),
-  :func:`fedjax_amd.tree_util.tree_trimmed_mean` / :func:`fedjax_amd.tree_util.tree_median`.
+  :func:`fedjax_amd.tree_util.tree_trimmed_mean` / :func:`fedjax_amd.tree_util.tree_median`;
+* :func:`krum_aggregator` / :func:`geometric_median_aggregator` — Krum / multi-Krum (Blanchard et
+  al., NeurIPS 2017) and the smoothed-Weiszfeld geometric median (Pillutla et al., IEEE TSP 2022;
+  no reference counterparts), :func:`fedjax_amd.tree_util.tree_krum` /
+  :func:`fedjax_amd.tree_util.tree_geometric_median`.
 """
 
 import dataclasses as std_dataclasses
@@ -213,5 +217,82 @@ def median_aggregator() -> Aggregator:
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
         return tree_util.tree_median(params), state
+
+    return Aggregator(init, apply)
+
+
+@dataclasses.dataclass
+class KrumAggregatorState:
+    """The last round's selection: ``selected`` — the client ids Krum chose, best first;
+    ``scores`` — every client's Krum score by client id (float; ``inf`` for a client whose
+    params held a non-finite value). Empty before the first round."""
+    selected: Tuple[ClientId, ...] = ()
+    scores: Dict[ClientId, float] = std_dataclasses.field(default_factory=dict)
+
+
+def krum_aggregator(num_byzantine: int, num_selected: int = 1) -> Aggregator:
+    """Builds the Krum (``num_selected = 1``) / multi-Krum aggregator of Blanchard et al.
+    (NeurIPS 2017): :func:`fedjax_amd.tree_util.tree_krum` of the round's params — the mean of
+    the ``num_selected`` clients closest to their ``K - num_byzantine - 2`` nearest neighbours.
+    A round needs ``K >= 2 * num_byzantine + 3`` clients.
+
+    ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
+    client must not be able to scale its own vote. It returns ``None`` for a round with no
+    clients or no selectable client. Float32 params, at most 1024 clients a round."""
+    if isinstance(num_byzantine, (bool, np.bool_)) or not isinstance(num_byzantine, (int, np.integer)):
+        raise TypeError("num_byzantine must be an int")
+    if isinstance(num_selected, (bool, np.bool_)) or not isinstance(num_selected, (int, np.integer)):
+        raise TypeError("num_selected must be an int")
+    if num_byzantine < 0 or num_selected < 1:
+        raise ValueError(f"need num_byzantine >= 0 and num_selected >= 1, got {num_byzantine} and {num_selected}")
+
+    def init():
+        return KrumAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        triples = list(clients_params_and_weights)  # the weights are not used
+        got = tree_util.tree_krum([param for _, param, _ in triples], num_byzantine, num_selected)
+        if got is None:
+            return None, KrumAggregatorState()
+        ids = [cid for cid, _, _ in triples]
+        return got.mean, KrumAggregatorState(tuple(ids[k] for k in got.selected),
+                                            {cid: float(s) for cid, s in zip(ids, got.scores)})
+
+    return Aggregator(init, apply)
+
+
+@dataclasses.dataclass
+class GeometricMedianAggregatorState:
+    """The last round's Weiszfeld weight per client id (float32 as the fold used it; 0 for a
+    client whose params held a non-finite value). Empty before the first round."""
+    weights: Dict[ClientId, float] = std_dataclasses.field(default_factory=dict)
+
+
+def geometric_median_aggregator(iterations: int = 4, nu: float = 1e-6) -> Aggregator:
+    """Builds the geometric-median aggregator ("RFA", Pillutla et al., IEEE TSP 2022):
+    :func:`fedjax_amd.tree_util.tree_geometric_median` of the round's params with unit client
+    weights, ``iterations`` smoothed Weiszfeld steps with smoothing ``nu``.
+
+    ``apply`` takes the usual triples and IGNORES the weights. It returns ``None`` for a round
+    with no clients or no usable client. Float32 params, at most 1024 clients a round."""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
+        raise TypeError("iterations must be an int")
+    if iterations < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations}")
+    if isinstance(nu, (bool, np.bool_)) or not isinstance(nu, (int, float, np.integer, np.floating)):
+        raise TypeError("nu must be a number")
+    if not (float(nu) > 0.0 and np.isfinite(float(nu))):
+        raise ValueError(f"nu must be finite and > 0, got {nu}")
+
+    def init():
+        return GeometricMedianAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        triples = list(clients_params_and_weights)  # the weights are not used
+        got = tree_util.tree_geometric_median([param for _, param, _ in triples], iterations=iterations, nu=nu)
+        if got is None:
+            return None, GeometricMedianAggregatorState()
+        return got.median, GeometricMedianAggregatorState(
+            {cid: float(w) for (cid, _, _), w in zip(triples, got.weights)})
 
     return Aggregator(init, apply)

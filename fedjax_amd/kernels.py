@@ -357,13 +357,20 @@ def check_noise_stddev(noise_stddev) -> float:
     return sd
 
 
-def refuse_capture(what: str) -> None:
+def refuse_capture(what: str, why: Optional[str] = None) -> None:
     """The differentially private calls bake the noise key into the kernel arguments: a graph
     replay would add the SAME noise every time, which voids the privacy guarantee without any
-    visible sign. They raise under stream capture, before anything is recorded."""
+    visible sign. They raise under stream capture, before anything is recorded. Other calls
+    that cannot be captured give their own reason as ``why``."""
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f"fedjax_amd: {what} is not capturable: its noise key is a kernel argument, so a "
-                           "graph replay would reuse the noise and void the privacy guarantee")
+        if why is None:
+            why = ("its noise key is a kernel argument, so a graph replay would reuse the noise and void the "
+                   "privacy guarantee")
+        raise RuntimeError(f"fedjax_amd: {what} is not capturable: {why}")
+
+
+_TWO_PASS = ("the selection between its two passes runs on the host over the Gram matrix, so a graph replay "
+             "would fold the clients chosen at capture time")
 
 
 class NoiseTable:
@@ -770,6 +777,102 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
     flags |= _lib.UNALIGNED if unaligned else 0
     _lib.call("fjagg_trim_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
+
+
+GRAM_MAX_CLIENTS = 1024  # fjagg_gram_*: G is K x K float64, at most 8 MiB (fjagg.h)
+GRAM_CHAIN = 256  # FJAGG_GRAM_CHAIN: columns per float32 fmaf chain, between float64 additions
+_GRAM_WS = {}  # device index -> workspace of the Gram pass (partial sums per workgroup chunk)
+
+
+def _gram_workspace(dev: torch.device, need: int) -> torch.Tensor:
+    """The Gram pass's workspace of ``dev``'s current stream, cached like :func:`_l2_workspace`:
+    launches on one stream are ordered, so they share it. Never zeroed; nothing is carried
+    from one call to the next."""
+    key = (dev.index, _stream_handle(dev))
+    ws = _GRAM_WS.get(key)
+    if ws is None and len(_GRAM_WS) >= 16:
+        _GRAM_WS.clear()
+    if ws is None or ws.numel() < need:
+        ws = _GRAM_WS[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _check_gram_clients(K: int) -> int:
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"the Gram matrix needs at least 1 client, got K = {K}")
+    if K > GRAM_MAX_CLIENTS:
+        raise ValueError(f"the Gram matrix supports K <= {GRAM_MAX_CLIENTS} clients, got K = {K}")
+    return K
+
+
+def _check_gram_out(out: Optional[torch.Tensor], K: int, dev: torch.device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(K, K, dtype=torch.float64, device=dev)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != (K, K) or out.dtype != torch.float64 \
+            or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{K}, {K}] tensor")
+    return out
+
+
+def gram_chunk_columns(K: int, P: int) -> int:
+    """Columns one workgroup of :func:`gram_dense` covers for a ``[K, P]`` slab: a multiple of
+    ``GRAM_CHAIN`` and a function of ``(K, P)`` alone (``fjagg_gram_chunk_columns``)."""
+    K = _check_gram_clients(K)
+    if int(P) < 1:
+        raise ValueError("P must be >= 1")
+    return int(_lib.load().fjagg_gram_chunk_columns(K, int(P)))
+
+
+def gram_dense(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gram matrix ``G[i][j] = sum_p x[i, p] * x[j, p]`` of a float32 slab ``x[K, P]`` (row
+    stride ``x.stride(0)``, unit column stride, float32 alignment only) as a float64 ``[K, K]``
+    device tensor: ``fjagg_gram_dense``, one pass over the slab on the f32 matrix instruction
+    plus a small combine launch, no host synchronisation. Chains of ``GRAM_CHAIN`` columns
+    accumulate in float32 (an fmaf chain), chains add up in float64 in a fixed order: bitwise
+    reproducible, bitwise symmetric, a non-finite client confined to its row and column
+    (fjagg.h). ``K <= 1024``; everything is checked before the library is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the Gram matrix takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    K = _check_gram_clients(K)
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the Gram matrix takes rows of up to 1 GiB")
+    dev = _require_device(x)
+    out = _check_gram_out(out, K, dev)
+    _require_device(x, out)
+    need = int(_lib.load().fjagg_gram_workspace_bytes(K, P, 0))
+    ws = _gram_workspace(dev, need)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_gram_dense", _lib.F32, x.data_ptr(), ld, K, P, out.data_ptr(), ws.data_ptr(), ws.numel(), 0,
+              _stream_handle(dev))
+    return out
+
+
+def gram_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, out: Optional[torch.Tensor] = None, *,
+              unaligned: bool = False) -> torch.Tensor:
+    """:func:`gram_dense`'s arithmetic over a device plan image (``in_ptrs[K*L] | out_ptrs[L] |
+    leaf_n[L] | blocks[2*nblk]``, the blocks of :func:`ptrs_plan` for float32 leaves;
+    ``out_ptrs`` is not read): ``fjagg_gram_ptrs``, G summed over all leaves, a chain never
+    crossing a leaf. ``unaligned`` as the plan was made. Checked before the library is touched."""
+    K = _check_gram_clients(K)
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    dev = _require_device(image_dev)
+    out = _check_gram_out(out, K, dev)
+    _require_device(image_dev, out)
+    need = int(_lib.load().fjagg_gram_workspace_bytes(K, 0, nblk))
+    ws = _gram_workspace(dev, need)
+    _lib.call("fjagg_gram_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, out.data_ptr(), ws.data_ptr(),
+              ws.numel(), _lib.UNALIGNED if unaligned else 0, _stream_handle(dev))
+    return out
 
 
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:

@@ -1,0 +1,151 @@
+"""Host-side selection for the two whole-vector Byzantine-robust aggregates, on the K x K Gram
+matrix ``G[i][j] = <x_i, x_j>`` of the client deltas (numpy float64; no GPU, no torch).
+
+* Krum / multi-Krum — Blanchard, El Mhamdi, Guerraoui and Stainer, "Machine Learning with
+  Adversaries: Byzantine Tolerant Gradient Descent", NeurIPS 2017: the client(s) whose delta is
+  closest to its ``K - f - 2`` nearest neighbours. Needs ``d2(i, j) = G_ii + G_jj - 2 G_ij``.
+* The geometric median by the smoothed Weiszfeld algorithm ("RFA") — Pillutla, Kakade and
+  Harchaoui, "Robust Aggregation for Federated Learning", IEEE Trans. Signal Processing 2022.
+  Every iterate is ``v = sum_j a_j x_j``, so ``|v - x_k|^2 = a'Ga - 2 (Ga)_k + G_kk``: all
+  iterations run on K x K numbers and only the final weights ``a`` go back to the device.
+
+The Gram matrix comes from :func:`fedjax_amd.kernels.gram_dense` / ``gram_ptrs`` (one pass over
+the deltas); the result is one grouped fold over the chosen or re-weighted clients. A client
+with a non-finite value anywhere in its delta has a non-finite ``G[k][k]``: it is *unusable*,
+never selected, and gets weight 0 — the callers give it group id -1, so the fold never loads it.
+"""
+
+from __future__ import annotations
+
+from typing import Tuple
+
+import numpy as np
+
+__all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "weiszfeld_weights"]
+
+
+def _gram(G) -> np.ndarray:
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+        raise ValueError(f"G must be a square [K, K] matrix with K >= 1, got shape {G.shape}")
+    return G
+
+
+def _int(name: str, v) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an int, not {type(v).__name__}")
+    return int(v)
+
+
+def usable(G) -> np.ndarray:
+    """bool[K]: client k is usable iff ``G[k][k]`` is finite (its delta holds no NaN or inf, and
+    its squared norm did not overflow)."""
+    return np.isfinite(np.diagonal(_gram(G)))
+
+
+def sq_distances(G) -> np.ndarray:
+    """float64[K, K] squared distances ``max(G_ii + G_jj - 2 G_ij, 0)``, 0 on the diagonal, and
+    ``+inf`` wherever either client is unusable or the value is not finite."""
+    G = _gram(G)
+    ok = usable(G)
+    d = np.diagonal(G)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d2 = (d[:, None] + d[None, :]) - 2.0 * G
+        d2 = np.where(np.isfinite(d2), np.maximum(d2, 0.0), np.inf)
+    d2[~ok, :] = np.inf
+    d2[:, ~ok] = np.inf
+    np.fill_diagonal(d2, 0.0)
+    return d2
+
+
+def _check_krum(K: int, f) -> int:
+    f = _int("num_byzantine", f)
+    if f < 0:
+        raise ValueError(f"num_byzantine must be >= 0, got {f}")
+    if K < 2 * f + 3:
+        raise ValueError(f"Krum needs K >= 2f + 3 clients: K = {K}, f = {f}")
+    return f
+
+
+def krum_scores(G, f) -> np.ndarray:
+    """float64[K] Krum scores: ``score_i`` is the sum of the ``K - f - 2`` smallest ``d2(i, j)``,
+    ``j != i``, added in ascending order; ``+inf`` for an unusable client (and for one with too
+    few usable neighbours). Needs ``K >= 2f + 3`` and an int ``f >= 0`` (a bool is refused)."""
+    G = _gram(G)
+    K = G.shape[0]
+    f = _check_krum(K, f)
+    d2 = sq_distances(G)
+    ok = usable(G)
+    others = d2[~np.eye(K, dtype=bool)].reshape(K, K - 1)  # row i without d2(i, i)
+    nearest = np.sort(others, axis=1)[:, : K - f - 2]
+    scores = np.zeros(K, dtype=np.float64)
+    for c in range(nearest.shape[1]):  # ascending, one addition per neighbour
+        scores = scores + nearest[:, c]
+    scores[~ok] = np.inf
+    return scores
+
+
+def krum_select(G, f, m=1) -> np.ndarray:
+    """int64 indices of the ``m`` clients of smallest finite Krum score, best first, ties to the
+    lower index (``m = 1``: Krum; ``m > 1``: multi-Krum). ``1 <= m <= K - f``. With fewer than
+    ``m`` finite scores, those there are; with none, an empty selection."""
+    G = _gram(G)
+    K = G.shape[0]
+    f = _check_krum(K, f)
+    m = _int("num_selected", m)
+    if not (1 <= m <= K - f):
+        raise ValueError(f"num_selected must be in [1, K - f] = [1, {K - f}], got {m}")
+    scores = krum_scores(G, f)
+    order = np.argsort(scores, kind="stable")
+    order = order[np.isfinite(scores[order])]
+    return order[:m].astype(np.int64)
+
+
+def weiszfeld_weights(G, alpha=None, nu: float = 1e-6, iterations: int = 4) -> Tuple[np.ndarray, np.ndarray]:
+    """The smoothed Weiszfeld iteration on the usable sub-matrix of ``G``. ``alpha``: positive
+    finite client weights (default: all 1). With ``a = alpha / sum(alpha)``, ``iterations`` times
+
+        d_k = sqrt(max(a'Ga - 2 (Ga)_k + G_kk, 0));  beta_k = alpha_k / max(nu, d_k);  a = beta / sum(beta)
+
+    Returns ``(a, d)``, both float64[K]: the final weights, summing to 1 over the usable clients
+    and 0 for the others, and the last distances (``d`` is zeros with ``iterations = 0`` and
+    ``inf`` for unusable clients). No usable client: all-zero weights."""
+    G = _gram(G)
+    K = G.shape[0]
+    iterations = _int("iterations", iterations)
+    if iterations < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations}")
+    if isinstance(nu, (bool, np.bool_)) or not isinstance(nu, (int, float, np.integer, np.floating)):
+        raise TypeError("nu must be a number")
+    nu = float(nu)
+    if not (nu > 0.0 and np.isfinite(nu)):
+        raise ValueError(f"nu must be finite and > 0, got {nu}")
+    if alpha is None:
+        alpha = np.ones(K, dtype=np.float64)
+    alpha = np.asarray(alpha)
+    if alpha.dtype == np.bool_:
+        raise TypeError("weights must be numbers, not bools")
+    alpha = alpha.astype(np.float64)
+    if alpha.shape != (K,):
+        raise ValueError(f"need {K} weights, got shape {alpha.shape}")
+    if not (np.isfinite(alpha).all() and (alpha > 0.0).all()):
+        raise ValueError("weights must be finite and > 0")
+    ok = usable(G)
+    a_full = np.zeros(K, dtype=np.float64)
+    d_full = np.where(ok, 0.0, np.inf)
+    if not ok.any():
+        return a_full, d_full
+    idx = np.flatnonzero(ok)
+    Gu = G[np.ix_(idx, idx)]
+    al = alpha[idx]
+    diag = np.diagonal(Gu)
+    a = al / al.sum()
+    d = np.zeros(len(idx), dtype=np.float64)
+    for _ in range(iterations):
+        Ga = Gu @ a
+        d = np.sqrt(np.maximum(a @ Ga - 2.0 * Ga + diag, 0.0))
+        beta = al / np.maximum(nu, d)
+        a = beta / beta.sum()
+    a_full[idx] = a
+    d_full[idx] = d
+    return a_full, d_full

@@ -327,6 +327,66 @@ class ClientDeltaSlab:
         kernels.trim_count(0, self.num_clients)
         return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
 
+    def gram(self, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Gram matrix ``G[i][j] = <row i, row j>`` of the K deltas as a float64 ``[K, K]`` device
+        tensor: one pass over the slab on the f32 matrix instruction
+        (:func:`kernels.gram_dense`), no host synchronisation, nothing uploaded. What Krum and
+        the geometric median are functions of (:mod:`fedjax_amd.robust`). Bitwise reproducible
+        and symmetric; a client holding a NaN or inf makes only its own row and column
+        non-finite. A float32 slab of up to 1024 clients."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"gram needs a float32 slab, not {self.dtype}")
+        K = kernels._check_gram_clients(self.num_clients)
+        if self.num_params == 0:  # a template of empty leaves: every inner product is the empty sum
+            if out is None:
+                return torch.zeros(K, K, dtype=torch.float64, device=self.device)
+            return kernels._check_gram_out(out, K, self.device).zero_()
+        return kernels.gram_dense(self.rows, out=out)
+
+    def krum(self, num_byzantine, num_selected=1) -> "tree_util.KrumResult":
+        """Krum (``num_selected = 1``) and multi-Krum (Blanchard et al., NeurIPS 2017) over the
+        rows: client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
+        other clients, ``f = num_byzantine``, and the ``num_selected`` clients of smallest
+        score are averaged (ties to the lower index). ``K >= 2f + 3``, ``1 <= num_selected <= K - f``.
+
+        :meth:`gram`, ONE device-to-host copy of the K x K float64 Gram, the selection on the
+        host, then ``grouped_mean([1] * K, ids, 1)[0]`` with id 0 for the selected clients and
+        -1 for the rest — which are never loaded, so up to ``f`` clients full of NaN, inf or
+        1e30 cannot reach the result. ``num_selected = 1`` gives the chosen client's delta
+        (times f32(1), from a +0 start). There are no client weights. Returns a
+        :class:`~fedjax_amd.tree_util.KrumResult`; ``mean`` is ``None`` when no client has a
+        finite score. A float32 slab of up to 1024 clients. Raises under stream capture."""
+        kernels.refuse_capture("krum", kernels._TWO_PASS)
+        if self.dtype != torch.float32:
+            raise TypeError(f"krum needs a float32 slab, not {self.dtype}")
+        tree_util._check_krum_args(self.num_clients, num_byzantine, num_selected)
+        gram = self.gram()
+        selected, scores, w, ids = tree_util._krum_plan(gram.cpu().numpy(), num_byzantine, num_selected)
+        mean = self.grouped_mean(w, ids, 1)[0] if len(selected) else None
+        return tree_util.KrumResult(mean, selected, scores, gram)
+
+    def geometric_median(self, weights: Optional[Sequence] = None, *, iterations=4,
+                         nu=1e-6) -> "tree_util.GeometricMedianResult":
+        """The geometric median of the rows by the smoothed Weiszfeld algorithm ("RFA", Pillutla
+        et al., IEEE TSP 2022), ``weights`` the clients' positive weights alpha (default all 1).
+        All ``iterations`` run on the host over the Gram matrix
+        (:func:`fedjax_amd.robust.weiszfeld_weights`), so the slab is read twice whatever
+        ``iterations`` is: :meth:`gram`, ONE device-to-host copy, then
+        ``grouped_mean(float32(a), ids, 1)[0]`` with id -1 (never loaded, weight 0) for a client
+        with a non-finite value. ``iterations = 0`` is the alpha-weighted mean of the usable
+        clients. Returns a :class:`~fedjax_amd.tree_util.GeometricMedianResult`; ``median`` is
+        ``None`` when no client is usable. A float32 slab of up to 1024 clients. Raises under
+        stream capture."""
+        kernels.refuse_capture("geometric_median", kernels._TWO_PASS)
+        if self.dtype != torch.float32:
+            raise TypeError(f"geometric_median needs a float32 slab, not {self.dtype}")
+        weights = None if weights is None else list(weights)
+        tree_util._check_median_args(self.num_clients, weights, iterations, nu)
+        gram = self.gram()
+        a32, d, ids = tree_util._median_plan(gram.cpu().numpy(), weights, iterations, nu)
+        median = self.grouped_mean(a32, ids, 1)[0] if (ids >= 0).any() else None
+        return tree_util.GeometricMedianResult(median, a32, d, gram)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

@@ -46,6 +46,7 @@ __all__ = [
     "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
     "tree_dp_clipped_mean",
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
+    "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -2028,3 +2029,152 @@ def tree_median(pytrees: Iterable[PyTree]) -> Optional[PyTree]:
         return None
     kernels.trim_count(0, len(trees))
     return tree_trimmed_mean(trees, (len(trees) - 1) // 2)
+
+
+class KrumResult(NamedTuple):
+    """Result of Krum / multi-Krum (:func:`tree_krum`, :meth:`fedjax_amd.slab.ClientDeltaSlab.krum`):
+    ``mean`` — the plain mean of the selected clients' deltas (``None`` when none could be
+    selected); ``selected`` — their indices, best first (int64 numpy); ``scores`` — every
+    client's Krum score (float64 numpy, ``inf`` for an unusable client); ``gram`` — the float64
+    ``[K, K]`` Gram matrix on the device."""
+    mean: Any
+    selected: Any
+    scores: Any
+    gram: Any
+
+
+class GeometricMedianResult(NamedTuple):
+    """Result of the smoothed-Weiszfeld geometric median (:func:`tree_geometric_median`,
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.geometric_median`): ``median`` — ``sum_k a_k x_k``
+    (``None`` when no client is usable); ``weights`` — the float32 ``a_k`` the fold used (numpy,
+    0 for an unusable client); ``distances`` — the last iteration's ``|v - x_k|`` (float64
+    numpy); ``gram`` — the float64 ``[K, K]`` Gram matrix on the device."""
+    median: Any
+    weights: Any
+    distances: Any
+    gram: Any
+
+
+def _krum_plan(G: np.ndarray, num_byzantine, num_selected):
+    """(selected, scores, fold weights, fold ids) of a Krum round over the host Gram ``G``."""
+    from fedjax_amd import robust
+
+    scores = robust.krum_scores(G, num_byzantine)
+    selected = robust.krum_select(G, num_byzantine, num_selected)
+    ids = np.full(G.shape[0], -1, dtype=np.int64)
+    ids[selected] = 0
+    return selected, scores, [1] * G.shape[0], ids
+
+
+def _median_plan(G: np.ndarray, weights, iterations, nu):
+    """(float32 weights, distances, fold ids) of a geometric-median round over the host Gram."""
+    from fedjax_amd import robust
+
+    alpha = None if weights is None else np.array([_host_weight(w) for w in weights], dtype=np.float64)
+    a, d = robust.weiszfeld_weights(G, alpha, nu, iterations)
+    a32 = a.astype(np.float32)
+    ids = np.where(robust.usable(G) & (a32 > 0), 0, -1).astype(np.int64)
+    return a32, d, ids
+
+
+def _check_krum_args(K: int, num_byzantine, num_selected) -> None:
+    """Krum's argument checks on K alone, before any pass over the deltas."""
+    from fedjax_amd import robust
+
+    kernels._check_gram_clients(K)
+    robust.krum_select(np.eye(K), num_byzantine, num_selected)
+
+
+def _check_median_args(K: int, weights, iterations, nu) -> None:
+    from fedjax_amd import robust
+
+    kernels._check_gram_clients(K)
+    if weights is not None and len(weights) != K:
+        raise ValueError(f"need {K} weights, got {len(weights)}")
+    alpha = None if weights is None else np.array([_host_weight(w) for w in weights], dtype=np.float64)
+    robust.weiszfeld_weights(np.eye(1) if alpha is None else np.eye(K), alpha, nu, 0)
+
+
+def tree_gram(pytrees: Iterable[PyTree]) -> Optional[torch.Tensor]:
+    """Gram matrix ``G[i][j] = <x_i, x_j>`` of K client pytrees (the inner product over every
+    element of every leaf) as a float64 ``[K, K]`` device tensor, in ONE pass over the deltas on
+    the f32 matrix instruction: no K x P temporary, no host synchronisation. The structure walk,
+    the checks and the plan image are :func:`tree_trimmed_mean`'s; float32's alignment is all a
+    leaf needs. Chains of ``kernels.GRAM_CHAIN`` columns accumulate in float32, chains in
+    float64; a chain never crosses a leaf, so the bits differ from
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.gram` of the same deltas (whose chains run through
+    the whole row) within the bound of fjagg.h. Float32 leaves, ``K <= 1024``. The inputs are
+    never written; a one-shot iterable is consumed once; no clients: ``None``. Raises under
+    stream capture (the plan image goes through a pinned staging buffer)."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    return _tree_gram(trees)[0]
+
+
+def _tree_gram(trees: list):
+    K = kernels._check_gram_clients(len(trees))
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"the Gram matrix needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    device = rows[0][0].device if rows[0] else _default_device()
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    if not leaf_n.any():  # no elements: every inner product is the empty sum
+        return torch.zeros(K, K, dtype=torch.float64, device=device), td, rows
+    L = len(leaf_n)
+    in_ptrs = _ptr_table(rows)
+    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, device)
+    image = np.concatenate([in_ptrs.ravel(), np.zeros(L, np.int64), leaf_n, blocks])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    return kernels.gram_ptrs(image_dev, L, K, len(blocks) // 2), td, rows
+
+
+def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1) -> Optional[KrumResult]:
+    """Krum (``num_selected = 1``) and multi-Krum over client pytrees (Blanchard et al., NeurIPS
+    2017): client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
+    other clients, ``f = num_byzantine``; the ``num_selected`` clients of smallest score are
+    averaged (ties to the lower index). Needs ``K >= 2f + 3``, ``1 <= num_selected <= K - f``.
+
+    Two passes over the deltas: :func:`tree_gram`, ONE device-to-host copy of the K x K float64
+    Gram, the selection on the host (:mod:`fedjax_amd.robust`), then
+    :func:`tree_grouped_mean` with weight 1 and group 0 for the selected clients and group -1
+    for all others — which are never loaded, so a client full of NaN, inf or 1e30 touches
+    nothing. Such a client has a non-finite or huge norm and is not selected. There are no
+    client weights: a client must not scale its own vote. Float32 leaves, ``K <= 1024``.
+    Returns a :class:`KrumResult`; no clients: ``None``. Raises under stream capture."""
+    kernels.refuse_capture("tree_krum", kernels._TWO_PASS)
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    _check_krum_args(len(trees), num_byzantine, num_selected)
+    gram = _tree_gram(trees)[0]
+    selected, scores, w, ids = _krum_plan(gram.cpu().numpy(), num_byzantine, num_selected)
+    mean = tree_grouped_mean(list(zip(trees, w)), ids, 1)[0] if len(selected) else None
+    return KrumResult(mean, selected, scores, gram)
+
+
+def tree_geometric_median(pytrees: Iterable[PyTree], weights=None, *, iterations=4,
+                          nu=1e-6) -> Optional[GeometricMedianResult]:
+    """The geometric median of client pytrees by the smoothed Weiszfeld algorithm ("RFA",
+    Pillutla et al., IEEE TSP 2022): from ``a = alpha / sum(alpha)`` (``weights``, default all 1),
+    ``iterations`` times ``beta_k = alpha_k / max(nu, |v - x_k|)``, ``a = beta / sum(beta)`` with
+    ``v = sum_k a_k x_k``. Every distance is a function of the Gram matrix, so the deltas are
+    read twice whatever ``iterations`` is: :func:`tree_gram`, ONE device-to-host copy, the
+    iteration on the host in float64 (:func:`fedjax_amd.robust.weiszfeld_weights`), then
+    :func:`tree_grouped_mean` with weights ``float32(a_k)`` — the result is
+    ``fl(sum_k x_k f32(a_k)) * f32(1 / sum_k f32(a_k))``, the fold's own normalisation. A client
+    with a non-finite value is unusable: weight 0, group -1, never loaded. ``iterations = 0`` is
+    the weighted mean of the usable clients. Float32 leaves, ``K <= 1024``. Returns a
+    :class:`GeometricMedianResult`; no clients: ``None``. Raises under stream capture."""
+    kernels.refuse_capture("tree_geometric_median", kernels._TWO_PASS)
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    weights = None if weights is None else list(weights)
+    _check_median_args(len(trees), weights, iterations, nu)
+    gram = _tree_gram(trees)[0]
+    a32, d, ids = _median_plan(gram.cpu().numpy(), weights, iterations, nu)
+    median = tree_grouped_mean(list(zip(trees, a32)), ids, 1)[0] if (ids >= 0).any() else None
+    return GeometricMedianResult(median, a32, d, gram)

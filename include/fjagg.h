@@ -20,6 +20,7 @@
  *     clipped round algorithms/mime_lite.py:131-149,162-167 fjagg_server_update_clip_* (clipped mean + step)
  *     (no reference row) DP-FedAvg's Gaussian mechanism      fjagg_wsum_clip_noise_* (clipped mean + noise)
  *     (no reference row) trimmed mean / median (Yin et al. 2018) fjagg_trim_* (order statistics per coordinate)
+ *     (no reference row) Krum / geometric median (Gram matrix)  fjagg_gram_* (K x K inner products, float64)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -574,6 +575,50 @@ int fjagg_trim_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int
  * launch over all leaves. */
 int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t, float scale,
                     int flags, void* stream);
+
+/*
+ * The K x K Gram matrix of the client deltas, G[i][j] = sum_p x_i[p] * x_j[p], in float64: the one
+ * pass over the deltas that the two whole-vector Byzantine-robust aggregates need. Krum and
+ * multi-Krum (Blanchard, El Mhamdi, Guerraoui and Stainer, "Machine Learning with Adversaries:
+ * Byzantine Tolerant Gradient Descent", NeurIPS 2017) score client i by its squared distances
+ * d2(i,j) = G_ii + G_jj - 2 G_ij; every iterate of the smoothed Weiszfeld algorithm for the
+ * geometric median (Pillutla, Kakade and Harchaoui, "Robust Aggregation for Federated Learning",
+ * IEEE Trans. Signal Processing 2022) is v = sum_j a_j x_j, so |v - x_k|^2 = a'Ga - 2 (Ga)_k + G_kk.
+ * The reference has neither aggregator, so there are no reference lines to cite; the semantics
+ * are fixed here. The selection itself runs on the host over G
+ * (fedjax_amd/robust.py); the final mean is a grouped fold that never loads an excluded client.
+ * Float32 deltas, 1 <= K <= 1024, one GPU. Arithmetic:
+ *     the columns of a row are cut into chains of at most FJAGG_GRAM_CHAIN consecutive columns
+ *       (dense: from column 0, and a workgroup's chunk, fjagg_gram_chunk_columns, is whole chains;
+ *       pytree: from the start of every plan entry, so a chain never crosses a leaf)
+ *     within a chain  c = +0; c = fmaf(x_i[p], x_j[p], c) in column order   (v_mfma_f32_32x32x2_f32)
+ *     chain results are added in float64: a workgroup adds its chains in column order, then the
+ *       workgroups' sums are added in chunk order by a second small kernel over the workspace
+ * No floating-point atomics; the order is a function of (K, P) (dense) or of the plan (pytree),
+ * so the result is run-to-run bitwise reproducible, and G[i][j] and G[j][i] are the same bits.
+ * |G_ij - exact| <= gamma_C * sum_p |x_i[p] x_j[p]|, gamma_C = C u / (1 - C u), u = 2^-24,
+ * C = FJAGG_GRAM_CHAIN (the float64 additions add under 1 % of that). A non-finite value in client
+ * k's delta makes row k and column k of G non-finite and changes no other entry's bits. Rows past K
+ * and columns past P are zeros made on chip, never loaded. Loads are 4 bytes wide: rows and leaves
+ * need float32's alignment only. The workspace needs no zeroing and carries nothing between calls.
+ * Flags: FJAGG_UNALIGNED on the pytree entry (the flag the plan was made with). Refused on the host
+ * with nothing launched: a dtype other than FJAGG_F32, FJAGG_ACCUMULATE, FJAGG_NARROW,
+ * FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, FJAGG_UNBALANCED, any other flag or a FJAGG_VARIANT byte, K > 1024,
+ * rows over 1 GiB (FJAGG_EUNSUPPORTED); K < 1, P < 1, ld < P, a bad plan, null pointers, a workspace
+ * under fjagg_gram_workspace_bytes (FJAGG_EINVAL).
+ */
+#define FJAGG_GRAM_CHAIN 256
+/* Dense slab: client k's row at x_dev + k*ld elements; gram_dev is double[K][K], row-major. */
+int fjagg_gram_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, double* gram_dev, void* ws_dev,
+                     int64_t ws_bytes, int flags, void* stream);
+/* Pytree path: the plan image of fjagg_ptrs_plan_leaves as fjagg_trim_ptrs takes it (in_ptrs[K*L] |
+ * out_ptrs[L] | leaf_n[L] | blocks[2*nblk]); out_ptrs is not read. G sums over all leaves. */
+int fjagg_gram_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, double* gram_dev,
+                    void* ws_dev, int64_t ws_bytes, int flags, void* stream);
+/* Workspace bytes: nblk = 0 for the dense entry over P columns, else for a plan of nblk entries. */
+int64_t fjagg_gram_workspace_bytes(int64_t K, int64_t P_or_total, int64_t nblk);
+/* Columns per workgroup of the dense entry (a multiple of FJAGG_GRAM_CHAIN, a function of K and P alone). */
+int64_t fjagg_gram_chunk_columns(int64_t K, int64_t P);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
