@@ -1,7 +1,10 @@
 """Host side of the Gram-matrix aggregates (Krum / multi-Krum, the smoothed-Weiszfeld geometric
 median): fedjax_amd.robust on an exact float64 Gram against restatements that work on the
 vectors and use no Gram (tests/robust_select_ref.py); unusable clients; argument validation; the
-library's host-side refusals; the public surface. No GPU needed."""
+library's host-side refusals; the public surface. And the restatements the GPU limit and fuzz tests
+rely on, shown not to be vacuous: the numpy chain is an fmaf chain on integers, the mid-size integer
+data tells chain lengths and arithmetics apart, the Krum seeds separate the scores by more than
+twice the derived bound, the sweep's case list holds the plan shapes it claims. No GPU needed."""
 import numpy as np
 import pytest
 import torch
@@ -306,3 +309,222 @@ def test_aggregator_arguments_and_empty_rounds():
         tree_util.tree_geometric_median(trees, [1.0, 2.0])
     with pytest.raises(ValueError):
         tree_util.tree_geometric_median(trees, nu=-1.0)
+
+
+# ------------------------------------------------------------------ the Gram arithmetic, restated bit for bit
+def _rne24(n):
+    """An integer rounded to 24 significant bits, ties to even: what float32 does to it."""
+    a = abs(n)
+    if a < 1 << 24:
+        return n
+    sh = a.bit_length() - 24
+    q, r = a >> sh, a & ((1 << sh) - 1)
+    half = 1 << (sh - 1)
+    q += r > half or (r == half and q & 1)
+    return (q << sh) * (1 if n > 0 else -1)
+
+
+@pytest.mark.parametrize("data", ["midsize", "wide"])
+def test_chain_gram_is_an_fmaf_chain_on_integers(data):
+    """On integer data chain_gram is fmaf bit for bit: checked against exact integer arithmetic
+    with one explicit round-to-nearest-even to 24 bits per step."""
+    K, P, C = 3, 700, 256
+    rng = np.random.default_rng(7)
+    x = ref.midsize_ints(rng, K, P) if data == "midsize" else ref.wide_ints(rng, K, P)
+    xi = x.astype(np.int64).tolist()
+    want = np.zeros((K, K))
+    for i in range(K):
+        for j in range(K):
+            total = 0
+            for c0 in range(0, P, C):
+                acc = 0
+                for p in range(c0, min(P, c0 + C)):
+                    acc = _rne24(acc + xi[i][p] * xi[j][p])
+                total += acc
+            assert abs(total) < 1 << 53
+            want[i, j] = float(total)
+    assert ref.chain_gram(x, C).tolist() == want.tolist()
+
+
+def _departs(P, chain, C=256):
+    """Columns at which a chain of `chain` columns has an accumulator other than the C-chain's."""
+    return max(0, P - min(chain, C))
+
+
+@pytest.mark.parametrize("K", ref.BITWISE_KS)
+def test_midsize_integers_tell_the_arithmetics_apart(K):
+    """Non-vacuity of the bitwise GPU test: at every (K, P) it uses, the 256-chain fmaf result on the
+    mid-size integer data differs from the exact Gram, from chains of 128, 512 and 1024 columns and
+    from the pairwise order in at least half of the entries — wherever the two arithmetics differ
+    on 127 columns or more. They cannot differ at all at P = 1 (one exact product) nor, for the
+    longer chains, at P <= 256 (the same chain), and at P = 257 the longer chains differ in one
+    column's addition only: there some entry differs. A kernel without the fold at a range's end
+    differs wherever P is no multiple of 256, P = 1 included."""
+    C = kernels.GRAM_CHAIN
+    assert C == ref.GRAM_CHAIN
+    for P in ref.bitwise_columns(kernels.gram_chunk_columns(K, 2 * C + 3)):
+        x = ref.midsize_case(K, P)
+        assert np.abs(x).max() <= ref.MIDSIZE and (x == np.rint(x)).all()
+        x64 = x.astype(np.float64)
+        g = ref.chain_gram(x, C)
+        others = {"exact": (x64 @ x64.T, P - 1), "pairwise": (ref.chain_gram(x, C, "pairwise"), P - 1)}
+        for chain in (128, 512, 1024):
+            others[chain] = (ref.chain_gram(x, chain), _departs(P, chain))
+        for name, (other, cols) in others.items():
+            frac = float(np.mean(other != g))
+            print(f"K={K} P={P} vs {name}: {frac:.2f} of the entries differ ({cols} columns apart)")
+            if cols >= 127:
+                assert frac >= 0.5, (K, P, name)
+            elif cols >= 1:
+                assert frac > 0, (K, P, name)
+            else:
+                assert frac == 0
+        dropped = ref.chain_gram(x, C, drop_partial=True)
+        assert (dropped != g).mean() >= (0.5 if P % C else 0) and ((dropped == g).all() or P % C)
+        assert (ref.chain_gram(x, C, "unfused") == g).all()  # products below 2^24: not told apart here
+
+
+def test_wide_integers_tell_fused_from_unfused():
+    x = ref.wide_ints(np.random.default_rng(11), 5, 700)
+    g = ref.chain_gram(x, 256)
+    assert np.mean(ref.chain_gram(x, 256, "unfused") != g) >= 0.5
+    assert np.mean(g != x.astype(np.float64) @ x.astype(np.float64).T) >= 0.5
+
+
+@pytest.mark.parametrize("chain", [128, 256, 512])
+def test_absorption_probe_shows_where_the_chain_folds(chain):
+    starts = [0, 1, 200, 255, 256, 257]
+    x = ref.absorption_rows(starts, 600)
+    diag = np.diagonal(ref.chain_gram(x, chain))
+    for c, g in zip(starts, diag):
+        fold = (c // chain + 1) * chain  # the first fold after the 2^12
+        absorbed = min(300, fold - c - 1)  # ones added to 2^24 in float32: each rounds away
+        assert g == 2.0 ** 24 + 300 - absorbed, (chain, c)
+    assert len({tuple(np.diagonal(ref.chain_gram(x, c)).tolist()) for c in (128, 256, 512)}) == 3
+    # the two k-steps of an instruction added first: 2^24 + (1 + 1) is exact, nothing is absorbed
+    # from the first whole pair on: the pairwise order shows wherever the column order absorbs
+    fused, paired = np.diagonal(ref.chain_gram(x, 256)), np.diagonal(ref.chain_gram(x, 256, "pairwise"))
+    assert ((paired != fused) == (fused < 2.0 ** 24 + 300)).all() and (paired >= 2.0 ** 24 + 299).all()
+
+
+def test_plan_ranges_cover_every_leaf_once():
+    leaf_n = [1027, 0, 1, 255, 700, 3]
+    P = sum(leaf_n)
+    x = np.random.RandomState(3).randint(-7, 8, size=(4, P)).astype(np.float32)
+    want = x.astype(np.float64) @ x.astype(np.float64).T
+    mask = np.array([0, 0, 1, 1, 0, 1], dtype=bool)
+    for unaligned, unit in ((False, 4), (mask, 4), (True, 1)):
+        blocks = kernels.ptrs_plan(_lib.F32, leaf_n, unaligned)
+        ranges = ref.plan_ranges(blocks, leaf_n, unit)
+        assert len(ranges) == len(blocks) // 2
+        seen = np.zeros(P, dtype=np.int64)
+        for e0, e1 in ranges:
+            assert 0 <= e0 <= e1 <= P
+            seen[e0:e1] += 1
+        assert (seen == 1).all()
+        if unaligned is mask:  # an element-unit leaf is cut into ranges of 64 elements, not 256
+            assert (700 + 1027 + 1 + 255, 700 + 1027 + 1 + 255 + 3) in ranges and (1028, 1028 + 64) in ranges
+        assert (ref.gram_of_ranges(x, ranges, 256) == want).all()
+    # chains restart at every range: on mid-size integers the ranges show in the bits
+    y = ref.midsize_ints(np.random.default_rng(5), 4, P)
+    a = ref.gram_of_ranges(y, ref.plan_ranges(kernels.ptrs_plan(_lib.F32, leaf_n, False), leaf_n, 4), 256)
+    b = ref.gram_of_ranges(y, ref.plan_ranges(kernels.ptrs_plan(_lib.F32, leaf_n, mask), leaf_n, 4), 256)
+    assert np.mean(a != b) >= 0.5 and np.mean(a != ref.chain_gram(y, 256)) >= 0.5
+
+
+# ------------------------------------------------------------------ Krum on float data: the bound is not vacuous
+# chain_gram -> robust.krum_select against the brute force on the vectors, per ratio of
+# tests/robust_select_ref.py OFFSET_RATIOS: in how many of the three OFFSET_KRUM cases the
+# selection (order included) is the same. The emulation's figures; DESIGN 3m holds the GPU's.
+EMULATED_AGREEMENT = {0: 3, 1: 3, 10: 3, 100: 3, 1e3: 0, 1e4: 0}
+
+
+def test_offset_seeds_separate_the_scores_by_more_than_2E():
+    for K, f, m in ref.OFFSET_KRUM:
+        assert K >= 2 * f + 3 and m + 1 <= K - f
+        for ratio in (0, 1):
+            x = ref.offset_data(np.random.default_rng(ref.offset_seed(K, ratio)), K, ref.OFFSET_P, ratio,
+                                ref.offset_outliers(K))
+            scores = np.sort(ref.krum_scores(x, f))
+            E = ref.krum_error_bound(x, f)
+            gaps = np.diff(scores[: m + 1])  # between consecutive selected scores, and to the first unselected
+            print(f"K={K} ratio={ratio}: E = {E:.4g}, gaps / 2E = {np.round(gaps / (2 * E), 2).tolist()}")
+            assert (gaps > 2 * E).all()
+
+
+def test_krum_error_bound_and_agreement_of_the_emulated_pipeline():
+    agree = {r: 0 for r in ref.OFFSET_RATIOS}
+    for K, f, m in ref.OFFSET_KRUM:
+        for ratio in ref.OFFSET_RATIOS:
+            x = ref.offset_data(np.random.default_rng(ref.offset_seed(K, ratio)), K, ref.OFFSET_P, ratio,
+                                ref.offset_outliers(K))
+            want, true = ref.krum_select(x, f, m)
+            G = ref.chain_gram(x, kernels.GRAM_CHAIN)
+            got, scores = robust.krum_select(G, f, m), robust.krum_scores(G, f)
+            E = ref.krum_error_bound(x, f)
+            err = np.abs(scores - true).max()
+            same = got.tolist() == want.tolist()
+            print(f"K={K} ratio={ratio:g}: err/E = {err / E:.4f}, selection {'equal' if same else 'DIFFERENT'}")
+            assert err <= E
+            unselected = np.setdiff1d(np.arange(K), got)
+            assert true[got].max() <= true[unselected].min() + 2 * E
+            agree[ratio] += same
+    assert agree == EMULATED_AGREEMENT
+
+
+def test_krum_error_bound_by_hand():
+    x = np.array([[1.0, -2.0], [3.0, 0.5], [0.0, 1.0], [1.0, 1.0], [2.0, 2.0]])
+    mass = np.abs(x) @ np.abs(x).T
+    want = max(mass[i, i] + mass[j, j] + 2 * mass[i, j] for i in range(5) for j in range(5)) * 2 * ref.GAMMA_C
+    assert ref.krum_error_bound(x, 1) == pytest.approx(want, rel=1e-15)
+    assert ref.GAMMA_C == pytest.approx(256 * 2.0 ** -24, rel=2e-5)
+
+
+def test_offset_data():
+    x = ref.offset_data(np.random.default_rng(1), 16, 4000, 100, 3)
+    assert x.dtype == np.float32 and x.shape == (16, 4000)
+    centred = x.astype(np.float64) - x[:13].astype(np.float64).mean(axis=0)
+    spread = centred.std(axis=1)
+    assert 0.9 < spread[:13].mean() < 1.1 and 2.8 < spread[13:].mean() < 3.6  # sqrt(1 + 9) = 3.16
+    assert 70 < np.abs(x).mean() < 90  # ratio * E|mu| = 100 * sqrt(2 / pi) = 79.8
+
+
+# ------------------------------------------------------------------ the seeded sweep covers what it claims
+def test_int_krum_equals_the_float64_brute_force():
+    x = int_vectors(12, 37, 4, twins=True)
+    for f, m in ((0, 1), (2, 5), (4, 8)):
+        sel, scores = ref.int_krum(x, f, m)
+        want_sel, want_scores = ref.krum_select(x, f, m)
+        assert sel.tolist() == want_sel.tolist() and scores.tolist() == want_scores.tolist()
+
+
+def test_sweep_cases_cover_the_plan_shapes():
+    lib = _lib.load()
+    cases = ref.sweep_cases()
+    assert len(cases) == 40 and cases == ref.sweep_cases()
+    assert [c[0] for c in cases[::2]] == list(ref.SWEEP_EDGE_KS)
+    assert all(1 <= c[0] <= 300 for c in cases[1::2])
+    sizes = [n for c in cases for n in c[1]]
+    assert 0 in sizes and 1 in sizes and max(sizes) <= 3000
+    assert any(n % 4 == 1 for n in sizes) and any(n % 4 == 3 for n in sizes)
+    assert any(n > 1 and n % 256 == 1 for n in sizes) and any(n % 256 == 255 for n in sizes)
+    assert {len(c[1]) for c in cases} >= {1, 2, 3, 5, 7}
+    assert any(c[2] for c in cases) and any(not c[2] for c in cases)
+    multi = elem = tails = 0
+    for K, leaves, views, f, m, seed in cases:
+        if K >= 1023:
+            assert sum(leaves) <= 600
+        if K >= 3:
+            assert K >= 2 * f + 3 and 1 <= m <= K - f
+        leaves = leaves if sum(leaves) else leaves + [1]
+        mask = ref.sweep_elem_mask(K, leaves, views)
+        blocks = kernels.ptrs_plan(_lib.F32, leaves, mask if mask.any() else False)
+        nblk = len(blocks) // 2
+        npanels = -(-K // 128)
+        nchunks = lib.fjagg_gram_workspace_bytes(K, 0, nblk) // (npanels * (npanels + 1) // 2 * 128 * 128 * 8)
+        assert 1 <= nchunks <= nblk
+        multi += nblk > nchunks and nblk % nchunks != 0  # a chunk walks b0..b1 with b1 - b0 > 1, split unevenly
+        elem += bool(mask.any())
+        tails += any((w0 >> 62) & 1 for w0 in blocks[::2].tolist())
+    assert multi >= 3 and elem >= 10 and tails >= 10
+    assert sum(c[0] > 256 for c in cases) >= 2 and sum(c[0] == 1024 for c in cases) == 1
