@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
@@ -852,19 +853,26 @@ inline size_t l2_smem(int64_t K, const L2Out& out, bool reserve = true) {
   return reserve && one_per_cu_lds() && need < kOnePerCuLds ? kOnePerCuLds : need;
 }
 
-// Lets `kern` launch with `bytes` of dynamic LDS (above the default 64 KiB: once per kernel).
+// Lets `kern` launch with `bytes` of dynamic LDS (above the default 64 KiB: once per kernel and
+// device — the attribute belongs to the current device's function object).
 int allow_lds(const void* kern, size_t bytes) {
   if (bytes <= 64 * 1024) return FJAGG_OK;
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) {
+    (void)hipGetLastError();
+    return fail(FJAGG_EHIP, "hipGetDevice: %s", hipGetErrorString(e));
+  }
   static std::mutex mu;
-  static std::unordered_map<const void*, size_t> done;
+  static std::map<std::pair<int, const void*>, size_t> done;
   std::lock_guard<std::mutex> g(mu);
-  auto it = done.find(kern);
+  const auto key = std::make_pair(dev, kern);
+  auto it = done.find(key);
   if (it != done.end() && it->second >= bytes) return FJAGG_OK;
   if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) {
     (void)hipGetLastError();
     return fail(FJAGG_EHIP, "hipFuncSetAttribute(max dynamic LDS %zu): %s", bytes, hipGetErrorString(e));
   }
-  done[kern] = bytes;
+  done[key] = bytes;
   return FJAGG_OK;
 }
 

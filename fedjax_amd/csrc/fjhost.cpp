@@ -1735,7 +1735,9 @@ struct SoloObject {
   long long nbytes;
   int state;
   int L, ndicts, tagged;
+  int dev;         // the captured leaves' device
   long long vsum;  // the leaves' version sum at the call
+  unsigned long long stream;  // the delta's device's current stream at the call: where a reader expects the value
   int cap_leaves, cap_dicts;  // capacity of the arrays below (one malloc'd block, kept across reuse)
   const void* order;          // the structure's flatten permutation (solo_structure), or nullptr
   PyObject** leaves;  // [cap_leaves] the captured leaf tensors in the capture walk's order (strong while pending)
@@ -1957,9 +1959,31 @@ int solo_sort_walk(const std::vector<int64_t>& sig, size_t& i, int& leaf, std::v
   for (auto& k : kids) out.insert(out.end(), k.second.begin(), k.second.end());
   return 0;
 }
+// takes (dir > 0) or releases a reference to every dict key object named in a walk signature
+void solo_sig_keys(const std::vector<int64_t>& sig, int dir) {
+  size_t j = 0;
+  std::function<void()> walk = [&]() {
+    const int64_t kind = sig[j++];
+    if (kind == kLeaf || kind == kNone) return;
+    const int64_t n = sig[j++];
+    for (int64_t c = 0; c < n; ++c) {
+      if (kind == kDict) {
+        PyObject* k = reinterpret_cast<PyObject*>(sig[j++]);
+        if (dir > 0) {
+          Py_INCREF(k);
+        } else {
+          Py_DECREF(k);
+        }
+      }
+      walk();
+    }
+  };
+  walk();
+}
 const SoloStruct* solo_structure(const std::vector<int64_t>& sig) {
   static auto* table = new std::unordered_map<std::vector<int64_t>, int64_t, SigHash>();
   static auto* structs = new std::deque<SoloStruct>();  // (stable addresses: nodes point at entries)
+  static auto* by_perm = new std::map<std::vector<int32_t>, int64_t>();  // one entry of structs per order
   static std::vector<int64_t> last_sig;
   static int64_t last = -1;
   if (last >= 0 && sig == last_sig) return &(*structs)[last];
@@ -1969,30 +1993,33 @@ const SoloStruct* solo_structure(const std::vector<int64_t>& sig) {
     last = it->second;
     return it->second >= 0 ? &(*structs)[it->second] : nullptr;
   }
-  if (table->size() >= 4096) return nullptr;
+  if (table->size() >= 4096) {
+    // pytrees rebuilt with fresh key objects every round add an entry each: past the cap the
+    // table starts over and lets its key objects go (the orders in structs stay: nodes point at
+    // them, and there is one per distinct order, not per entry)
+    auto old = std::move(*table);
+    table->clear();
+    last_sig.clear();
+    last = -1;
+    for (auto& e : old) solo_sig_keys(e.first, -1);
+  }
   SoloStruct st;
   size_t i = 0;
   int leaf = 0;
   const bool ok = solo_sort_walk(sig, i, leaf, st.perm) == 0 && i == sig.size();
   int64_t id = -1;
   if (ok) {
-    id = static_cast<int64_t>(structs->size());
-    structs->push_back(std::move(st));
+    auto f = by_perm->find(st.perm);
+    if (f != by_perm->end()) {
+      id = f->second;
+    } else {
+      id = static_cast<int64_t>(structs->size());
+      by_perm->emplace(st.perm, id);
+      structs->push_back(std::move(st));
+    }
   }
   // keep the key objects alive for as long as the entry exists (their addresses are in the sig)
-  {
-    size_t j = 0;
-    std::function<void()> walk = [&]() {
-      const int64_t kind = sig[j++];
-      if (kind == kLeaf || kind == kNone) return;
-      const int64_t n = sig[j++];
-      for (int64_t c = 0; c < n; ++c) {
-        if (kind == kDict) Py_INCREF(reinterpret_cast<PyObject*>(sig[j++]));
-        walk();
-      }
-    };
-    walk();
-  }
+  solo_sig_keys(sig, 1);
   table->emplace(sig, id);
   last_sig = sig;
   last = id;
@@ -2060,6 +2087,7 @@ bool solo_capture_into(SoloObject* n, PyObject* tree) {
   const bool tagged = !lists && dv.size() <= static_cast<size_t>(kSoloMaxDicts);
   if (!solo_reserve(n, L, tagged ? static_cast<int>(dv.size()) : 0)) return false;
   n->L = L;
+  n->dev = dev;
   n->vsum = vs;
   n->nbytes = 4 * numel;
   n->order = order;
@@ -2100,12 +2128,40 @@ bool solo_aligned(const SoloObject* n) {
   return true;
 }
 
+// The current stream of device `dev` is being captured into a graph. The default (null) stream
+// cannot be captured, so the runtime is asked on a side stream only: a loop on the default stream
+// (the example's) pays a thread-local read per call.
+bool solo_capturing(int dev, unsigned long long* stream = nullptr) {
+  constexpr int kDevs = 64;
+  static c10::StreamId default_id[kDevs];
+  static bool known[kDevs];
+  const c10::hip::HIPStream cur = c10::hip::getCurrentHIPStream(static_cast<c10::DeviceIndex>(dev));
+  if (dev >= 0 && dev < kDevs) {  // (the default stream by its id: no second call into torch)
+    if (!known[dev]) {
+      default_id[dev] = c10::hip::getDefaultHIPStream(static_cast<c10::DeviceIndex>(dev)).id();
+      known[dev] = true;
+    }
+    if (cur.id() == default_id[dev]) {
+      if (stream) *stream = 0;  // (the null stream's handle)
+      return false;
+    }
+  }
+  const hipStream_t s = cur.stream();
+  if (stream) *stream = reinterpret_cast<unsigned long long>(s);
+  return s != nullptr && stream_capturing(reinterpret_cast<unsigned long long>(s));
+}
+
 // Computes the values of `nodes` (pending ones; others are skipped) by pytree-kernel launches on
 // the current stream, the leaves in flatten order (solo_flatten_order): runs of consecutive
 // columns of one buffer with equal leaf shapes, every pointer aligned, fold together (the fold's
 // outputs are dropped); a misaligned node folds alone (its own element-unit plan, as every
 // computation of it). A node whose leaves changed turns stale. 0, or -1 with a Python error.
-int solo_resolve(std::vector<SoloObject*>& nodes) {
+// While the stream is being captured a launch is only recorded: nothing writes the column until a
+// replay runs, so a node must not count as done on its strength. Only solo_norm's capture route
+// (`recorded`: a node made inside the capture, whose column every replay writes before anything
+// reads it) resolves under a capture; for any other node the call raises before launching and
+// the node stays pending (read it before the capture or after it ends).
+int solo_resolve(std::vector<SoloObject*>& nodes, bool recorded = false) {
   std::vector<SoloObject*> todo;
   for (SoloObject* n : nodes) {
     if (n->state != kSoloPending) continue;
@@ -2117,6 +2173,21 @@ int solo_resolve(std::vector<SoloObject*>& nodes) {
     todo.push_back(n);
   }
   if (todo.empty()) return 0;
+  if (!recorded) {
+    int asked = -1;
+    for (SoloObject* n : todo) {
+      const int dev = THPVariable_Unpack(n->leaves[0]).get_device();
+      if (dev == asked) continue;
+      asked = dev;
+      if (solo_capturing(dev)) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "lazy norms: a norm taken before a graph capture cannot be computed while its stream is "
+                        "capturing (the launch would only be recorded, and the value would not exist until a replay); "
+                        "read it before the capture starts or after it ends");
+        return -1;
+      }
+    }
+  }
   if (!g_solo.rows_fn || !g_solo.l2ws_fn || !g_solo.plan_fn) {
     PyErr_SetString(PyExc_RuntimeError, "lazy norms: libfjagg entry points not configured (solo_config)");
     return -1;
@@ -2245,6 +2316,7 @@ int solo_evict() {
 // registry entry after the previous match is tried first (clients in registration order); after
 // a miss, a map of the pending nodes by tree (built once per mean) answers.
 struct SoloMatcher {
+  unsigned long long stream = 0;  // the mean's stream
   size_t cursor = 0;
   bool built = false;
   std::unordered_map<PyObject*, SoloObject*> by_tree;
@@ -2268,7 +2340,9 @@ struct SoloMatcher {
       if (it == by_tree.end() || it->second->state != kSoloPending) return nullptr;
       n = it->second;
     }
-    return (n->L == L && solo_same_tree(n, tree) && solo_unchanged(n)) ? n : nullptr;
+    // (a norm taken on another stream than the mean's stays pending: its reader is ordered behind
+    // its own stream, not behind the mean's launch, and computes it there when it reads)
+    return (n->L == L && n->stream == stream && solo_same_tree(n, tree) && solo_unchanged(n)) ? n : nullptr;
   }
 };
 
@@ -2515,6 +2589,7 @@ PyObject* mean_pairs_impl(PyObject* pairs, bool triples, int may_pipeline, doubl
       }
     } held_nodes{fused};
     SoloMatcher matcher;
+    matcher.stream = stream;
     SoloObject* next_node = nullptr;  // a match found past the end of the previous run (borrowed)
     bool next_none = false;           // the client past the previous run has no pending node
     for (int64_t k1 : bounds) {
@@ -3664,66 +3739,48 @@ PyObject* solo_probe(PyObject*, PyObject* args) {
 
 // tree_l2_norm / tree_l2_squared (which 1 / 0) of a delta no running sum took: a lazy view of a
 // SoloNorm node (see "standalone lazy norms"). The most recent node answers for its own tree
-// when unchanged (the norm and the squared norm of one delta share a column); a norm takes the
-// pool's next pair. Py_None: not the fast case; nullptr: a Python error.
+// when unchanged and taken on the same stream (the norm and the squared norm of one delta share a
+// column); a norm takes the pool's next pair. A node remembers the stream current at the call: only
+// a mean on that stream fills it (SoloMatcher), so its reader, ordered behind that stream, never
+// runs ahead of the write. Py_None: not the fast case; nullptr: a Python error.
 PyObject* solo_norm(PyObject* tree, int which) {
   try {
     // Under a graph capture the norm is computed now, by the launch that computes it whenever it is
     // read alone (solo_resolve: the same kernel and plan, so the same bits), which the graph records:
     // a node with a column of its own (a direct column is never handed out again, a pooled one is
-    // once its view is dropped, and every replay writes the column). Asked at the first norm of a
-    // round (nothing pending), not per client.
-    if (g_solo.pending == 0 &&
-        stream_capturing(reinterpret_cast<unsigned long long>(c10::hip::getCurrentHIPStream().stream()))) {
-      auto* c = reinterpret_cast<SoloObject*>(g_solo.type->tp_alloc(g_solo.type, 0));
-      if (!c) return nullptr;
-      struct DropC {
-        SoloObject* n;
-        ~DropC() { Py_DECREF(n); }
-      } drop_c{c};
-      if (!solo_capture_into(c, tree)) {
-        if (PyErr_Occurred()) return nullptr;
-        Py_RETURN_NONE;
-      }
-      PyObject* buf;
-      long long idx;
-      if (!solo_column(THPVariable_Unpack(c->leaves[0]).get_device(), &buf, &idx)) return nullptr;
-      Py_INCREF(buf);
-      Py_XSETREF(c->buf, buf);
-      c->idx = idx;
-      PyObject* v = solo_view(c, which);
-      if (!v) return nullptr;
-      c->state = kSoloPending;
-      ++g_solo.pending;
-      g_solo.pending_bytes += c->nbytes;
-      std::vector<SoloObject*> one{c};
-      if (solo_resolve(one) != 0) {
-        solo_release(c, kSoloDone);
-        Py_DECREF(v);
-        return nullptr;
-      }
-      return v;
-    }
+    // once its view is dropped, and every replay writes the column). Asked on every call, whatever
+    // is pending (a norm left pending from before the capture must neither answer for a delta the
+    // captured round norms again nor turn the round's norms into pending nodes no replay refreshes),
+    // once the delta's device is known: solo_capturing asks the runtime on a side stream only.
+    bool capturing = false, asked = false;
+    unsigned long long home = 0;  // the delta's device's current stream
     if (!g_solo.reg.empty()) {
       SoloObject* c = g_solo.reg.back().node;
-      if (c->state == kSoloPending && c->tree == tree && solo_same_tree(c, tree) && solo_unchanged(c))
-        return solo_view(c, which);
+      if (c->state == kSoloPending && c->tree == tree && solo_same_tree(c, tree) && solo_unchanged(c)) {
+        capturing = solo_capturing(c->dev, &home);
+        asked = true;
+        if (!capturing && home == c->stream) return solo_view(c, which);
+      }
     }
     SoloObject* n = nullptr;   // (a new reference)
     PyObject* view = nullptr;  // the pool's view for n (a new reference)
     bool pooled = false;       // (its buffer's record holds the view too)
-    if (which == 1 && g_solo.pool_head < g_solo.pool.size()) {
+    if (!capturing && which == 1 && g_solo.pool_head < g_solo.pool.size()) {
       const auto pr = g_solo.pool[g_solo.pool_head];
       auto* pn = reinterpret_cast<SoloObject*>(pr.second);
       if (!solo_capture_into(pn, tree)) {
         if (PyErr_Occurred()) return nullptr;
         Py_RETURN_NONE;  // (the pair stays in the pool)
       }
-      if (THPVariable_Unpack(pn->leaves[0]).get_device() == THPVariable_Unpack(pn->buf).get_device()) {
+      capturing = solo_capturing(pn->dev, &home);
+      asked = true;
+      if (capturing) {
+        solo_release(pn, kSoloDone);  // (the pair stays in the pool: a pooled column is handed out again)
+      } else if (pn->dev == THPVariable_Unpack(pn->buf).get_device()) {
         ++g_solo.pool_head;  // the pool's references to the pair move to its buffer's record
         SoloState::BufRec* rec = nullptr;
-        for (auto& r : g_solo.bufs)
-          if (r.buf == pn->buf) rec = &r;
+        for (size_t r = g_solo.bufs.size(); r-- > 0 && !rec;)  // (usually the newest record)
+          if (g_solo.bufs[r].buf == pn->buf) rec = &g_solo.bufs[r];
         if (rec) {
           rec->pairs.push_back(pr);
           Py_INCREF(pr.first);
@@ -3749,7 +3806,35 @@ PyObject* solo_norm(PyObject* tree, int which) {
       SoloObject* n;
       ~DropN() { Py_DECREF(n); }
     } drop_n{n};
-    const int dev = THPVariable_Unpack(n->leaves[0]).get_device();
+    const int dev = n->dev;
+    if (!asked) capturing = solo_capturing(dev, &home);
+    n->stream = home;
+    if (capturing) {  // (n is a fresh node: not the pool's, not registered; its view holds it)
+      PyObject* buf;
+      long long idx;
+      if (!solo_column(dev, &buf, &idx)) {
+        solo_release(n, kSoloDone);
+        return nullptr;
+      }
+      Py_INCREF(buf);
+      Py_XSETREF(n->buf, buf);
+      n->idx = idx;
+      PyObject* v = solo_view(n, which);
+      if (!v) {
+        solo_release(n, kSoloDone);
+        return nullptr;
+      }
+      n->state = kSoloPending;
+      ++g_solo.pending;
+      g_solo.pending_bytes += n->nbytes;
+      std::vector<SoloObject*> one{n};
+      if (solo_resolve(one, true) != 0) {
+        solo_release(n, kSoloDone);
+        Py_DECREF(v);
+        return nullptr;
+      }
+      return v;
+    }
     // the pending limits: past max_pending every pending norm is computed now (one launch per
     // run); past the byte budget, the ones whose pytree nobody but the node holds any more (the
     // deltas the views alone keep alive), rechecked after every further quarter budget

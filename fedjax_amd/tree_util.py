@@ -815,7 +815,13 @@ def set_lazy_norms(enabled: bool = True, *, budget_bytes: Optional[int] = None,
     updated in place before its norm is computed makes reading the view raise RuntimeError
     (the value at the call is gone); writes that bypass torch's version counter are not
     detected, as for deferred sums. Disabled (or ``set_deferred_sums(False)``): every call
-    computes at once, as the reference does."""
+    computes at once, as the reference does.
+
+    Streams and graph captures: a norm is filled only by a mean running on the stream that was
+    current at the norm's call (any other reader computes it on its own stream). While the
+    current stream is being captured every norm is computed at once by a recorded launch, so
+    replays refresh it; a norm still pending from before the capture cannot be computed until
+    the capture ends (reading it inside the capture raises RuntimeError)."""
     _LAZY["enabled"] = bool(enabled)
     if budget_bytes is not None:
         _LAZY["budget_bytes"] = int(budget_bytes) if int(budget_bytes) > 0 else None
@@ -1727,6 +1733,22 @@ def _l2_fast(pytree_, which: int):
     return None if got is None else got[1 + which]
 
 
+def _l2_converted(pytree_, td, row: List[torch.Tensor], which: int):
+    """(l2sq, l2)[which] of a tree some of whose leaves had to be converted (DLPack producers such
+    as jax.Arrays, host or strided leaves) once they are all float32: by :func:`_l2_fast` over the
+    canonical device leaves, so the value has the bits of the equivalent device tensors' norm,
+    computed at once (the converted leaves do not share the originals' version counters, so a
+    pending capture could not notice a later in-place write). None: not this case."""
+    if any(x.dtype != torch.float32 for x in row):
+        return None
+    if all(a is b for a, b in zip(pytree.leaves_of(pytree_), row)):
+        return None  # (nothing was converted: _l2_fast already declined this tree)
+    got = _l2_fast(pytree.unflatten(td, list(row)), which)
+    if type(got) is _NormView:
+        _HOST.flush_views(got)
+    return got
+
+
 def _tree_l2_squared_py(pytree_: PyTree) -> torch.Tensor:
     """Returns squared l2 norm of tree (tree_util.py:105-108), a 0-d float32 tensor.
     :func:`tree_l2_squared` is the native fjhost.tree_l2_squared, which returns the lazy
@@ -1735,9 +1757,12 @@ def _tree_l2_squared_py(pytree_: PyTree) -> torch.Tensor:
     got = _l2_fast(pytree_, 0)
     if got is not None:
         return got
-    _, rows = _client_rows([pytree_])
+    td, rows = _client_rows([pytree_])
     if not rows[0]:
         return torch.zeros((), dtype=torch.float32, device=_default_device())
+    got = _l2_converted(pytree_, td, rows[0], 0)
+    if got is not None:
+        return got
     if len({x.dtype for x in rows[0]}) > 1 or rows[0][0].dtype == torch.int32:
         return _l2sq_mixed(rows[0])
     return _l2_rows(rows, take_sqrt=False).reshape(())
@@ -1750,9 +1775,12 @@ def _tree_l2_norm_py(pytree_: PyTree) -> torch.Tensor:
     got = _l2_fast(pytree_, 1)
     if got is not None:
         return got
-    _, rows = _client_rows([pytree_])
+    td, rows = _client_rows([pytree_])
     if not rows[0]:
         return torch.zeros((), dtype=torch.float32, device=_default_device())
+    got = _l2_converted(pytree_, td, rows[0], 1)
+    if got is not None:
+        return got
     if len({x.dtype for x in rows[0]}) > 1 or rows[0][0].dtype == torch.int32:
         return torch.sqrt(_l2sq_mixed(rows[0]).float())  # jnp.sqrt of an int32 sum is float32
     return _l2_rows(rows, take_sqrt=True).reshape(())

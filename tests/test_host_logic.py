@@ -53,6 +53,36 @@ def test_leaf_canonicalisation_rules():
         tu._to_tensor(True)
 
 
+class _DLPackOnly:
+    """A DLPack producer with no other tensor attribute (what a jax.Array is to this library)."""
+
+    def __init__(self, t):
+        self._t = t
+
+    def __dlpack__(self, stream=None, **kw):
+        return self._t.__dlpack__(stream=stream, **kw)
+
+    def __dlpack_device__(self):
+        return self._t.__dlpack_device__()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.int32])
+def test_dlpack_leaf_shares_the_producers_memory(dtype):
+    """_to_tensor of a DLPack producer is a zero-copy tensor of its dtype and shape: a later
+    in-place write to the producer's tensor is seen through it (nothing is snapshotted)."""
+    private = (torch.arange(33 * 3, dtype=torch.float32).reshape(33, 3) - 40).to(dtype)
+    t = tu._to_tensor(_DLPackOnly(private))
+    assert type(t) is torch.Tensor and t.dtype == dtype and t.shape == private.shape
+    assert t.data_ptr() == private.data_ptr() and torch.equal(t, private)
+    private.add_(3)
+    assert torch.equal(t, private)
+    strided = tu._to_tensor(_DLPackOnly(private.t()))  # a non-contiguous producer keeps its strides
+    assert strided.shape == (3, 33) and strided.stride() == private.t().stride() and torch.equal(strided, private.t())
+    leaf = tu._device_leaf(_DLPackOnly(private.t()), torch.device("cpu"), -1)
+    assert leaf.is_contiguous() and torch.equal(leaf, private.t())
+    assert not hasattr(_DLPackOnly(private), "dtype")  # (only the protocol is used)
+
+
 def _decode(blocks):
     b = blocks.reshape(-1, 2).tolist()
     return [((w0 >> 40) & 0x3FFFFF, bool((w0 >> 62) & 1), w0 & ((1 << 40) - 1), w1) for w0, w1 in b]
@@ -229,3 +259,23 @@ def test_nontemporal_threshold_setter():
     finally:
         tu.set_nontemporal_min_bytes(old)
     assert tu.NONTEMPORAL_MIN_BYTES == old
+
+
+def test_structure_table_lets_its_keys_go_past_the_cap():
+    """fjhost's solo_structure interns a pytree structure by the addresses of its dict key objects
+    and holds those keys. Pytrees rebuilt with fresh key objects add an entry each: at 4096
+    entries the table starts over and releases every key it held (it used to stop taking new
+    structures for good, the keys pinned for the life of the process)."""
+    import sys
+    H = tu._HOST
+    first = ["".join(["w", str(i)]) for i in range(2)]  # (built at run time: not interned)
+    tree = {first[0]: torch.ones(4), first[1]: torch.ones(3)}
+    held = [sys.getrefcount(k) for k in first]
+    H.solo_probe(tree, 1)  # (walks the tree and looks its structure up; host tensors: nothing is captured)
+    assert [sys.getrefcount(k) for k in first] == [c + 1 for c in held]
+    for _ in range(4096):
+        keys = ["".join(["w", str(i)]) for i in range(2)]
+        H.solo_probe({keys[0]: torch.ones(4), keys[1]: torch.ones(3)}, 1)
+    assert [sys.getrefcount(k) for k in first] == held
+    H.solo_probe(tree, 1)  # the same structure is taken again after the table started over
+    assert [sys.getrefcount(k) for k in first] == [c + 1 for c in held]
