@@ -18,7 +18,10 @@ Mirror of google/fedjax 0.0.17 ``fedjax/aggregators/aggregator.py``:
 * :func:`krum_aggregator` / :func:`geometric_median_aggregator` — Krum / multi-Krum (Blanchard et
   al., NeurIPS 2017) and the smoothed-Weiszfeld geometric median (Pillutla et al., IEEE TSP 2022;
   no reference counterparts), :func:`fedjax_amd.tree_util.tree_krum` /
-  :func:`fedjax_amd.tree_util.tree_geometric_median`.
+  :func:`fedjax_amd.tree_util.tree_geometric_median`;
+* :func:`mean_around_median_aggregator` / :func:`bulyan_aggregator` — the mean around the median
+  (Xie et al. 2018) and Bulyan (El Mhamdi et al., ICML 2018; no reference counterparts),
+  :func:`fedjax_amd.tree_util.tree_mean_around_median` / :func:`fedjax_amd.tree_util.tree_bulyan`.
 """
 
 import dataclasses as std_dataclasses
@@ -257,6 +260,67 @@ def krum_aggregator(num_byzantine: int, num_selected: int = 1) -> Aggregator:
         ids = [cid for cid, _, _ in triples]
         return got.mean, KrumAggregatorState(tuple(ids[k] for k in got.selected),
                                             {cid: float(s) for cid, s in zip(ids, got.scores)})
+
+    return Aggregator(init, apply)
+
+
+def mean_around_median_aggregator(keep: int) -> Aggregator:
+    """Builds the mean-around-the-median aggregator ("MeaMed", Xie et al. 2018): per coordinate
+    the mean of the ``keep`` client values closest to the coordinate's median, in one launch
+    (:func:`fedjax_amd.tree_util.tree_mean_around_median`). A round needs ``K >= keep`` clients.
+
+    ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
+    client must not be able to scale its own vote in a robust aggregate. Float32 params, at most
+    128 clients a round."""
+    if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)):
+        raise TypeError("keep must be an int count")
+    if keep < 1:
+        raise ValueError(f"a keep count must be >= 1, got {keep}")
+
+    def init():
+        return RobustAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
+        return tree_util.tree_mean_around_median(params, keep), state
+
+    return Aggregator(init, apply)
+
+
+@dataclasses.dataclass
+class BulyanAggregatorState:
+    """The last round's selection: ``selected`` — the client ids Bulyan's first stage chose, in
+    selection order; ``keep`` — how many of their values the second stage averaged per
+    coordinate. Empty before the first round."""
+    selected: Tuple[ClientId, ...] = ()
+    keep: int = 0
+
+
+def bulyan_aggregator(num_byzantine: int) -> Aggregator:
+    """Builds the Bulyan aggregator of El Mhamdi, Guerraoui and Rouault (ICML 2018):
+    :func:`fedjax_amd.tree_util.tree_bulyan` of the round's params — ``K - 2f`` clients chosen by
+    iterated Krum, ``f = num_byzantine``, then per coordinate the mean of the ``K - 4f`` chosen
+    values closest to their median. A round needs ``K >= 4f + 3`` clients.
+
+    ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
+    client must not be able to scale its own vote. It returns ``None`` for a round with no
+    clients or too few selectable ones. Float32 params, at most 1024 clients a round with
+    ``K - 2f <= 128``."""
+    if isinstance(num_byzantine, (bool, np.bool_)) or not isinstance(num_byzantine, (int, np.integer)):
+        raise TypeError("num_byzantine must be an int")
+    if num_byzantine < 0:
+        raise ValueError(f"need num_byzantine >= 0, got {num_byzantine}")
+
+    def init():
+        return BulyanAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        triples = list(clients_params_and_weights)  # the weights are not used
+        got = tree_util.tree_bulyan([param for _, param, _ in triples], num_byzantine)
+        if got is None:
+            return None, BulyanAggregatorState()
+        ids = [cid for cid, _, _ in triples]
+        return got.mean, BulyanAggregatorState(tuple(ids[k] for k in got.selected), int(got.keep))
 
     return Aggregator(init, apply)
 

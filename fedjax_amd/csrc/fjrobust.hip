@@ -1,5 +1,7 @@
 // fjrobust.hip — coordinate-wise trimmed mean and median over the client axis
-// (include/fjagg.h: fjagg_trim_dense, fjagg_trim_ptrs; Yin et al., ICML 2018).
+// (include/fjagg.h: fjagg_trim_dense, fjagg_trim_ptrs; Yin et al., ICML 2018) and the mean
+// around the median (fjagg_meamed_dense, fjagg_meamed_ptrs; Xie et al. 2018), Bulyan's second
+// stage.
 //
 // Not a fold: every coordinate needs two order statistics of its K client values. One lane
 // owns one column (fjrobust_dev.h has the per-column routine and the reasons for its shape):
@@ -40,6 +42,7 @@ int check_launch(const char* what) {
 
 constexpr int64_t kTrimMaxRowBytes = 1ll << 30;
 constexpr int kTrimMaxClients = 128;
+constexpr int kMeamedMaxSlabRows = 1024;  // the Gram pass's client limit: Bulyan selects among so many
 
 // Workgroup size per width: 256 lanes while the tile stays at 32 KiB, one wave above that
 // (16 KiB at N = 64, 32 KiB at N = 128: five workgroups of a CU's 160 KiB). 256 lanes at every
@@ -91,9 +94,8 @@ __global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_dense(const uint32_t
 // with the element flag, or the leaf's tail past its last whole unit — and the 256 / TPB
 // workgroups blockIdx.y of that entry walk it 256 columns at a time, as one 256-lane workgroup
 // of the fold would.
-template <int N, bool NT>
-__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_ptrs(const int64_t* __restrict__ img, int L, int K, int V,
-                                                                  int t, float scale, int do_scale) {
+template <int N, bool NT, class Column>
+__device__ __forceinline__ void ptrs_walk(const int64_t* __restrict__ img, int L, int K, int V, Column column) {
   constexpr int TPB = TrimShape<N>::TPB;
   const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + (int64_t)K * L;
@@ -117,26 +119,82 @@ __global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_ptrs(const int64_t* 
     auto load = [=](int k) {
       return load_bits<NT>(reinterpret_cast<const uint32_t*>(in_ptrs[(int64_t)k * L + leaf]) + g, off);
     };
-    const uint32_t y = fjrobust::trim_column<N, TPB>(load, K, t, do_scale != 0, scale, tile);
+    const uint32_t y = column(load, tile);
     if (valid) store_bits(ob + col, y);
   }
 }
 
-int trim_check(int in_dtype, int64_t K, int64_t t, int flags, int allowed) {
-  if (in_dtype != FJAGG_F32) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: float32 deltas and output only");
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_ptrs(const int64_t* __restrict__ img, int L, int K, int V,
+                                                                  int t, float scale, int do_scale) {
+  ptrs_walk<N, NT>(img, L, K, V, [=](auto load, fjrobust::KeyPair* tile) {
+    return fjrobust::trim_column<N, TrimShape<N>::TPB>(load, K, t, do_scale != 0, scale, tile);
+  });
+}
+
+// The mean around the median (fjrobust_dev.h around_median_column) over the same two layouts.
+// Dense: participating client k is slab row rows.r[k]. The table travels in the kernel
+// arguments and k is uniform over the wave, so a row's index is a scalar load from the argument
+// segment: nothing is uploaded and no row outside the table is ever addressed.
+constexpr int kMeamedMaxClients = 128;
+struct MeamedRows {
+  int32_t r[kMeamedMaxClients];
+};
+
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_meamed_dense(const uint32_t* __restrict__ x, int64_t ld, int M,
+                                                                     int64_t P, int keep, float scale, int do_scale,
+                                                                     uint32_t* __restrict__ out,
+                                                                     const MeamedRows rows) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const int64_t col0 = (int64_t)blockIdx.x * TPB, col = col0 + threadIdx.x;
+  const bool valid = col < P;
+  const uint32_t off = valid ? threadIdx.x : (uint32_t)(P - 1 - col0);
+  const uint32_t* base = x + col0;
+  const int32_t* rt = rows.r;
+  auto load = [=](int k) { return load_bits<NT>(base + (int64_t)rt[k] * ld, off); };
+  const uint32_t y =
+      fjrobust::around_median_column<N, TPB>(load, M, keep, do_scale != 0, scale, lane_tile<N, TPB>());
+  if (valid) store_bits(out + col, y);
+}
+
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_meamed_ptrs(const int64_t* __restrict__ img, int L, int K,
+                                                                    int V, int keep, float scale, int do_scale) {
+  ptrs_walk<N, NT>(img, L, K, V, [=](auto load, fjrobust::KeyPair* tile) {
+    return fjrobust::around_median_column<N, TrimShape<N>::TPB>(load, K, keep, do_scale != 0, scale, tile);
+  });
+}
+
+// what both aggregates refuse: the dtype, the flags and the client count
+int column_check(const char* who, int in_dtype, int64_t K, int flags, int allowed) {
+  if (in_dtype != FJAGG_F32) return fail(FJAGG_EUNSUPPORTED, "%s: float32 deltas and output only", who);
   if (flags & FJAGG_ACCUMULATE)
-    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: order statistics do not accumulate (no FJAGG_ACCUMULATE)");
-  if (flags & FJAGG_NARROW) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no FJAGG_NARROW plans");
+    return fail(FJAGG_EUNSUPPORTED, "%s: order statistics do not accumulate (no FJAGG_ACCUMULATE)", who);
+  if (flags & FJAGG_NARROW) return fail(FJAGG_EUNSUPPORTED, "%s: no FJAGG_NARROW plans", who);
   if (flags & FJAGG_HOST_TABLES)
-    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: device plan only (no FJAGG_HOST_TABLES)");
-  if (flags & FJAGG_ZEROED_WS) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no norms (no FJAGG_ZEROED_WS)");
-  if (flags & FJAGG_UNBALANCED) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: no FJAGG_UNBALANCED");
-  if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "trimmed mean: unsupported flags 0x%x", flags & ~allowed);
+    return fail(FJAGG_EUNSUPPORTED, "%s: device plan only (no FJAGG_HOST_TABLES)", who);
+  if (flags & FJAGG_ZEROED_WS) return fail(FJAGG_EUNSUPPORTED, "%s: no norms (no FJAGG_ZEROED_WS)", who);
+  if (flags & FJAGG_UNBALANCED) return fail(FJAGG_EUNSUPPORTED, "%s: no FJAGG_UNBALANCED", who);
+  if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "%s: unsupported flags 0x%x", who, flags & ~allowed);
   if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
   if (K > kTrimMaxClients)
-    return fail(FJAGG_EUNSUPPORTED, "trimmed mean: K <= %d clients (got %lld)", kTrimMaxClients, (long long)K);
+    return fail(FJAGG_EUNSUPPORTED, "%s: K <= %d clients (got %lld)", who, kTrimMaxClients, (long long)K);
+  return FJAGG_OK;
+}
+
+int trim_check(int in_dtype, int64_t K, int64_t t, int flags, int allowed) {
+  if (int rc = column_check("trimmed mean", in_dtype, K, flags, allowed)) return rc;
   if (t < 0 || 2 * t >= K)
     return fail(FJAGG_EINVAL, "trimmed mean: need 0 <= 2t < K (t=%lld, K=%lld)", (long long)t, (long long)K);
+  return FJAGG_OK;
+}
+
+int meamed_check(int in_dtype, int64_t M, int64_t keep, int flags, int allowed) {
+  if (int rc = column_check("mean around median", in_dtype, M, flags, allowed)) return rc;
+  if (keep < 1 || keep > M)
+    return fail(FJAGG_EINVAL, "mean around median: need 1 <= keep <= M (keep=%lld, M=%lld)", (long long)keep,
+                (long long)M);
   return FJAGG_OK;
 }
 
@@ -156,6 +214,24 @@ int launch_trim_ptrs(const int64_t* img, int L, int K, int64_t nblk, int V, int 
   const dim3 grid((unsigned)nblk, 256 / TPB);
   hipLaunchKernelGGL((k_trim_ptrs<N, NT>), grid, dim3(TPB), 0, s, img, L, K, V, t, scale, ds);
   return check_launch("k_trim_ptrs");
+}
+
+template <int N, bool NT>
+int launch_meamed_dense(const uint32_t* x, int64_t ld, int K, int64_t P, int keep, float scale, int ds, uint32_t* y,
+                        const MeamedRows& rows, hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)((P + TPB - 1) / TPB));
+  hipLaunchKernelGGL((k_meamed_dense<N, NT>), grid, dim3(TPB), 0, s, x, ld, K, P, keep, scale, ds, y, rows);
+  return check_launch("k_meamed_dense");
+}
+
+template <int N, bool NT>
+int launch_meamed_ptrs(const int64_t* img, int L, int K, int64_t nblk, int V, int keep, float scale, int ds,
+                       hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)nblk, 256 / TPB);
+  hipLaunchKernelGGL((k_meamed_ptrs<N, NT>), grid, dim3(TPB), 0, s, img, L, K, V, keep, scale, ds);
+  return check_launch("k_meamed_ptrs");
 }
 
 }  // namespace
@@ -195,6 +271,51 @@ int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
   const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
   return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_trim_ptrs, true, image_dev, L, k, nblk, V, tt, scale, ds, s)
                                      : FJ_TRIM_WIDTH(launch_trim_ptrs, false, image_dev, L, k, nblk, V, tt, scale, ds, s);
+}
+
+int fjagg_meamed_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P, const int32_t* rows_host,
+                       int64_t M, int64_t keep, float scale, void* out_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = meamed_check(in_dtype, M, keep, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (K_rows < 1 || K_rows > kMeamedMaxSlabRows)
+    return fail(K_rows < 1 ? FJAGG_EINVAL : FJAGG_EUNSUPPORTED,
+                "mean around median: a slab of 1 <= K_rows <= %d rows (got %lld)", kMeamedMaxSlabRows, (long long)K_rows);
+  if (M > K_rows)
+    return fail(FJAGG_EINVAL, "mean around median: M <= K_rows (M=%lld, K_rows=%lld)", (long long)M, (long long)K_rows);
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld (P=%lld, ld=%lld)", (long long)P, (long long)ld);
+  if (P * 4 > kTrimMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "mean around median: rows <= 1 GiB");
+  if (!x_dev || !out_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  MeamedRows rows;
+  for (int k = 0; k < kMeamedMaxClients; ++k) {
+    // entries past M are never read; they repeat the last row so that every entry is a row of the slab
+    const int64_t r = k < M ? (rows_host ? (int64_t)rows_host[k] : (int64_t)k) : (int64_t)rows.r[M - 1];
+    if (r < 0 || r >= K_rows || (k > 0 && k < M && r <= rows.r[k - 1]))
+      return fail(FJAGG_EINVAL,
+                  "mean around median: rows must be strictly ascending in [0, K_rows) (rows[%d]=%lld, K_rows=%lld)", k,
+                  (long long)r, (long long)K_rows);
+    rows.r[k] = (int32_t)r;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(x_dev);
+  uint32_t* y = reinterpret_cast<uint32_t*>(out_dev);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, K = (int)M, kp = (int)keep;
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_meamed_dense, true, x, ld, K, P, kp, scale, ds, y, rows, s)
+                                     : FJ_TRIM_WIDTH(launch_meamed_dense, false, x, ld, K, P, kp, scale, ds, y, rows, s);
+}
+
+int fjagg_meamed_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t keep, float scale,
+                      int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = meamed_check(in_dtype, K, keep, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1 || L >= (1 << 22))
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!image_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, k = (int)K, kp = (int)keep;
+  const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
+  return (flags & FJAGG_NONTEMPORAL)
+             ? FJ_TRIM_WIDTH(launch_meamed_ptrs, true, image_dev, L, k, nblk, V, kp, scale, ds, s)
+             : FJ_TRIM_WIDTH(launch_meamed_ptrs, false, image_dev, L, k, nblk, V, kp, scale, ds, s);
 }
 
 }  // extern "C"

@@ -779,6 +779,100 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 
+MEAMED_MAX_SLAB_ROWS = 1024  # fjagg_meamed_dense: the slab a row table selects from (the Gram pass's limit)
+
+
+def keep_count(keep, K: int) -> int:
+    """The keep count ``beta`` of a mean around the median over ``K`` participating clients,
+    checked: an int in ``[1, K]``. Raises ``TypeError`` for a bool or a non-int, ``ValueError``
+    for ``K`` outside ``[1, 128]`` or a count out of range. Nothing here touches the library."""
+    K = int(K)
+    if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)):
+        raise TypeError(f"keep must be an int count, not {type(keep).__name__}")
+    if K < 1:
+        raise ValueError(f"a mean around the median needs at least 1 client, got K = {K}")
+    if K > TRIM_MAX_CLIENTS:
+        raise ValueError(f"the mean around the median supports K <= {TRIM_MAX_CLIENTS} participating clients, "
+                         f"got K = {K}")
+    if not (1 <= int(keep) <= K):
+        raise ValueError(f"keep must be in [1, K] = [1, {K}], got {keep}")
+    return int(keep)
+
+
+def _row_table(rows, K_rows: int) -> np.ndarray:
+    """``rows`` as the int32 table ``fjagg_meamed_dense`` takes: strictly ascending indices into
+    a slab of ``K_rows`` rows, at most 128 of them."""
+    if isinstance(rows, torch.Tensor):
+        rows = rows.cpu().numpy()
+    table = np.asarray(rows)
+    if table.ndim != 1 or not (1 <= table.size <= TRIM_MAX_CLIENTS):
+        raise ValueError(f"rows must name between 1 and {TRIM_MAX_CLIENTS} slab rows, got shape {table.shape}")
+    if table.dtype == np.bool_ or not np.issubdtype(table.dtype, np.integer):
+        raise TypeError("rows must be a sequence of int row indices")
+    table = table.astype(np.int64)
+    if table[0] < 0 or table[-1] >= K_rows or (np.diff(table) <= 0).any():
+        raise ValueError(f"rows must be strictly ascending in [0, K) = [0, {K_rows})")
+    return np.ascontiguousarray(table, dtype=np.int32)
+
+
+def meamed_dense(x: torch.Tensor, keep: int, rows=None, *, scale: Optional[float] = None,
+                 out: Optional[torch.Tensor] = None, nontemporal: bool = False) -> torch.Tensor:
+    """Coordinate-wise sum around the median of a float32 slab ``x[K, P]`` (row stride
+    ``x.stride(0)``, unit column stride, float32 alignment only): per column the ``keep`` values
+    closest to the column's lower median (fjagg.h: a tie keeps the lower side) are added in
+    client order, then multiplied by ``scale`` (the mean passes f32(1 / keep)). ``rows``: the
+    participating slab rows, strictly ascending, at most 128 of a slab of up to 1024 (default:
+    all ``K <= 128`` rows); the table travels in the kernel arguments, so nothing is uploaded
+    and no other row is read. One launch of ``fjagg_meamed_dense``; there are no weights.
+    Everything is checked before the library is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the mean around the median takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if rows is not None:
+        if not (1 <= K <= MEAMED_MAX_SLAB_ROWS):
+            raise ValueError(f"a row table selects from a slab of 1 <= K <= {MEAMED_MAX_SLAB_ROWS} rows, got K = {K}")
+        table = _row_table(rows, K)
+    else:
+        table = None
+    M = K if table is None else int(table.size)
+    keep = keep_count(keep, M)
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the mean around the median takes rows of up to 1 GiB")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.dim() != 1 or out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, out)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_meamed_dense", _lib.F32, x.data_ptr(), ld, K, P, None if table is None else table.ctypes.data,
+              M, keep, float(scale if scale is not None else 1.0), out.data_ptr(), flags, _stream_handle(dev))
+    return out
+
+
+def meamed_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, keep: int, scale: Optional[float], *,
+                unaligned: bool = False, nontemporal: bool = False) -> None:
+    """Launch ``fjagg_meamed_ptrs`` over a device plan image (as :func:`trim_ptrs` takes it,
+    holding only the ``K`` participating clients): :func:`meamed_dense`'s arithmetic on every
+    leaf in one launch. ``unaligned`` as the plan was made. Checked before the library is
+    touched."""
+    keep = keep_count(keep, K)
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    dev = _require_device(image_dev)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    flags |= _lib.UNALIGNED if unaligned else 0
+    _lib.call("fjagg_meamed_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, keep,
+              float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
+
+
 GRAM_MAX_CLIENTS = 1024  # fjagg_gram_*: G is K x K float64, at most 8 MiB (fjagg.h)
 GRAM_CHAIN = 256  # FJAGG_GRAM_CHAIN: columns per float32 fmaf chain, between float64 additions
 _GRAM_WS = {}  # device index -> workspace of the Gram pass (partial sums per workgroup chunk)

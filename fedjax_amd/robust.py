@@ -1,9 +1,13 @@
-"""Host-side selection for the two whole-vector Byzantine-robust aggregates, on the K x K Gram
+"""Host-side selection for the whole-vector Byzantine-robust aggregates, on the K x K Gram
 matrix ``G[i][j] = <x_i, x_j>`` of the client deltas (numpy float64; no GPU, no torch).
 
 * Krum / multi-Krum — Blanchard, El Mhamdi, Guerraoui and Stainer, "Machine Learning with
   Adversaries: Byzantine Tolerant Gradient Descent", NeurIPS 2017: the client(s) whose delta is
   closest to its ``K - f - 2`` nearest neighbours. Needs ``d2(i, j) = G_ii + G_jj - 2 G_ij``.
+* Bulyan's selection — El Mhamdi, Guerraoui and Rouault, "The Hidden Vulnerability of Distributed
+  Learning in Byzantium", ICML 2018: Krum iterated ``K - 2f`` times on the shrinking set of
+  clients not yet chosen. The coordinate-wise second stage is the mean around the median
+  (``fjagg_meamed_*``) over the chosen clients.
 * The geometric median by the smoothed Weiszfeld algorithm ("RFA") — Pillutla, Kakade and
   Harchaoui, "Robust Aggregation for Federated Learning", IEEE Trans. Signal Processing 2022.
   Every iterate is ``v = sum_j a_j x_j``, so ``|v - x_k|^2 = a'Ga - 2 (Ga)_k + G_kk``: all
@@ -21,7 +25,7 @@ from typing import Tuple
 
 import numpy as np
 
-__all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "weiszfeld_weights"]
+__all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "bulyan_select", "weiszfeld_weights"]
 
 
 def _gram(G) -> np.ndarray:
@@ -99,6 +103,59 @@ def krum_select(G, f, m=1) -> np.ndarray:
     order = np.argsort(scores, kind="stable")
     order = order[np.isfinite(scores[order])]
     return order[:m].astype(np.int64)
+
+
+def check_bulyan(K: int, f) -> int:
+    """Bulyan's conditions on the client count alone: an int ``f >= 0`` (a bool is refused) and
+    ``K >= 4f + 3``. Returns ``f``."""
+    f = _int("num_byzantine", f)
+    if f < 0:
+        raise ValueError(f"num_byzantine must be >= 0, got {f}")
+    if K < 4 * f + 3:
+        raise ValueError(f"Bulyan needs K >= 4f + 3 clients: K = {K}, f = {f}")
+    return f
+
+
+def bulyan_select(G, f) -> np.ndarray:
+    """int64 indices of Bulyan's first stage, in selection order: ``theta = K - 2f`` times, the
+    client of smallest Krum score among the set ``R`` of usable clients not yet chosen, which
+    then leaves ``R``. Needs ``K >= 4f + 3`` and an int ``f >= 0`` (a bool is refused).
+
+    With ``n = |R|``, ``score_i`` is the sum of the ``c = max(n - f - 2, 1)`` smallest ``d2(i, j)``,
+    ``j`` in ``R`` without ``i``, added in ascending order from 0.0 (0.0 when ``n = 1``); the
+    smallest FINITE score wins, ties to the lower index; with no finite score the selection stops
+    short. The paper applies Krum to the remaining set unchanged, whose neighbour count ``n - f - 2``
+    falls below 1 on the last steps (Krum itself wants ``n >= 2f + 3``, and the set shrinks to
+    ``2f + 1``); the clamp at one neighbour is this project's decision. With every client usable
+    the first pick is ``krum_select(G, f, 1)[0]``.
+
+    Every row's neighbours are sorted once (by distance, then index); a step takes each
+    remaining row's first ``c`` remaining neighbours in that order, so the sums are those of a
+    fresh sort per step."""
+    G = _gram(G)
+    K = G.shape[0]
+    f = check_bulyan(K, f)
+    d2 = sq_distances(G)
+    alive = usable(G).copy()
+    order = np.argsort(d2, axis=1, kind="stable")  # row i: its neighbours, nearest first
+    near = np.take_along_axis(d2, order, axis=1)
+    not_self = order != np.arange(K)[:, None]
+    selected = []
+    for _ in range(K - 2 * f):
+        rows = np.flatnonzero(alive)  # R, ascending
+        if rows.size == 0:
+            break
+        c = max(rows.size - f - 2, 1)
+        cand = alive[order[rows]] & not_self[rows]
+        take = cand & (np.cumsum(cand, axis=1) <= c)
+        # zeros between the taken terms leave a sequential sum of non-negative terms unchanged
+        scores = np.cumsum(np.where(take, near[rows], 0.0), axis=1)[:, -1]
+        best = int(np.argmin(scores))  # the first minimum: ties to the lower index
+        if not np.isfinite(scores[best]):
+            break
+        selected.append(int(rows[best]))
+        alive[rows[best]] = False
+    return np.array(selected, dtype=np.int64)
 
 
 def weiszfeld_weights(G, alpha=None, nu: float = 1e-6, iterations: int = 4) -> Tuple[np.ndarray, np.ndarray]:

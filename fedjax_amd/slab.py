@@ -327,6 +327,64 @@ class ClientDeltaSlab:
         kernels.trim_count(0, self.num_clients)
         return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
 
+    def mean_around_median(self, keep, *, rows: Optional[Sequence[int]] = None,
+                           out: Optional[torch.Tensor] = None) -> PyTree:
+        """The mean around the median of the rows ("MeaMed", Xie et al. 2018; the coordinate-wise
+        stage of Bulyan): in every coordinate, the mean of the ``keep`` client values closest to
+        the coordinate's lower median ``s_mid``, ``mid = (K-1) // 2``. ``keep`` is an int in
+        ``[1, K]``; a bool is refused. ``rows``: the participating clients, strictly ascending
+        row indices, at most 128 of a slab of up to 1024 rows (default: all rows of a slab of up
+        to 128); ``K`` is then their number and no other row is read. One launch, nothing
+        uploaded (the row table travels in the kernel arguments: graph-capturable), no
+        temporary.
+
+        The order, the ties and the sum are :meth:`trimmed_mean`'s; a value's distance from the
+        median is ``|fl(v - med)|`` in float32 (0 for the median's own bits, ``+inf`` where the
+        difference is NaN) and the kept sorted positions are a window around ``mid`` grown
+        towards the strictly closer side, the lower side on a tie. The result is multiplied by
+        f32(1 / keep): ``keep = K`` is bit for bit ``mean([1] * K)``, ``keep = 1`` the lower
+        median verbatim. There are no weights. A float32 slab. Returns the template's pytree
+        (views into ``out`` if given: float32, ``num_params`` elements)."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"mean_around_median needs a float32 slab, not {self.dtype}")
+        if rows is not None:
+            if self.num_clients > kernels.MEAMED_MAX_SLAB_ROWS:
+                raise ValueError(f"a row table selects from a slab of up to {kernels.MEAMED_MAX_SLAB_ROWS} "
+                                 f"clients, got K = {self.num_clients}")
+            rows = kernels._row_table(rows, self.num_clients)
+        M = self.num_clients if rows is None else int(rows.size)
+        keep = kernels.keep_count(keep, M)
+        if self.num_params == 0:  # a template of empty leaves: nothing to launch
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            return self.unflatten(flat)
+        flat = kernels.meamed_dense(self.rows, keep, rows, scale=float(np.float32(tree_util._inverse(keep))), out=out,
+                                    nontemporal=M * self.num_params * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return self.unflatten(flat)
+
+    def bulyan(self, num_byzantine) -> "tree_util.BulyanResult":
+        """Bulyan (El Mhamdi, Guerraoui and Rouault, ICML 2018) over the rows: Krum iterated
+        ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
+        (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then
+        :meth:`mean_around_median` with ``keep = theta - 2f`` over the chosen rows in ascending
+        order. ``K >= 4f + 3``.
+
+        :meth:`gram`, ONE device-to-host copy of the K x K float64 Gram, the selection on the
+        host, then one launch whose row table names the chosen clients — the others are never
+        loaded, so up to ``f`` clients full of NaN, inf or 1e30 cannot reach the result, and a
+        client that hides one huge coordinate behind a small distance is cut by the
+        coordinate-wise stage. There are no client weights. Returns a
+        :class:`~fedjax_amd.tree_util.BulyanResult`; ``mean`` is ``None`` when fewer than
+        ``2f + 1`` clients could be selected. A float32 slab of up to 1024 clients with
+        ``K - 2f <= 128``. Raises under stream capture."""
+        kernels.refuse_capture("bulyan", kernels._TWO_PASS)
+        if self.dtype != torch.float32:
+            raise TypeError(f"bulyan needs a float32 slab, not {self.dtype}")
+        f = tree_util._check_bulyan_args(self.num_clients, num_byzantine)
+        gram = self.gram()
+        selected, members, keep = tree_util._bulyan_plan(gram.cpu().numpy(), f)
+        mean = self.mean_around_median(keep, rows=members) if keep else None
+        return tree_util.BulyanResult(mean, selected, keep, gram)
+
     def gram(self, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Gram matrix ``G[i][j] = <row i, row j>`` of the K deltas as a float64 ``[K, K]`` device
         tensor: one pass over the slab on the f32 matrix instruction

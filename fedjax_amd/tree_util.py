@@ -47,6 +47,7 @@ __all__ = [
     "tree_dp_clipped_mean",
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
     "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
+    "tree_mean_around_median", "tree_bulyan", "BulyanResult",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -2022,10 +2023,21 @@ def tree_trimmed_mean(pytrees: Iterable[PyTree], trim) -> Optional[PyTree]:
         return None
     K = len(trees)
     t = kernels.trim_count(trim, K)
+    scale = float(np.float32(_inverse(K - 2 * t)))
+    return _tree_columns(trees, "tree_trimmed_mean",
+                         lambda image_dev, L, nblk, nt: kernels.trim_ptrs(image_dev, L, K, nblk, t, scale,
+                                                                          nontemporal=nt))
+
+
+def _tree_columns(trees: list, what: str, launch) -> PyTree:
+    """The pytree route of the per-column aggregates (trimmed mean, mean around the median) over
+    a non-empty list of client trees: ``tree_mean``'s structure walk and checks, one result row,
+    one plan image, and ``launch(image_dev, L, nblk, nontemporal)`` once over every leaf."""
+    K = len(trees)
     bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
                   if _CANONICAL.get(x.dtype) != torch.float32})
     if bad:
-        raise TypeError(f"tree_trimmed_mean needs float32 leaves (got {bad})")
+        raise TypeError(f"{what} needs float32 leaves (got {bad})")
     td, rows = _client_table(trees)
     if not rows[0]:
         return pytree.unflatten(td, [])
@@ -2043,8 +2055,7 @@ def tree_trimmed_mean(pytrees: Iterable[PyTree], trim) -> Optional[PyTree]:
     blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)
     image = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, blocks])
     image_dev = _lib.upload(torch.from_numpy(image), device)
-    nt = int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES
-    kernels.trim_ptrs(image_dev, L, K, len(blocks) // 2, t, float(np.float32(_inverse(K - 2 * t))), nontemporal=nt)
+    launch(image_dev, L, len(blocks) // 2, int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES)
     return result
 
 
@@ -2057,6 +2068,95 @@ def tree_median(pytrees: Iterable[PyTree]) -> Optional[PyTree]:
         return None
     kernels.trim_count(0, len(trees))
     return tree_trimmed_mean(trees, (len(trees) - 1) // 2)
+
+
+def tree_mean_around_median(pytrees: Iterable[PyTree], keep) -> Optional[PyTree]:
+    """The mean around the median of client pytrees ("MeaMed", Xie et al. 2018; the coordinate-wise
+    stage of Bulyan): in every coordinate of every leaf, the mean of the ``keep`` client values
+    closest to the coordinate's lower median ``s_mid``, ``mid = (K-1) // 2``. ``keep`` is an int
+    in ``[1, K]``; a bool is refused.
+
+    Values are ranked by the total order of :func:`tree_trimmed_mean`, ties by client index; the
+    distance of a value from the median is ``|fl(v - med)|`` in float32 (0 for the median's own
+    bits, ``+inf`` where the difference is NaN); the kept sorted positions are a window around
+    ``mid`` grown towards the strictly closer side, the lower side on a tie. The kept values are
+    added in client order and multiplied by f32(1 / keep): ``keep = K`` is bit for bit
+    ``tree_trimmed_mean(0)``, ``keep = 1`` the lower median verbatim, and the result is bit for
+    bit :meth:`fedjax_amd.slab.ClientDeltaSlab.mean_around_median` over the same deltas. There
+    are no weights. The walk, checks, plan image and ONE launch are :func:`tree_trimmed_mean`'s.
+    Float32 leaves, ``K <= 128``; no clients: ``None``. Raises under stream capture (the plan
+    image goes through a pinned staging buffer)."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    K = len(trees)
+    keep = kernels.keep_count(keep, K)
+    scale = float(np.float32(_inverse(keep)))
+    return _tree_columns(trees, "tree_mean_around_median",
+                         lambda image_dev, L, nblk, nt: kernels.meamed_ptrs(image_dev, L, K, nblk, keep, scale,
+                                                                            nontemporal=nt))
+
+
+class BulyanResult(NamedTuple):
+    """Result of Bulyan (:func:`tree_bulyan`, :meth:`fedjax_amd.slab.ClientDeltaSlab.bulyan`):
+    ``mean`` — the mean around the median over the selected clients (``None`` when fewer than
+    ``2f + 1`` could be selected); ``selected`` — their indices in selection order (int64
+    numpy); ``keep`` — the keep count ``len(selected) - 2f`` of the second stage (0 with no
+    mean); ``gram`` — the float64 ``[K, K]`` Gram matrix on the device."""
+    mean: Any
+    selected: Any
+    keep: int
+    gram: Any
+
+
+BULYAN_MAX_SELECTED = kernels.TRIM_MAX_CLIENTS  # theta = K - 2f clients reach the column routine
+
+
+def _check_bulyan_args(K: int, num_byzantine) -> int:
+    """Bulyan's argument checks on K and f alone, before any pass over the deltas."""
+    from fedjax_amd import robust
+
+    kernels._check_gram_clients(K)
+    f = robust.check_bulyan(K, num_byzantine)
+    if K - 2 * f > BULYAN_MAX_SELECTED:
+        raise ValueError(f"Bulyan's second stage takes K - 2f <= {BULYAN_MAX_SELECTED} selected clients, "
+                         f"got K = {K}, f = {f}")
+    return f
+
+
+def _bulyan_plan(G: np.ndarray, f: int):
+    """(selected in selection order, the participating clients ascending, keep) over the host Gram."""
+    from fedjax_amd import robust
+
+    selected = robust.bulyan_select(G, f)
+    keep = len(selected) - 2 * f
+    return selected, sorted(int(k) for k in selected), (keep if keep >= 1 else 0)
+
+
+def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine) -> Optional[BulyanResult]:
+    """Bulyan over client pytrees (El Mhamdi, Guerraoui and Rouault, ICML 2018): Krum iterated
+    ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
+    (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then, per coordinate, the
+    mean of the ``theta - 2f`` selected values closest to their median
+    (:func:`tree_mean_around_median` over the selected trees in ascending client order). Krum
+    bounds the distance of what it picks but lets an attacker hide a huge error in one
+    coordinate; the coordinate-wise stage closes that. Needs ``K >= 4f + 3``.
+
+    Two passes over the deltas, as :func:`tree_krum`: the Gram matrix, ONE device-to-host copy,
+    the selection on the host, then one launch that never loads an unselected client. A client
+    holding NaN, inf or 1e30 has a non-finite squared norm: it is unusable and never selected;
+    with more than ``theta - 2f - 1`` such clients the selection is too short and ``mean`` is
+    ``None``. There are no client weights. Float32 leaves, ``K <= 1024`` and ``K - 2f <= 128``.
+    Returns a :class:`BulyanResult`; no clients: ``None``. Raises under stream capture."""
+    kernels.refuse_capture("tree_bulyan", kernels._TWO_PASS)
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    f = _check_bulyan_args(len(trees), num_byzantine)
+    gram = _tree_gram(trees)[0]
+    selected, members, keep = _bulyan_plan(gram.cpu().numpy(), f)
+    mean = tree_mean_around_median([trees[k] for k in members], keep) if keep else None
+    return BulyanResult(mean, selected, keep, gram)
 
 
 class KrumResult(NamedTuple):

@@ -21,6 +21,7 @@
  *     (no reference row) DP-FedAvg's Gaussian mechanism      fjagg_wsum_clip_noise_* (clipped mean + noise)
  *     (no reference row) trimmed mean / median (Yin et al. 2018) fjagg_trim_* (order statistics per coordinate)
  *     (no reference row) Krum / geometric median (Gram matrix)  fjagg_gram_* (K x K inner products, float64)
+ *     (no reference row) mean around the median / Bulyan        fjagg_meamed_* (the keep values nearest the median)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -575,6 +576,39 @@ int fjagg_trim_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int
  * launch over all leaves. */
 int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t, float scale,
                     int flags, void* stream);
+
+/*
+ * The mean around the median over the client axis ("MeaMed": Xie, Koyejo and Gupta, "Generalized
+ * Byzantine-tolerant SGD", 2018), which is also the coordinate-wise second stage of Bulyan (El Mhamdi,
+ * Guerraoui and Rouault, "The Hidden Vulnerability of Distributed Learning in Byzantium", ICML 2018):
+ * per coordinate, the mean of the `keep` client values closest to the coordinate's median. The
+ * reference has no such aggregator; the semantics are fixed here. One launch, the
+ * participating deltas read once, no temporary. Float32, 1 <= M <= 128 participating clients in client
+ * order, 1 <= keep <= M. For every element p, with v_k = x_k[p] and key() and the total order as above:
+ *     s_0 .. s_{M-1} = the values ranked by (key(v_k), k); mid = (M-1)/2; med = s_mid (the lower median)
+ *     d_j = 0 if key(s_j) == key(med), else |fl(s_j - med)| with a NaN result replaced by +inf
+ *     a_lo = max(0, mid - keep + 1), a_hi = min(mid, M - keep),
+ *     a = a_lo + #{ i in [a_lo, a_hi) : d_{i+keep} < d_i }   (strict: a tie keeps the lower side)
+ *     the clients of rank a .. a + keep - 1 are kept (ties among equal keys by client index)
+ *     s = the first kept v_k verbatim; s = fl(s + v_k) over the kept clients in CLIENT order (no FMA)
+ *     out[p] = fl(s * scale) with FJAGG_SCALE (the caller passes f32(1 / keep)), else s
+ * keep = M is bit for bit fjagg_trim_* at t = 0; keep = 1 is s_mid verbatim (odd M: the median).
+ * There are no weights. The dense entry takes an optional table of M slab rows: participating client
+ * k is row rows_host[k] of a slab of K_rows rows (strictly ascending; null: rows 0 .. M-1). The table
+ * travels in the kernel arguments: nothing is uploaded, and a row outside the table is never read.
+ * Flags: FJAGG_SCALE, FJAGG_NONTEMPORAL and, on the pytree entry, FJAGG_UNALIGNED (the flag the
+ * plan was made with). Refused on the host with nothing launched: everything fjagg_trim_* refuses
+ * for its dtype, flags and client count (M > 128: FJAGG_EUNSUPPORTED; M < 1: FJAGG_EINVAL); keep < 1
+ * or keep > M, M > K_rows, K_rows < 1, rows not strictly ascending or outside [0, K_rows), null
+ * pointers, P < 1, ld < P, a bad plan (FJAGG_EINVAL); K_rows > 1024 and rows over 1 GiB
+ * (FJAGG_EUNSUPPORTED).
+ */
+/* Dense slab: row r at x_dev + r*ld elements, P elements each; out_dev is float[P]. */
+int fjagg_meamed_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P, const int32_t* rows_host,
+                       int64_t M, int64_t keep, float scale, void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image as fjagg_trim_ptrs takes it, holding only the K participating clients. */
+int fjagg_meamed_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t keep, float scale,
+                      int flags, void* stream);
 
 /*
  * The K x K Gram matrix of the client deltas, G[i][j] = sum_p x_i[p] * x_j[p], in float64: the one
