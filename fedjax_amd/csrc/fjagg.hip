@@ -648,6 +648,80 @@ __device__ __forceinline__ void l2_epilogue(float* l2lds, float* __restrict__ ws
   }
 }
 
+// The norm policy of a fold kernel. L2: the launch's dynamic LDS is this workgroup's
+// (kThreads/64) x K norm rows, zeroed here, and each wave accumulates into its own row (LdsNorm);
+// norm_epilogue turns the rows into the workgroup's partial row. Otherwise NoNorm, no LDS.
+__device__ __forceinline__ float* l2_rows() {
+  extern __shared__ __attribute__((aligned(16))) float l2lds[];
+  return l2lds;
+}
+template <bool L2>
+__device__ __forceinline__ auto lds_norm(int64_t K) {
+  if constexpr (L2) {
+    float* rows = l2_rows();
+    for (int64_t i = threadIdx.x; i < (kThreads / 64) * K; i += kThreads) rows[i] = 0.f;
+    __syncthreads();
+    return LdsNorm{rows + (threadIdx.x >> 6) * K};
+  } else {
+    return NoNorm{};
+  }
+}
+template <bool L2>
+__device__ __forceinline__ void norm_epilogue(float* __restrict__ ws, int64_t K, const L2Out& out, int64_t row) {
+  if constexpr (L2) l2_epilogue(l2_rows(), ws, K, out, row);
+}
+
+// The slab walk of every dense fold kernel but k_dense (which adds split mode, MINW and WK): the
+// layout described at k_dense. Block 0 folds the tail_n tail elements with 1-element units, every
+// other block its range of S units in groups of kThreads*E, lanes past the range clamped to its
+// last unit and masked. The policies go to fold() untouched. ALL_LANES: the tail block's lanes
+// past tail_n fold too, masked (with norms every lane must join the per-client wave reductions);
+// otherwise they return.
+template <int IN, int OUT, int V, int E, int U, bool NT, bool BURST, bool ALL_LANES, class RowFn, class NORM,
+          class EPI, class CLIP = NoClip, class INIT = FromFirst>
+__device__ __forceinline__ void dense_walk(RowFn row, int64_t K, int64_t nunits, int tail_n, int64_t S,
+                                           uint8_t* __restrict__ ob, const float* __restrict__ w, bool dsc,
+                                           float scale, bool acm, NORM nrm, const EPI& epi, CLIP clip = CLIP(),
+                                           INIT init = INIT()) {
+  constexpr int IB = Elem<IN>::B;
+  const int tid = threadIdx.x;
+  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
+  int64_t b = blockIdx.x;
+  bool is_tail = false;
+  if (tail_n > 0) {
+    if (b == 0) {
+      is_tail = true;
+      const bool active = tid < tail_n;
+      if (ALL_LANES || active) {
+        const int64_t e = nunits * V + (active ? tid : 0);
+        const uint32_t off[1] = {(uint32_t)(e * IB)};
+        const bool valid[1] = {active};
+        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip, init);
+      }
+      // (the two exits as the kernels had them before they shared this walk: either form alone
+      // moves the register count of some instantiation, DESIGN.md "One dense walk")
+      if constexpr (!ALL_LANES) return;
+    }
+    b -= 1;
+  }
+  if (is_tail) return;
+  const int64_t u_begin = b * S;
+  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
+  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
+    uint32_t off[E];
+    bool valid[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      int64_t u = g + j * kThreads + tid;
+      valid[j] = u < u_end;
+      if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the store is skipped
+      off[j] = (uint32_t)(u * (V * IB));
+    }
+    fold<IN, AccF, OUT, V, E, U, NT, BURST>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip,
+                                            init);
+  }
+}
+
 // k_dense + per-client squared norms (exact mode, float fold). Dynamic LDS holds
 // (kThreads/64) x K floats (16 x K with a completion counter); block b writes its
 // per-client partials to ws[b*K + k], added in block order by the last workgroup
@@ -657,46 +731,11 @@ __global__ __launch_bounds__(kThreads) void k_dense_l2(
     const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
     const float* __restrict__ w, float scale, int do_scale, int accumulate,
     uint8_t* __restrict__ out, int64_t S, float* __restrict__ ws, const L2Out l2out) {
-  extern __shared__ __attribute__((aligned(16))) float l2lds[];
-  constexpr int IB = Elem<IN>::B;
-  const int tid = threadIdx.x;
-  for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
-  __syncthreads();
-  LdsNorm nrm{l2lds + (tid >> 6) * K};
+  const auto nrm = lds_norm<true>(K);
   auto row = [=](int64_t k) { return x + k * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  bool is_tail = false;
-  if (tail_n > 0) {
-    if (b == 0) {
-      is_tail = true;
-      const bool active = tid < tail_n;  // every lane joins the wave reductions
-      const int64_t e = nunits * V + (active ? tid : 0);
-      const uint32_t off[1] = {(uint32_t)(e * IB)};
-      const bool valid[1] = {active};
-      fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0,
-                                       scale, accumulate != 0, nrm);
-    }
-    b -= 1;
-  }
-  if (!is_tail) {
-    const int64_t u_begin = b * S;
-    const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-      uint32_t off[E];
-      bool valid[E];
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        int64_t u = g + j * kThreads + tid;
-        valid[j] = u < u_end;
-        if (!valid[j]) u = u_end - 1;
-        off[j] = (uint32_t)(u * (V * IB));
-      }
-      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0,
-                                       scale, accumulate != 0, nrm);
-    }
-  }
-  l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+  dense_walk<IN, OUT, V, E, U, NT, true, true>(row, K, nunits, tail_n, S, out, w, do_scale != 0, scale,
+                                               accumulate != 0, nrm, PlainEpi());
+  norm_epilogue<true>(ws, K, l2out, blockIdx.x);
 }
 
 // The dense exact fold with per-client clip factors c[K] applied before the weights
@@ -709,53 +748,11 @@ __global__ __launch_bounds__(kThreads) void k_dense_clip(
     const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
     const float* __restrict__ w, const float* __restrict__ c, float scale, int do_scale, int accumulate,
     uint8_t* __restrict__ out, int64_t S, float* __restrict__ ws, const L2Out l2out) {
-  extern __shared__ __attribute__((aligned(16))) float l2lds[];
-  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
-  const int tid = threadIdx.x;
-  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
-  Norm nrm{};
-  if constexpr (L2) {
-    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
-    __syncthreads();
-    nrm = LdsNorm{l2lds + (tid >> 6) * K};
-  }
-  const DevClip clip{c};
+  const auto nrm = lds_norm<L2>(K);
   auto row = [=](int64_t k) { return x + k * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  bool is_tail = false;
-  if (tail_n > 0) {
-    if (b == 0) {
-      is_tail = true;
-      const bool active = tid < tail_n;
-      if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
-        const int64_t e = nunits * V + (active ? tid : 0);
-        const uint32_t off[1] = {(uint32_t)(e * IB)};
-        const bool valid[1] = {active};
-        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0, scale,
-                                         accumulate != 0, nrm, PlainEpi(), clip);
-      }
-    }
-    b -= 1;
-  }
-  if (!is_tail) {
-    const int64_t u_begin = b * S;
-    const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-      uint32_t off[E];
-      bool valid[E];
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        int64_t u = g + j * kThreads + tid;
-        valid[j] = u < u_end;
-        if (!valid[j]) u = u_end - 1;
-        off[j] = (uint32_t)(u * (V * IB));
-      }
-      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, out, valid, w, do_scale != 0, scale,
-                                       accumulate != 0, nrm, PlainEpi(), clip);
-    }
-  }
-  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+  dense_walk<FJAGG_F32, FJAGG_F32, V, E, U, NT, true, L2>(row, K, nunits, tail_n, S, out, w, do_scale != 0, scale,
+                                                          accumulate != 0, nrm, PlainEpi(), DevClip{c});
+  norm_epilogue<L2>(ws, K, l2out, blockIdx.x);
 }
 
 // Clip factors of K clients from their squared norms (fjagg_clip_scales), one lane per client:
@@ -882,38 +879,9 @@ template <int IN, int V, int E, int U, bool NT>
 __global__ __launch_bounds__(kThreads) void k_dense_opt(
     const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
     const float* __restrict__ w, float scale, int64_t S, OptEpi epi) {
-  constexpr int IB = Elem<IN>::B;
-  const int tid = threadIdx.x;
   auto row = [=](int64_t k) { return x + k * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  if (tail_n > 0) {
-    if (b == 0) {
-      if (tid < tail_n) {
-        const uint32_t off[1] = {(uint32_t)((nunits * V + tid) * IB)};
-        const bool valid[1] = {true};
-        fold<IN, AccF, FJAGG_F32, 1, 1, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true,
-                                               scale, false, NoNorm(), epi);
-      }
-      return;
-    }
-    b -= 1;
-  }
-  const int64_t u_begin = b * S;
-  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-    uint32_t off[E];
-    bool valid[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-      int64_t u = g + j * kThreads + tid;
-      valid[j] = u < u_end;
-      if (!valid[j]) u = u_end - 1;
-      off[j] = (uint32_t)(u * (V * IB));
-    }
-    fold<IN, AccF, FJAGG_F32, V, E, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale,
-                                           false, NoNorm(), epi);
-  }
+  dense_walk<IN, FJAGG_F32, V, E, U, NT, true, false>(row, K, nunits, tail_n, S, nullptr, w, true, scale, false,
+                                                      NoNorm(), epi);
 }
 
 // Walks the unit range [u0, u1) of one leaf (units of VV elements): in groups of
@@ -953,11 +921,72 @@ __device__ __forceinline__ void walk_units(RowFn row, uint32_t row_bytes, int64_
   }
 }
 
-// The plan entry of hardware workgroup h of nb when XCD x (= h % 8) takes the consecutive
-// entries [x*q + min(x, r), +q + (x < r)), q = nb / 8, r = nb % 8: a permutation of [0, nb).
-__device__ __forceinline__ int64_t xcd_plan_index(int64_t h, int64_t nb) {
-  const int64_t q = nb >> 3, r = nb & 7, x = h & 7, i = h >> 3;
-  return x * q + (x < r ? x : r) + i;
+// One entry of a plan image's block table, decoded (the words are described at k_ptrs). blocks =
+// leaf_n + L in every image. e_base: the leaf element this workgroup's rows and output are rebased
+// at, so that lane offsets stay 32-bit for a leaf of any size (a workgroup's range is a few MB at
+// most): the tail's first element, else the range's first unit.
+struct PlanBlock {
+  int leaf;
+  bool tail, elem;
+  int64_t u0, u1, n, e_base;
+};
+template <int V>
+__device__ __forceinline__ PlanBlock plan_block(const int64_t* __restrict__ leaf_n, int L, int64_t bid) {
+  const int64_t* blk = leaf_n + L + 2 * bid;
+  const int64_t be = blk[0];
+  PlanBlock p;
+  p.leaf = (int)((be >> 40) & 0x3fffff);
+  p.tail = (be >> 62) & 1;
+  p.elem = ((uint64_t)be >> 63) != 0;
+  p.u0 = be & ((1ll << 40) - 1);
+  p.u1 = blk[1];
+  p.n = leaf_n[p.leaf];
+  p.e_base = p.tail ? p.n / V * V : ((V > 1 && p.elem) ? p.u0 : p.u0 * V);
+  return p;
+}
+// address `addr` (0: absent) as float32 elements, from element e on
+__device__ __forceinline__ float* f32_at(int64_t addr, int64_t e) {
+  return addr ? reinterpret_cast<float*>(addr) + e : nullptr;
+}
+// the block's first output byte in the leaf at `addr`
+template <int OUT>
+__device__ __forceinline__ uint8_t* out_at(int64_t addr, const PlanBlock& p) {
+  return reinterpret_cast<uint8_t*>(addr) + p.e_base * Elem<OUT>::B;
+}
+
+// Folds a plan block: client k's row is leaf p.leaf of in_ptrs[k*L + ..], rebased at p.e_base
+// like ob. The tail block takes 1-element units over the leaf's last n % V elements, a block
+// with the element flag walks single elements, every other one units of V (walk_units). The
+// policies go to fold() untouched. ALL_LANES as in dense_walk. (k_ptrs_opt and k_ptrs_group_opt
+// use plan_block and walk_leaf; the other pytree folds keep the same decode and dispatch in their
+// bodies: with these pieces their register counts move, for two of them across a wave per SIMD,
+// DESIGN.md §3o.)
+template <int IN, class ACC, int OUT, int V, bool NT, bool BURST, bool ALL_LANES, class NORM, class EPI,
+          class CLIP = NoClip, class INIT = FromFirst>
+__device__ __forceinline__ void walk_leaf(const PlanBlock& p, const int64_t* __restrict__ in_ptrs, int L, int64_t K,
+                                          uint8_t* ob, const typename ACC::T* __restrict__ w, bool dsc, float scale,
+                                          bool acm, NORM nrm, const EPI& epi, CLIP clip = CLIP(), INIT init = INIT()) {
+  constexpr int IB = Elem<IN>::B;
+  const int tid = threadIdx.x;
+  const int leaf = p.leaf;
+  const int64_t e_base = p.e_base;
+  auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
+  const uint32_t row_bytes = row_range((p.n - e_base) * IB);
+  if (p.tail) {
+    const bool active = tid < p.n - e_base;
+    if (ALL_LANES || active) {
+      const int64_t e = active ? tid : 0;
+      const uint32_t off[1] = {(uint32_t)(e * IB)};
+      const bool valid[1] = {active};
+      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, K, off, ob, valid, w, dsc, scale, acm, nrm, epi, clip, init);
+    }
+  } else if (V > 1 && p.elem) {
+    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, K, 0, p.u1 - p.u0, ob, w, dsc, scale, acm, nrm, epi, clip,
+                                           init);
+  } else {
+    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, K, 0, p.u1 - p.u0, ob, w, dsc, scale, acm, nrm, epi, clip,
+                                           init);
+  }
 }
 
 // Pytree path. image = in_ptrs[K*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk].
@@ -984,12 +1013,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs(const int64_t* __restrict__ i
   const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + K * L;
   const int64_t* leaf_n = out_ptrs + L;
-  // accumulate bit 1 (FJAGG_XCD_REMAP, the launchers): workgroups are dealt round-robin over the
-  // 8 XCDs, so hardware workgroup h runs on XCD h % 8; plan entry bid = xcd_plan_index(h) gives
-  // each XCD a run of consecutive plan entries (neighbouring unit ranges of one leaf: the same
-  // pages of every client's row in that XCD's L2 and translation caches). Each entry is folded
-  // exactly as without it, and its norm partial keeps its row: the same bits.
-  const int64_t bid = (accumulate & 2) ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t bid = (int64_t)blockIdx.x;
   const int64_t* blk = leaf_n + L + 2 * bid;
   const int64_t be = blk[0];
   const int leaf = (int)((be >> 40) & 0x3fffff);
@@ -1005,7 +1029,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs(const int64_t* __restrict__ i
   uint8_t* ob = reinterpret_cast<uint8_t*>(out_ptrs[leaf]) + e_base * Elem<OUT>::B;
   auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
   const uint32_t row_bytes = row_range((n - e_base) * IB);
-  const bool dsc = do_scale != 0, acm = (accumulate & 1) != 0;
+  const bool dsc = do_scale != 0, acm = accumulate != 0;
   // L2: per-client squared norms of this block's units, (kThreads/64) x K floats in LDS
   extern __shared__ __attribute__((aligned(16))) float l2lds[];
   using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
@@ -1032,10 +1056,9 @@ __global__ __launch_bounds__(kThreads) void k_ptrs(const int64_t* __restrict__ i
 }
 
 // k_ptrs with per-client clip factors c[K] applied before the weights (fjagg_wsum_clip_ptrs):
-// float32 leaves and fold, device image and weights; the plan image, block words and unit walk
-// are k_ptrs's (restated here rather than shared, so that k_ptrs compiles to the code it always
-// did). L2: also the per-client squares of the clipped products, into the partial rows ws
-// (added by k_l2_combine only: l2out.done is never set here).
+// float32 leaves and fold, device image and weights; k_ptrs's plan image. L2: also the per-client
+// squares of the clipped products, into the partial rows ws (added by k_l2_combine only:
+// l2out.done is never set here).
 template <int V, bool NT, bool L2, bool BURST>
 __global__ __launch_bounds__(kThreads) void k_ptrs_clip(const int64_t* __restrict__ img, int L, int64_t K,
                                                         const float* __restrict__ w, const float* __restrict__ c,
@@ -1048,7 +1071,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip(const int64_t* __restric
   const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + K * L;
   const int64_t* leaf_n = out_ptrs + L;
-  const int64_t bid = (accumulate & 2) ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t bid = (int64_t)blockIdx.x;
   const int64_t* blk = leaf_n + L + 2 * bid;
   const int64_t be = blk[0];
   const int leaf = (int)((be >> 40) & 0x3fffff);
@@ -1062,7 +1085,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip(const int64_t* __restric
   uint8_t* ob = reinterpret_cast<uint8_t*>(out_ptrs[leaf]) + e_base * Elem<OUT>::B;
   auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
   const uint32_t row_bytes = row_range((n - e_base) * IB);
-  const bool dsc = do_scale != 0, acm = (accumulate & 1) != 0;
+  const bool dsc = do_scale != 0, acm = accumulate != 0;
   extern __shared__ __attribute__((aligned(16))) float l2lds[];
   using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
   Norm nrm{};
@@ -1119,59 +1142,26 @@ __global__ __launch_bounds__(kThreads) void k_dense_group(
     const int* __restrict__ seg, const float* __restrict__ wperm, const float* __restrict__ gscale,
     const int* __restrict__ gorder, int G, int do_scale, uint8_t* __restrict__ out, int64_t out_stride_bytes,
     int64_t S) {
-  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
-  const int tid = threadIdx.x;
   GroupSlot gs;
   if (!group_slot(gorder, seg, G, gs)) return;
   const int* ord = order + gs.m0;
-  const float* w = wperm + gs.m0;
   const float scale = do_scale ? gscale[gs.g] : 1.0f;
-  uint8_t* ob = out + (int64_t)gs.g * out_stride_bytes;
   auto row = [=](int64_t j) { return x + (int64_t)ord[j] * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  if (tail_n > 0) {
-    if (b == 0) {
-      if (tid < tail_n) {
-        const int64_t e = nunits * V + tid;
-        const uint32_t off[1] = {(uint32_t)(e * IB)};
-        const bool valid[1] = {true};
-        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, gs.n, off, ob, valid, w, do_scale != 0, scale, false,
-                                         NoNorm(), PlainEpi(), NoClip(), FromZero());
-      }
-      return;
-    }
-    b -= 1;
-  }
-  const int64_t u_begin = b * S;
-  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-    uint32_t off[E];
-    bool valid[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-      int64_t u = g + j * kThreads + tid;
-      valid[j] = u < u_end;
-      if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the store is skipped
-      off[j] = (uint32_t)(u * (V * IB));
-    }
-    fold<IN, AccF, OUT, V, E, U, NT, BURST>(row, row_bytes, gs.n, off, ob, valid, w, do_scale != 0, scale, false,
-                                            NoNorm(), PlainEpi(), NoClip(), FromZero());
-  }
+  dense_walk<FJAGG_F32, FJAGG_F32, V, E, U, NT, BURST, false>(
+      row, gs.n, nunits, tail_n, S, out + (int64_t)gs.g * out_stride_bytes, wperm + gs.m0, do_scale != 0, scale,
+      false, NoNorm(), PlainEpi(), NoClip(), FromZero());
 }
 
-// The grouped fold on the pytree path: k_ptrs's plan image and block words (restated, as
-// k_ptrs_clip restates them, so that k_ptrs compiles to the code it always did), one leaf plan
-// for every group. image = in_ptrs[M*L] in member order | out_ptrs[G*L] | leaf_n[L] |
+// The grouped fold on the pytree path: k_ptrs's block words, one leaf plan for every group.
+// image = in_ptrs[M*L] in member order | out_ptrs[G*L] | leaf_n[L] |
 // blocks[2*nblk]; group g's members start at in_ptrs + seg[g]*L, its outputs are
-// out_ptrs[g*L + leaf]. xcd != 0: the XCD remap of k_ptrs (xcd_plan_index) within the slot.
+// out_ptrs[g*L + leaf].
 template <int V, bool NT, bool BURST>
 __global__ __launch_bounds__(kThreads) void k_ptrs_group(const int64_t* __restrict__ img, int L, int64_t M,
                                                          const int* __restrict__ seg,
                                                          const float* __restrict__ wperm,
                                                          const float* __restrict__ gscale,
-                                                         const int* __restrict__ gorder, int G, int do_scale,
-                                                         int xcd) {
+                                                         const int* __restrict__ gorder, int G, int do_scale) {
   constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
   using ACC = AccF;
   const int tid = threadIdx.x;
@@ -1182,7 +1172,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_group(const int64_t* __restri
   const int64_t* leaf_n = img + M * L + (int64_t)G * L;
   const float* w = wperm + gs.m0;
   const float scale = do_scale ? gscale[gs.g] : 1.0f;
-  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t bid = (int64_t)blockIdx.x;
   const int64_t* blk = leaf_n + L + 2 * bid;
   const int64_t be = blk[0];
   const int leaf = (int)((be >> 40) & 0x3fffff);
@@ -1219,62 +1209,26 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_group(const int64_t* __restri
 // differ once a cluster has sat out a round, so their bias corrections and scheduled learning
 // rates do). The descriptor and the state addresses are wave-uniform loads indexed by the
 // slot's group; nothing is written through them but OptEpi::apply's per-element stores.
-// k_dense_group's unit layout, slot order, tables and FromZero start (restated, as k_ptrs_clip
-// restates k_ptrs, so that k_dense_group compiles to the code it always did).
+// k_dense_group's unit layout, slot order, tables and FromZero start.
 // state[4G]: params | m | v | mean address of group g at state[4g ..] (0 where absent). A slot
 // without members, or whose params address is 0, returns at once: nothing of it is read or
 // written.
-__device__ __forceinline__ float* f32_at(int64_t addr, int64_t e) {
-  return addr ? reinterpret_cast<float*>(addr) + e : nullptr;
-}
-
 template <int V, int E, int U, bool NT, bool BURST>
 __global__ __launch_bounds__(kThreads) void k_dense_group_opt(
     const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t nunits, int tail_n, const int* __restrict__ order,
     const int* __restrict__ seg, const float* __restrict__ wperm, const float* __restrict__ gscale,
     const int* __restrict__ gorder, int G, int64_t S, const fjagg_server_opt* __restrict__ opts,
     const int64_t* __restrict__ state) {
-  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
-  const int tid = threadIdx.x;
   GroupSlot gs;
   if (!group_slot(gorder, seg, G, gs)) return;
   const int64_t* st = state + 4 * (int64_t)gs.g;
   if (st[0] == 0) return;
   const OptEpi epi{opts[gs.g], f32_at(st[0], 0), f32_at(st[1], 0), f32_at(st[2], 0), f32_at(st[3], 0)};
   const int* ord = order + gs.m0;
-  const float* w = wperm + gs.m0;
-  const float scale = gscale[gs.g];
   auto row = [=](int64_t j) { return x + (int64_t)ord[j] * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  if (tail_n > 0) {
-    if (b == 0) {
-      if (tid < tail_n) {
-        const int64_t e = nunits * V + tid;
-        const uint32_t off[1] = {(uint32_t)(e * IB)};
-        const bool valid[1] = {true};
-        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false, NoNorm(),
-                                         epi, NoClip(), FromZero());
-      }
-      return;
-    }
-    b -= 1;
-  }
-  const int64_t u_begin = b * S;
-  const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-  for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-    uint32_t off[E];
-    bool valid[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-      int64_t u = g + j * kThreads + tid;
-      valid[j] = u < u_end;
-      if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the epilogue is skipped
-      off[j] = (uint32_t)(u * (V * IB));
-    }
-    fold<IN, AccF, OUT, V, E, U, NT, BURST>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false,
-                                            NoNorm(), epi, NoClip(), FromZero());
-  }
+  dense_walk<FJAGG_F32, FJAGG_F32, V, E, U, NT, BURST, false>(row, gs.n, nunits, tail_n, S, nullptr, wperm + gs.m0,
+                                                              true, gscale[gs.g], false, NoNorm(), epi, NoClip(),
+                                                              FromZero());
 }
 
 // The same on the pytree path: k_ptrs_group's image with out_ptrs[G*L] = the clusters' params
@@ -1286,51 +1240,20 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_group_opt(const int64_t* __re
                                                              const int* __restrict__ seg,
                                                              const float* __restrict__ wperm,
                                                              const float* __restrict__ gscale,
-                                                             const int* __restrict__ gorder, int G, int xcd,
-                                                             const fjagg_server_opt* __restrict__ opts,
+                                                             const int* __restrict__ gorder, int G, const fjagg_server_opt* __restrict__ opts,
                                                              const int64_t* __restrict__ state) {
-  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
-  using ACC = AccF;
-  const int tid = threadIdx.x;
   GroupSlot gs;
   if (!group_slot(gorder, seg, G, gs)) return;
-  const int64_t* in_ptrs = img + gs.m0 * L;
   const int64_t* out_ptrs = img + M * L + (int64_t)gs.g * L;
-  const int64_t* leaf_n = img + M * L + (int64_t)G * L;
   const int64_t* st = state + (int64_t)gs.g * 3 * L;
-  const float* w = wperm + gs.m0;
-  const float scale = gscale[gs.g];
-  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
-  const int64_t* blk = leaf_n + L + 2 * bid;
-  const int64_t be = blk[0];
-  const int leaf = (int)((be >> 40) & 0x3fffff);
-  const bool tail = (be >> 62) & 1;
-  const bool elem = ((uint64_t)be >> 63) != 0;
-  const int64_t u0 = be & ((1ll << 40) - 1);
-  const int64_t u1 = blk[1];
-  const int64_t n = leaf_n[leaf];
-  const int64_t nunits = n / V;
-  // rebased at the workgroup's first element, as in k_ptrs (the epilogue's element index too)
-  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);
-  if (out_ptrs[leaf] == 0) return;
-  const OptEpi epi{opts[gs.g], f32_at(out_ptrs[leaf], e_base), f32_at(st[leaf], e_base),
-                   f32_at(st[L + leaf], e_base), f32_at(st[2 * L + leaf], e_base)};
-  auto row = [=](int64_t j) { return reinterpret_cast<const uint8_t*>(in_ptrs[j * L + leaf]) + e_base * IB; };
-  const uint32_t row_bytes = row_range((n - e_base) * IB);
-  if (tail) {
-    if (tid < n - nunits * V) {
-      const uint32_t off[1] = {(uint32_t)(tid * IB)};
-      const bool valid[1] = {true};
-      fold<IN, ACC, OUT, 1, 1, 8, NT>(row, row_bytes, gs.n, off, nullptr, valid, w, true, scale, false, NoNorm(), epi,
-                                      NoClip(), FromZero());
-    }
-  } else if (V > 1 && elem) {
-    walk_units<IN, ACC, OUT, 1, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, nullptr, w, true, scale, false, NoNorm(),
-                                           epi, NoClip(), FromZero());
-  } else {
-    walk_units<IN, ACC, OUT, V, NT, BURST>(row, row_bytes, gs.n, 0, u1 - u0, nullptr, w, true, scale, false, NoNorm(),
-                                           epi, NoClip(), FromZero());
-  }
+  const int64_t bid = (int64_t)blockIdx.x;
+  const PlanBlock p = plan_block<V>(img + M * L + (int64_t)G * L, L, bid);
+  if (out_ptrs[p.leaf] == 0) return;
+  const OptEpi epi{opts[gs.g], f32_at(out_ptrs[p.leaf], p.e_base), f32_at(st[p.leaf], p.e_base),
+                   f32_at(st[L + p.leaf], p.e_base), f32_at(st[2 * L + p.leaf], p.e_base)};
+  walk_leaf<FJAGG_F32, AccF, FJAGG_F32, V, NT, BURST, false>(p, img + gs.m0 * L, L, gs.n, nullptr, wperm + gs.m0,
+                                                             true, gscale[gs.g], false, NoNorm(), epi, NoClip(),
+                                                             FromZero());
 }
 
 // Pytree path + server optimizer step in the epilogue (fjagg_server_update_ptrs): the
@@ -1341,114 +1264,38 @@ template <int IN, int V, bool NT>
 __global__ __launch_bounds__(kThreads) void k_ptrs_opt(const int64_t* __restrict__ img, int L, int64_t K,
                                                        const float* __restrict__ w, float scale,
                                                        fjagg_server_opt opt, const int64_t* __restrict__ state) {
-  constexpr int IB = Elem<IN>::B;
-  const int tid = threadIdx.x;
-  const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + K * L;
-  const int64_t* leaf_n = out_ptrs + L;
-  const int64_t* blk = leaf_n + L + 2 * (int64_t)blockIdx.x;
-  const int64_t be = blk[0];
-  const int leaf = (int)((be >> 40) & 0x3fffff);
-  const bool tail = (be >> 62) & 1;
-  const bool elem = ((uint64_t)be >> 63) != 0;
-  const int64_t u0 = be & ((1ll << 40) - 1);
-  const int64_t u1 = blk[1];
-  const int64_t n = leaf_n[leaf];
-  const int64_t nunits = n / V;
-  // rebased at the workgroup's first element, as in k_ptrs (the epilogue's element index too)
-  const int64_t e_base = tail ? nunits * V : ((V > 1 && elem) ? u0 : u0 * V);
-  auto at = [=](int64_t p) { return p ? reinterpret_cast<float*>(p) + e_base : nullptr; };
-  const OptEpi epi{opt, at(out_ptrs[leaf]), at(state[leaf]), at(state[L + leaf]), at(state[2 * L + leaf])};
-  auto row = [=](int64_t k) { return reinterpret_cast<const uint8_t*>(in_ptrs[k * L + leaf]) + e_base * IB; };
-  const uint32_t row_bytes = row_range((n - e_base) * IB);
-  if (tail) {
-    if (tid < n - nunits * V) {
-      const uint32_t off[1] = {(uint32_t)(tid * IB)};
-      const bool valid[1] = {true};
-      fold<IN, AccF, FJAGG_F32, 1, 1, 8, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false,
-                                             NoNorm(), epi);
-    }
-    return;
-  }
-  if (V > 1 && elem)
-    walk_units<IN, AccF, FJAGG_F32, 1, NT, true>(row, row_bytes, K, 0, u1 - u0, nullptr, w, true, scale, false,
-                                                 NoNorm(), epi);
-  else
-    walk_units<IN, AccF, FJAGG_F32, V, NT, true>(row, row_bytes, K, 0, u1 - u0, nullptr, w, true, scale, false,
-                                                 NoNorm(), epi);
+  const PlanBlock p = plan_block<V>(out_ptrs + L, L, blockIdx.x);
+  const OptEpi epi{opt, f32_at(out_ptrs[p.leaf], p.e_base), f32_at(state[p.leaf], p.e_base),
+                   f32_at(state[L + p.leaf], p.e_base), f32_at(state[2 * L + p.leaf], p.e_base)};
+  walk_leaf<IN, AccF, FJAGG_F32, V, NT, true, false>(p, img, L, K, nullptr, w, true, scale, false, NoNorm(), epi);
 }
 
 // The clipped fold with the server optimizer step in its epilogue (fjagg_server_update_clip_dense;
-// mime_lite.py:131-149, then :162-167): k_dense_clip's unit layout, grid, tail block, LdsNorm rows
-// and partial rows (restated here rather than shared, so that k_dense_clip and k_dense_opt compile
-// to the code they always did), folding with DevClip and OptEpi together. The clipped mean
-// y = fl(s * scale) stays in registers; only params, moments and (optionally) epi.mean are written.
-// L2: in the tail block every lane joins the per-client wave reductions (k_dense_opt's early
-// return for lanes past tail_n would leave them out); the epilogue skips invalid units.
+// mime_lite.py:131-149, then :162-167): k_dense_clip's grid, LdsNorm rows and partial rows,
+// folding with DevClip and OptEpi together. The clipped mean y = fl(s * scale) stays in registers;
+// only params, moments and (optionally) epi.mean are written; the epilogue skips invalid units.
 template <int V, int E, int U, bool NT, bool L2>
 __global__ __launch_bounds__(kThreads) void k_dense_clip_opt(
     const uint8_t* __restrict__ x, int64_t ld_bytes, int64_t K, int64_t nunits, int tail_n,
     const float* __restrict__ w, const float* __restrict__ c, float scale, int64_t S, OptEpi epi,
     float* __restrict__ ws, const L2Out l2out) {
-  extern __shared__ __attribute__((aligned(16))) float l2lds[];
-  constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
-  const int tid = threadIdx.x;
-  using Norm = typename std::conditional<L2, LdsNorm, NoNorm>::type;
-  Norm nrm{};
-  if constexpr (L2) {
-    for (int64_t i = tid; i < (kThreads / 64) * K; i += kThreads) l2lds[i] = 0.f;
-    __syncthreads();
-    nrm = LdsNorm{l2lds + (tid >> 6) * K};
-  }
-  const DevClip clip{c};
+  const auto nrm = lds_norm<L2>(K);
   auto row = [=](int64_t k) { return x + k * ld_bytes; };
-  const uint32_t row_bytes = (uint32_t)((nunits * V + tail_n) * IB);
-  int64_t b = blockIdx.x;
-  bool is_tail = false;
-  if (tail_n > 0) {
-    if (b == 0) {
-      is_tail = true;
-      const bool active = tid < tail_n;
-      if (L2 || active) {  // with L2 every lane joins the per-client wave reductions
-        const int64_t e = nunits * V + (active ? tid : 0);
-        const uint32_t off[1] = {(uint32_t)(e * IB)};
-        const bool valid[1] = {active};
-        fold<IN, AccF, OUT, 1, 1, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false, nrm, epi,
-                                         clip);
-      }
-    }
-    b -= 1;
-  }
-  if (!is_tail) {
-    const int64_t u_begin = b * S;
-    const int64_t u_end = (u_begin + S < nunits) ? u_begin + S : nunits;
-    for (int64_t g = u_begin; g < u_end; g += (int64_t)kThreads * E) {
-      uint32_t off[E];
-      bool valid[E];
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        int64_t u = g + j * kThreads + tid;
-        valid[j] = u < u_end;
-        if (!valid[j]) u = u_end - 1;  // keep the load in bounds; the epilogue is skipped
-        off[j] = (uint32_t)(u * (V * IB));
-      }
-      fold<IN, AccF, OUT, V, E, U, NT>(row, row_bytes, K, off, nullptr, valid, w, true, scale, false, nrm, epi,
-                                       clip);
-    }
-  }
-  if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
+  dense_walk<FJAGG_F32, FJAGG_F32, V, E, U, NT, true, L2>(row, K, nunits, tail_n, S, nullptr, w, true, scale, false,
+                                                          nrm, epi, DevClip{c});
+  norm_epilogue<L2>(ws, K, l2out, blockIdx.x);
 }
 
 // The same on the pytree path (fjagg_server_update_clip_ptrs): k_ptrs_clip's plan image, block
-// words, XCD remap and unit walk with out_ptrs[L] = the params leaves and state[3L] = m | v | mean
+// words and unit walk with out_ptrs[L] = the params leaves and state[3L] = m | v | mean
 // leaf pointers as k_ptrs_opt lays them out (0 where absent). Each workgroup owns one leaf's unit
 // range, so its OptEpi points at that leaf and indexes it by the element within the range. No
 // workgroup returns before the norm epilogue's barriers.
 template <int V, bool NT, bool L2, bool BURST>
 __global__ __launch_bounds__(kThreads) void k_ptrs_clip_opt(const int64_t* __restrict__ img, int L, int64_t K,
                                                             const float* __restrict__ w,
-                                                            const float* __restrict__ c, float scale, int xcd,
-                                                            fjagg_server_opt opt,
+                                                            const float* __restrict__ c, float scale, fjagg_server_opt opt,
                                                             const int64_t* __restrict__ state,
                                                             float* __restrict__ ws, const L2Out l2out) {
   constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, IB = 4;
@@ -1458,7 +1305,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip_opt(const int64_t* __res
   const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + K * L;
   const int64_t* leaf_n = out_ptrs + L;
-  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t bid = (int64_t)blockIdx.x;
   const int64_t* blk = leaf_n + L + 2 * bid;
   const int64_t be = blk[0];
   const int leaf = (int)((be >> 40) & 0x3fffff);
@@ -1501,9 +1348,8 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip_opt(const int64_t* __res
 }
 
 // The clipped fold with Gaussian noise in its epilogue (fjagg_wsum_clip_noise_dense): the second
-// half of DP-FedAvg onto the clipped mean of k_dense_clip. k_dense_clip's unit layout, grid, tail
-// block, LdsNorm rows and partial rows (restated here rather than shared, so that k_dense_clip
-// compiles to the code it always did), folding with DevClip and NoiseTabEpi. The scale is always
+// half of DP-FedAvg onto the clipped mean of k_dense_clip. k_dense_clip's grid, LdsNorm rows and
+// partial rows, folding with DevClip and NoiseTabEpi. The scale is always
 // applied. The leaf table sits in the kernel arguments; each workgroup first narrows it to the
 // leaves its own element range meets (scalar, once).
 template <int V, int E, int U, bool NT, bool L2>
@@ -1565,8 +1411,8 @@ __global__ __launch_bounds__(kThreads) void k_dense_clip_noise(
   if constexpr (L2) l2_epilogue(l2lds, ws, K, l2out, blockIdx.x);
 }
 
-// The same on the pytree path (fjagg_wsum_clip_noise_ptrs): k_ptrs_clip's plan image, block words,
-// XCD remap and unit walk (restated, as k_ptrs_clip restates k_ptrs). Each workgroup owns one
+// The same on the pytree path (fjagg_wsum_clip_noise_ptrs): k_ptrs_clip's plan image. Each
+// workgroup owns one
 // leaf's unit range, so its NoiseLeafEpi holds that leaf's key and length (leaf_n of the image)
 // and indexes the draw by the element within the leaf. The keys come from the table in the
 // kernel arguments, or from tab_dev (the same entries on the device) when the tree has more
@@ -1574,8 +1420,7 @@ __global__ __launch_bounds__(kThreads) void k_dense_clip_noise(
 template <int V, bool NT, bool L2, bool BURST>
 __global__ __launch_bounds__(kThreads) void k_ptrs_clip_noise(const int64_t* __restrict__ img, int L, int64_t K,
                                                               const float* __restrict__ w,
-                                                              const float* __restrict__ c, float scale, int xcd,
-                                                              float* __restrict__ ws, const L2Out l2out,
+                                                              const float* __restrict__ c, float scale, float* __restrict__ ws, const L2Out l2out,
                                                               float stddev,
                                                               const fjagg_noise_leaf* __restrict__ tab_dev,
                                                               const NoiseTab tab) {
@@ -1586,7 +1431,7 @@ __global__ __launch_bounds__(kThreads) void k_ptrs_clip_noise(const int64_t* __r
   const int64_t* in_ptrs = img;
   const int64_t* out_ptrs = img + K * L;
   const int64_t* leaf_n = out_ptrs + L;
-  const int64_t bid = xcd ? xcd_plan_index(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t bid = (int64_t)blockIdx.x;
   const int64_t* blk = leaf_n + L + 2 * bid;
   const int64_t be = blk[0];
   const int leaf = (int)((be >> 40) & 0x3fffff);
@@ -2348,21 +2193,10 @@ int dense_exact_chunked(int in, int acc, int out, const uint8_t* x, int64_t ld_b
   return FJAGG_OK;
 }
 
-// k_ptrs' XCD-aware plan order (xcd_plan_index), carried in bit 1 of its accumulate argument.
-// FJAGG_XCD_REMAP=1 turns it on (A/B runs).
-inline int xcd_remap_bit() {
-  static const int on = [] {
-    const char* e = getenv("FJAGG_XCD_REMAP");
-    return (e && e[0] == '1') ? 2 : 0;
-  }();
-  return on;
-}
-
 template <int IN, class ACC, int OUT, int V>
 int launch_ptrs_t(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const void* w,
                   float scale, int do_scale, int accumulate, float* ws, L2Out l2, hipStream_t s) {
   const auto* wt = reinterpret_cast<const typename ACC::T*>(w);
-  accumulate = (accumulate ? 1 : 0) | xcd_remap_bit();
   if constexpr (std::is_same<ACC, AccF>::value) {
     if (ws) {  // fused per-client squared l2 norms: block partials, then ordered combine
       if (nblk > cu_count()) l2.done = nullptr;  // combine_last: a grid of one wave of workgroups
@@ -2679,7 +2513,6 @@ int launch_ptrs_karg_n(bool nt, const int64_t* img, int L, int64_t K, int64_t nb
                        int ds, int ac, float* ws, L2Out l2, hipStream_t s) {
   constexpr int IN = FJAGG_F32, OUT = FJAGG_F32, V = 4;
   using ACC = AccF;
-  ac = (ac ? 1 : 0) | xcd_remap_bit();
   KargWords<NW> ki;
   const int64_t nimg = K * L + 2 * (int64_t)L + 2 * nblk;
   std::memcpy(ki.w, img, sizeof(int64_t) * (size_t)nimg);
@@ -3102,77 +2935,111 @@ int clip_flags_check(int in_dtype, int flags, int allowed) {
 }
 
 extern "C++" {
-template <int V, int E, int U, bool NT, bool L2>
-int launch_dense_clip_t(const DenseArgs& a, const float* c, float* ws, int64_t ws_floats, L2Out l2,
+// The launchers shared by the clipped folds (clip, clip + server step, clip + noise). A family F
+// holds the kernel arguments that are its own and names its kernels:
+//   F::kName, F::kNameL2                          check_launch strings
+//   F::kern<V, E, U, NT, L2>()                    dense kernel     F::kern<V, NT, L2, BURST>()  pytree
+//   f.launch(kern, grid, smem, s, a, S, ws, l2)   dense launch     f.launch(kern, grid, smem, s, ws, l2)
+//
+// One dense fold with optional norm rows: LDS allowance, balanced grid from the runtime residency,
+// workspace check, launch, combine (l2.done is null here: the wave rows, k_l2_combine).
+// With L2 the partition of the parameter axis fixes the order the clipped squares are added in,
+// so the grid of every family is sized by k_dense_clip<.., true>'s residency, not its own
+// kernel's: the same partial rows, the same clipped norms bit for bit as fjagg_wsum_clip_dense
+// on the same slab.
+template <class F, int V, int E, int U, bool NT, bool L2>
+int launch_dense_fold_t(const F& f, const DenseArgs& a, float* ws, int64_t ws_floats, const L2Out& l2,
                         hipStream_t s) {
-  auto kern = k_dense_clip<V, E, U, NT, L2>;
-  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
+  auto kern = F::template kern<V, E, U, NT, L2>();
+  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;
   if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  const void* sized_by = L2 ? reinterpret_cast<const void*>(k_dense_clip<V, E, U, NT, true>)
+                            : reinterpret_cast<const void*>(kern);
   int64_t S = (int64_t)kThreads * E, nblk = 0;
-  balanced_grid(residency(reinterpret_cast<const void*>(kern), smem), a.nunits, (int64_t)kThreads * E, 1, &S,
-                &nblk);
+  balanced_grid(residency(sized_by, smem), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
   if (a.nunits == 0) nblk = 0;
   const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
   if (L2 && grid * a.K > ws_floats)
     return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
                 (long long)a.K);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
-                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, a.do_scale, a.accumulate, a.out, S,
-                     ws, l2);
-  if (int rc = check_launch("k_dense_clip")) return rc;
+  f.launch(kern, dim3((unsigned)grid), smem, s, a, S, ws, l2);
+  if (int rc = check_launch(F::kName)) return rc;
   return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
 }
 
 // the shapes of launch_dense_l2_io: E=8 x U=4 where pick_variant says so, else E=1 x U=8
-template <bool L2>
-int launch_dense_clip(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, float* ws,
-                      int64_t ws_floats, L2Out l2, hipStream_t s) {
+template <bool L2, class F>
+int launch_dense_fold(const F& f, bool vec, bool nt, int variant, const DenseArgs& a, float* ws, int64_t ws_floats,
+                      const L2Out& l2, hipStream_t s) {
   if (!vec)
-    return nt ? launch_dense_clip_t<1, 1, 8, true, L2>(a, c, ws, ws_floats, l2, s)
-              : launch_dense_clip_t<1, 1, 8, false, L2>(a, c, ws, ws_floats, l2, s);
+    return nt ? launch_dense_fold_t<F, 1, 1, 8, true, L2>(f, a, ws, ws_floats, l2, s)
+              : launch_dense_fold_t<F, 1, 1, 8, false, L2>(f, a, ws, ws_floats, l2, s);
   if (variant == 12)
-    return nt ? launch_dense_clip_t<4, 8, 4, true, L2>(a, c, ws, ws_floats, l2, s)
-              : launch_dense_clip_t<4, 8, 4, false, L2>(a, c, ws, ws_floats, l2, s);
-  return nt ? launch_dense_clip_t<4, 1, 8, true, L2>(a, c, ws, ws_floats, l2, s)
-            : launch_dense_clip_t<4, 1, 8, false, L2>(a, c, ws, ws_floats, l2, s);
+    return nt ? launch_dense_fold_t<F, 4, 8, 4, true, L2>(f, a, ws, ws_floats, l2, s)
+              : launch_dense_fold_t<F, 4, 8, 4, false, L2>(f, a, ws, ws_floats, l2, s);
+  return nt ? launch_dense_fold_t<F, 4, 1, 8, true, L2>(f, a, ws, ws_floats, l2, s)
+            : launch_dense_fold_t<F, 4, 1, 8, false, L2>(f, a, ws, ws_floats, l2, s);
 }
 
-template <int V, bool L2>
-int launch_ptrs_clip(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w, const float* c,
-                     float scale, int ds, int ac, float* ws, L2Out l2, hipStream_t s) {
-  const dim3 grid((unsigned)nblk), block(kThreads);
-  ac = (ac ? 1 : 0) | xcd_remap_bit();
+// One pytree fold over a plan of nblk entries. With norms always the burst schedule (and ws, l2
+// set); without, launch_ptrs_t's rule: interleaved once the plan has two workgroups per CU.
+template <class F, int V, bool NT, bool L2, bool BURST>
+int launch_ptrs_fold_t(const F& f, int64_t K, int64_t nblk, float* ws, const L2Out& l2, hipStream_t s) {
+  auto kern = F::template kern<V, NT, L2, BURST>();
+  const size_t smem = L2 ? l2_smem(K, l2) : 0;
+  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  f.launch(kern, dim3((unsigned)nblk), smem, s, ws, l2);
+  if (int rc = check_launch(L2 ? F::kNameL2 : F::kName)) return rc;
+  return L2 ? launch_l2_combine(ws, nblk, K, l2, s) : FJAGG_OK;
+}
+template <int V, bool L2, class F>
+int launch_ptrs_fold_v(const F& f, bool nt, int64_t K, int64_t nblk, float* ws, const L2Out& l2, hipStream_t s) {
   if constexpr (L2) {
-    const size_t smem = l2_smem(K, l2);
-    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip<V, true, true, true>)
-                        : reinterpret_cast<const void*>(k_ptrs_clip<V, false, true, true>);
-    if (int rc = allow_lds(kf, smem)) return rc;
-    if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, ds, ac, ws,
-                         l2);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, ds, ac,
-                         ws, l2);
-    if (int rc = check_launch("k_ptrs_clip (l2)")) return rc;
-    return launch_l2_combine(ws, nblk, K, l2, s);
+    return nt ? launch_ptrs_fold_t<F, V, true, true, true>(f, K, nblk, ws, l2, s)
+              : launch_ptrs_fold_t<F, V, false, true, true>(f, K, nblk, ws, l2, s);
   } else {
-    // the schedule rule of launch_ptrs_t
     const bool burst = nblk < 2 * (int64_t)cu_count();
-    if (nt && burst)
-      hipLaunchKernelGGL((k_ptrs_clip<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
-                         nullptr, l2);
-    else if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
-                         nullptr, l2);
-    else if (burst)
-      hipLaunchKernelGGL((k_ptrs_clip<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
-                         nullptr, l2);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, ds, ac,
-                         nullptr, l2);
-    return check_launch("k_ptrs_clip");
+    if (nt)
+      return burst ? launch_ptrs_fold_t<F, V, true, false, true>(f, K, nblk, nullptr, l2, s)
+                   : launch_ptrs_fold_t<F, V, true, false, false>(f, K, nblk, nullptr, l2, s);
+    return burst ? launch_ptrs_fold_t<F, V, false, false, true>(f, K, nblk, nullptr, l2, s)
+                 : launch_ptrs_fold_t<F, V, false, false, false>(f, K, nblk, nullptr, l2, s);
   }
 }
+template <bool L2, class F>
+int launch_ptrs_fold(const F& f, bool vec, bool nt, int64_t K, int64_t nblk, float* ws, const L2Out& l2,
+                     hipStream_t s) {
+  if (!vec) return launch_ptrs_fold_v<1, L2>(f, nt, K, nblk, ws, l2, s);
+  return launch_ptrs_fold_v<4, L2>(f, nt, K, nblk, ws, l2, s);
+}
+
+struct ClipDense {
+  const float* c;
+  static constexpr const char* kName = "k_dense_clip";
+  template <int V, int E, int U, bool NT, bool L2>
+  static auto kern() { return k_dense_clip<V, E, U, NT, L2>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, const DenseArgs& a, int64_t S, float* ws,
+              const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits, a.tail_n,
+                       reinterpret_cast<const float*>(a.w), c, a.scale, a.do_scale, a.accumulate, a.out, S, ws, l2);
+  }
+};
+struct ClipPtrs {
+  const int64_t* img;
+  int L;
+  int64_t K;
+  const float *w, *c;
+  float scale;
+  int ds, ac;
+  static constexpr const char *kName = "k_ptrs_clip", *kNameL2 = "k_ptrs_clip (l2)";
+  template <int V, bool NT, bool L2, bool BURST>
+  static auto kern() { return k_ptrs_clip<V, NT, L2, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, float* ws, const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, img, L, K, w, c, scale, ds, ac, ws, l2);
+  }
+};
 }  // extern "C++"
 }  // namespace
 
@@ -3239,10 +3106,11 @@ int fjagg_wsum_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K
   const int variant = pick_variant(a.nunits, K);
   const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const ClipDense f{c_dev};
   if (l2sq_clipped_dev)
-    return launch_dense_clip<true>(vec, nt, variant, a, c_dev, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
+    return launch_dense_fold<true>(f, vec, nt, variant, a, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
                                    L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
-  return launch_dense_clip<false>(vec, nt, variant, a, c_dev, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr}, s);
+  return launch_dense_fold<false>(f, vec, nt, variant, a, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
@@ -3263,95 +3131,45 @@ int fjagg_wsum_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
   const int ds = (flags & FJAGG_SCALE) ? 1 : 0, ac = (flags & FJAGG_ACCUMULATE) ? 1 : 0;
-  float* ws = reinterpret_cast<float*>(ws_dev);
-  if (l2sq_clipped_dev) {
-    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
-    return vec ? launch_ptrs_clip<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, ws, l2, s)
-               : launch_ptrs_clip<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, ws, l2, s);
-  }
-  const L2Out l2{nullptr, nullptr, 0, nullptr};
-  return vec ? launch_ptrs_clip<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s)
-             : launch_ptrs_clip<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ds, ac, nullptr, l2, s);
+  const ClipPtrs f{image_dev, L, K, w_dev, c_dev, scale, ds, ac};
+  if (l2sq_clipped_dev)
+    return launch_ptrs_fold<true>(f, vec, nt, K, nblk, reinterpret_cast<float*>(ws_dev),
+                                  L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_ptrs_fold<false>(f, vec, nt, K, nblk, nullptr, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 // ------------------------- clipped weighted mean + server step in the fold's epilogue (fjagg.h)
 namespace {
 extern "C++" {
-template <int V, int E, int U, bool NT, bool L2>
-int launch_dense_clip_opt_t(const DenseArgs& a, const float* c, const OptEpi& epi, float* ws, int64_t ws_floats,
-                            L2Out l2, hipStream_t s) {
-  auto kern = k_dense_clip_opt<V, E, U, NT, L2>;
-  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
-  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
-  // With L2 the partition of the parameter axis fixes the order the clipped squares are added
-  // in, so the grid is sized by k_dense_clip's residency, not this kernel's: the same partial
-  // rows, the same clipped norms bit for bit as fjagg_wsum_clip_dense on the same slab.
-  const void* sized_by = L2 ? reinterpret_cast<const void*>(k_dense_clip<V, E, U, NT, true>)
-                            : reinterpret_cast<const void*>(kern);
-  int64_t S = (int64_t)kThreads * E, nblk = 0;
-  balanced_grid(residency(sized_by, smem), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
-  if (a.nunits == 0) nblk = 0;
-  const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
-  if (L2 && grid * a.K > ws_floats)
-    return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
-                (long long)a.K);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
-                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, S, epi, ws, l2);
-  if (int rc = check_launch("k_dense_clip_opt")) return rc;
-  return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
-}
-
-// the shapes of launch_dense_clip: E=8 x U=4 where pick_variant says so, else E=1 x U=8
-template <bool L2>
-int launch_dense_clip_opt(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, const OptEpi& epi,
-                          float* ws, int64_t ws_floats, L2Out l2, hipStream_t s) {
-  if (!vec)
-    return nt ? launch_dense_clip_opt_t<1, 1, 8, true, L2>(a, c, epi, ws, ws_floats, l2, s)
-              : launch_dense_clip_opt_t<1, 1, 8, false, L2>(a, c, epi, ws, ws_floats, l2, s);
-  if (variant == 12)
-    return nt ? launch_dense_clip_opt_t<4, 8, 4, true, L2>(a, c, epi, ws, ws_floats, l2, s)
-              : launch_dense_clip_opt_t<4, 8, 4, false, L2>(a, c, epi, ws, ws_floats, l2, s);
-  return nt ? launch_dense_clip_opt_t<4, 1, 8, true, L2>(a, c, epi, ws, ws_floats, l2, s)
-            : launch_dense_clip_opt_t<4, 1, 8, false, L2>(a, c, epi, ws, ws_floats, l2, s);
-}
-
-// launch_ptrs_clip's rule: with norms always the burst schedule, else launch_ptrs_t's
-template <int V, bool L2>
-int launch_ptrs_clip_opt(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w, const float* c,
-                         float scale, const fjagg_server_opt& opt, const int64_t* state, float* ws, L2Out l2,
-                         hipStream_t s) {
-  const dim3 grid((unsigned)nblk), block(kThreads);
-  const int xcd = xcd_remap_bit() ? 1 : 0;
-  if constexpr (L2) {
-    const size_t smem = l2_smem(K, l2);
-    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip_opt<V, true, true, true>)
-                        : reinterpret_cast<const void*>(k_ptrs_clip_opt<V, false, true, true>);
-    if (int rc = allow_lds(kf, smem)) return rc;
-    if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
-                         opt, state, ws, l2);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
-                         opt, state, ws, l2);
-    if (int rc = check_launch("k_ptrs_clip_opt (l2)")) return rc;
-    return launch_l2_combine(ws, nblk, K, l2, s);
-  } else {
-    const bool burst = nblk < 2 * (int64_t)cu_count();
-    if (nt && burst)
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd, opt,
-                         state, nullptr, l2);
-    else if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         opt, state, nullptr, l2);
-    else if (burst)
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         opt, state, nullptr, l2);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip_opt<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         opt, state, nullptr, l2);
-    return check_launch("k_ptrs_clip_opt");
+struct ClipOptDense {
+  const float* c;
+  OptEpi epi;
+  static constexpr const char* kName = "k_dense_clip_opt";
+  template <int V, int E, int U, bool NT, bool L2>
+  static auto kern() { return k_dense_clip_opt<V, E, U, NT, L2>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, const DenseArgs& a, int64_t S, float* ws,
+              const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits, a.tail_n,
+                       reinterpret_cast<const float*>(a.w), c, a.scale, S, epi, ws, l2);
   }
-}
+};
+struct ClipOptPtrs {
+  const int64_t* img;
+  int L;
+  int64_t K;
+  const float *w, *c;
+  float scale;
+  fjagg_server_opt opt;
+  const int64_t* state;
+  static constexpr const char *kName = "k_ptrs_clip_opt", *kNameL2 = "k_ptrs_clip_opt (l2)";
+  template <int V, bool NT, bool L2, bool BURST>
+  static auto kern() { return k_ptrs_clip_opt<V, NT, L2, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, float* ws, const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, img, L, K, w, c, scale, opt, state, ws, l2);
+  }
+};
 }  // extern "C++"
 }  // namespace
 
@@ -3398,11 +3216,11 @@ int fjagg_server_update_clip_dense(int in_dtype, const void* x_dev, int64_t ld, 
   const int variant = pick_variant(a.nunits, K);
   const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const ClipOptDense f{c_dev, epi};
   if (l2sq_clipped_dev)
-    return launch_dense_clip_opt<true>(vec, nt, variant, a, c_dev, epi, reinterpret_cast<float*>(ws_dev),
-                                       ws_bytes / 4, L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
-  return launch_dense_clip_opt<false>(vec, nt, variant, a, c_dev, epi, nullptr, 0,
-                                      L2Out{nullptr, nullptr, 0, nullptr}, s);
+    return launch_dense_fold<true>(f, vec, nt, variant, a, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
+                                   L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_dense_fold<false>(f, vec, nt, variant, a, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
@@ -3425,19 +3243,11 @@ int fjagg_server_update_clip_ptrs(int in_dtype, const int64_t* image_dev, int L,
                 (long long)fjagg_wsum_clip_ptrs_workspace_bytes(K, nblk));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
-  float* ws = reinterpret_cast<float*>(ws_dev);
-  if (l2sq_clipped_dev) {
-    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
-    return vec ? launch_ptrs_clip_opt<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev, ws,
-                                               l2, s)
-               : launch_ptrs_clip_opt<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev, ws,
-                                               l2, s);
-  }
-  const L2Out l2{nullptr, nullptr, 0, nullptr};
-  return vec ? launch_ptrs_clip_opt<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev,
-                                              nullptr, l2, s)
-             : launch_ptrs_clip_opt<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, *opt, state_dev,
-                                              nullptr, l2, s);
+  const ClipOptPtrs f{image_dev, L, K, w_dev, c_dev, scale, *opt, state_dev};
+  if (l2sq_clipped_dev)
+    return launch_ptrs_fold<true>(f, vec, nt, K, nblk, reinterpret_cast<float*>(ws_dev),
+                                  L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_ptrs_fold<false>(f, vec, nt, K, nblk, nullptr, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 // ------------------------- clipped weighted mean + Gaussian noise in the fold's epilogue (fjagg.h)
@@ -3474,80 +3284,38 @@ int noise_check(const fjagg_noise* nz, int64_t P, bool dense, NoiseTab* tab) {
 }
 
 extern "C++" {
-template <int V, int E, int U, bool NT, bool L2>
-int launch_dense_clip_noise_t(const DenseArgs& a, const float* c, float* ws, int64_t ws_floats, L2Out l2,
-                              float stddev, int NL, const NoiseTab& tab, hipStream_t s) {
-  auto kern = k_dense_clip_noise<V, E, U, NT, L2>;
-  const size_t smem = L2 ? l2_smem(a.K, l2) : 0;  // l2.done is null: the wave rows
-  if (int rc = allow_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
-  // the grid of k_dense_clip (launch_dense_clip_opt_t's rule): the same partial rows, the same
-  // clipped norms bit for bit as fjagg_wsum_clip_dense on the same slab
-  const void* sized_by = L2 ? reinterpret_cast<const void*>(k_dense_clip<V, E, U, NT, true>)
-                            : reinterpret_cast<const void*>(kern);
-  int64_t S = (int64_t)kThreads * E, nblk = 0;
-  balanced_grid(residency(sized_by, smem), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
-  if (a.nunits == 0) nblk = 0;
-  const int64_t grid = nblk + (a.tail_n > 0 ? 1 : 0);
-  if (L2 && grid * a.K > ws_floats)
-    return fail(FJAGG_EINVAL, "clip workspace too small (%lld workgroups x %lld clients)", (long long)grid,
-                (long long)a.K);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits,
-                     a.tail_n, reinterpret_cast<const float*>(a.w), c, a.scale, a.out, S, ws, l2, stddev, NL, tab);
-  if (int rc = check_launch("k_dense_clip_noise")) return rc;
-  return L2 ? launch_l2_combine(ws, grid, a.K, l2, s) : FJAGG_OK;
-}
-
-// the shapes of launch_dense_clip: E=8 x U=4 where pick_variant says so, else E=1 x U=8
-template <bool L2>
-int launch_dense_clip_noise(bool vec, bool nt, int variant, const DenseArgs& a, const float* c, float* ws,
-                            int64_t ws_floats, L2Out l2, float sd, int NL, const NoiseTab& tab, hipStream_t s) {
-  if (!vec)
-    return nt ? launch_dense_clip_noise_t<1, 1, 8, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
-              : launch_dense_clip_noise_t<1, 1, 8, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
-  if (variant == 12)
-    return nt ? launch_dense_clip_noise_t<4, 8, 4, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
-              : launch_dense_clip_noise_t<4, 8, 4, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
-  return nt ? launch_dense_clip_noise_t<4, 1, 8, true, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s)
-            : launch_dense_clip_noise_t<4, 1, 8, false, L2>(a, c, ws, ws_floats, l2, sd, NL, tab, s);
-}
-
-// launch_ptrs_clip's rule: with norms always the burst schedule, else launch_ptrs_t's
-template <int V, bool L2>
-int launch_ptrs_clip_noise(bool nt, const int64_t* img, int L, int64_t K, int64_t nblk, const float* w,
-                           const float* c, float scale, float* ws, L2Out l2, float sd,
-                           const fjagg_noise_leaf* tab_dev, const NoiseTab& tab, hipStream_t s) {
-  const dim3 grid((unsigned)nblk), block(kThreads);
-  const int xcd = xcd_remap_bit() ? 1 : 0;
-  if constexpr (L2) {
-    const size_t smem = l2_smem(K, l2);
-    const void* kf = nt ? reinterpret_cast<const void*>(k_ptrs_clip_noise<V, true, true, true>)
-                        : reinterpret_cast<const void*>(k_ptrs_clip_noise<V, false, true, true>);
-    if (int rc = allow_lds(kf, smem)) return rc;
-    if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
-                         ws, l2, sd, tab_dev, tab);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, true, true>), grid, block, smem, s, img, L, K, w, c, scale, xcd,
-                         ws, l2, sd, tab_dev, tab);
-    if (int rc = check_launch("k_ptrs_clip_noise (l2)")) return rc;
-    return launch_l2_combine(ws, nblk, K, l2, s);
-  } else {
-    const bool burst = nblk < 2 * (int64_t)cu_count();
-    if (nt && burst)
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         nullptr, l2, sd, tab_dev, tab);
-    else if (nt)
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, true, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         nullptr, l2, sd, tab_dev, tab);
-    else if (burst)
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, false, true>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         nullptr, l2, sd, tab_dev, tab);
-    else
-      hipLaunchKernelGGL((k_ptrs_clip_noise<V, false, false, false>), grid, block, 0, s, img, L, K, w, c, scale, xcd,
-                         nullptr, l2, sd, tab_dev, tab);
-    return check_launch("k_ptrs_clip_noise");
+struct ClipNoiseDense {
+  const float* c;
+  float stddev;
+  int NL;
+  const NoiseTab& tab;
+  static constexpr const char* kName = "k_dense_clip_noise";
+  template <int V, int E, int U, bool NT, bool L2>
+  static auto kern() { return k_dense_clip_noise<V, E, U, NT, L2>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, const DenseArgs& a, int64_t S, float* ws,
+              const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, a.x, a.ld_bytes, a.K, a.nunits, a.tail_n,
+                       reinterpret_cast<const float*>(a.w), c, a.scale, a.out, S, ws, l2, stddev, NL, tab);
   }
-}
+};
+struct ClipNoisePtrs {
+  const int64_t* img;
+  int L;
+  int64_t K;
+  const float *w, *c;
+  float scale, stddev;
+  const fjagg_noise_leaf* tab_dev;
+  const NoiseTab& tab;
+  static constexpr const char *kName = "k_ptrs_clip_noise", *kNameL2 = "k_ptrs_clip_noise (l2)";
+  template <int V, bool NT, bool L2, bool BURST>
+  static auto kern() { return k_ptrs_clip_noise<V, NT, L2, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, size_t smem, hipStream_t s, float* ws, const L2Out& l2) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), smem, s, img, L, K, w, c, scale, ws, l2, stddev, tab_dev,
+                       tab);
+  }
+};
 }  // extern "C++"
 }  // namespace
 
@@ -3591,12 +3359,11 @@ int fjagg_wsum_clip_noise_dense(int in_dtype, const void* x_dev, int64_t ld, int
   const int variant = pick_variant(a.nunits, K);
   const bool nt = (flags & FJAGG_NONTEMPORAL) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const ClipNoiseDense f{c_dev, noise->stddev, noise->L, tab};
   if (l2sq_clipped_dev)
-    return launch_dense_clip_noise<true>(vec, nt, variant, a, c_dev, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
-                                         L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, noise->stddev, noise->L, tab,
-                                         s);
-  return launch_dense_clip_noise<false>(vec, nt, variant, a, c_dev, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr},
-                                        noise->stddev, noise->L, tab, s);
+    return launch_dense_fold<true>(f, vec, nt, variant, a, reinterpret_cast<float*>(ws_dev), ws_bytes / 4,
+                                   L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_dense_fold<false>(f, vec, nt, variant, a, nullptr, 0, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 int fjagg_wsum_clip_noise_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
@@ -3620,20 +3387,11 @@ int fjagg_wsum_clip_noise_ptrs(int in_dtype, const int64_t* image_dev, int L, in
   const fjagg_noise_leaf* tab_dev = L > FJAGG_NOISE_MAX_LEAVES ? noise->leaves_dev : nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
-  float* ws = reinterpret_cast<float*>(ws_dev);
-  const float sd = noise->stddev;
-  if (l2sq_clipped_dev) {
-    const L2Out l2{l2sq_clipped_dev, nullptr, 0, nullptr};
-    return vec ? launch_ptrs_clip_noise<4, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ws, l2, sd, tab_dev,
-                                                 tab, s)
-               : launch_ptrs_clip_noise<1, true>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, ws, l2, sd, tab_dev,
-                                                 tab, s);
-  }
-  const L2Out l2{nullptr, nullptr, 0, nullptr};
-  return vec ? launch_ptrs_clip_noise<4, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, nullptr, l2, sd,
-                                                tab_dev, tab, s)
-             : launch_ptrs_clip_noise<1, false>(nt, image_dev, L, K, nblk, w_dev, c_dev, scale, nullptr, l2, sd,
-                                                tab_dev, tab, s);
+  const ClipNoisePtrs f{image_dev, L, K, w_dev, c_dev, scale, noise->stddev, tab_dev, tab};
+  if (l2sq_clipped_dev)
+    return launch_ptrs_fold<true>(f, vec, nt, K, nblk, reinterpret_cast<float*>(ws_dev),
+                                  L2Out{l2sq_clipped_dev, nullptr, 0, nullptr}, s);
+  return launch_ptrs_fold<false>(f, vec, nt, K, nblk, nullptr, L2Out{nullptr, nullptr, 0, nullptr}, s);
 }
 
 // ------------------------------------------------- grouped weighted mean (fjagg.h)
@@ -3715,47 +3473,87 @@ int group_dense_shape(const void* x, int64_t ld, int64_t P, int64_t M, int64_t n
 }
 
 extern "C++" {
+// The launchers shared by the grouped fold and the grouped fold + server step; families as for
+// the clipped folds (launch_dense_fold_t), with kern<V, E, U, NT, BURST>() / kern<V, NT, BURST>().
+//
 // The balanced grid of ONE group over the whole chip (S units per workgroup), times G slots: the
 // largest group's workgroups are dispatched first (gorder) and fill every CU; the shorter groups'
 // workgroups take the CUs as they free up.
-template <int V, int E, int U, bool NT, bool BURST>
-int launch_dense_group_t(const GroupArgs& a, hipStream_t s) {
-  auto kern = k_dense_group<V, E, U, NT, BURST>;
+template <class F, int V, int E, int U, bool NT, bool BURST>
+int launch_dense_group_t(const F& f, const GroupArgs& a, hipStream_t s) {
+  auto kern = F::template kern<V, E, U, NT, BURST>();
   int64_t S = (int64_t)kThreads * E, nblk = 0;
   balanced_grid(residency(reinterpret_cast<const void*>(kern)), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
   if (a.nunits == 0) nblk = 0;
-  const dim3 grid((unsigned)(nblk + (a.tail_n > 0 ? 1 : 0)), (unsigned)a.G);
-  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
-                     a.gscale, a.gorder, a.G, a.do_scale, a.out, a.out_stride, S);
-  return check_launch("k_dense_group");
+  f.launch(kern, dim3((unsigned)(nblk + (a.tail_n > 0 ? 1 : 0)), (unsigned)a.G), s, a, S);
+  return check_launch(F::kName);
 }
 
-template <bool NT>
-int launch_dense_group(bool vec, int variant, const GroupArgs& a, hipStream_t s) {
-  if (!vec) return launch_dense_group_t<1, 1, 8, NT, false>(a, s);
+template <bool NT, class F>
+int launch_dense_group(const F& f, bool vec, int variant, const GroupArgs& a, hipStream_t s) {
+  if (!vec) return launch_dense_group_t<F, 1, 1, 8, NT, false>(f, a, s);
   if (variant == 12) {
     // the schedule rule of k_dense's E=8 shape, over every slot's tiles
     const int64_t ntiles = (a.nunits + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
-    if (ntiles * a.nonempty >= 2 * (int64_t)cu_count()) return launch_dense_group_t<4, 8, 4, NT, false>(a, s);
-    return launch_dense_group_t<4, 8, 4, NT, true>(a, s);
+    if (ntiles * a.nonempty >= 2 * (int64_t)cu_count()) return launch_dense_group_t<F, 4, 8, 4, NT, false>(f, a, s);
+    return launch_dense_group_t<F, 4, 8, 4, NT, true>(f, a, s);
   }
-  if (variant == 5) return launch_dense_group_t<4, 4, 4, NT, false>(a, s);
-  return launch_dense_group_t<4, 1, 8, NT, false>(a, s);
+  if (variant == 5) return launch_dense_group_t<F, 4, 4, 4, NT, false>(f, a, s);
+  return launch_dense_group_t<F, 4, 1, 8, NT, false>(f, a, s);
 }
 
-template <int V, bool NT>
-int launch_ptrs_group(const int64_t* img, int L, int64_t M, int64_t nblk, const int32_t* seg, const float* wperm,
-                      const float* gscale, const int32_t* gorder, int G, int ds, int64_t nonempty, hipStream_t s) {
-  const dim3 grid((unsigned)nblk, (unsigned)G), block(kThreads);
-  const int xcd = xcd_remap_bit() ? 1 : 0;
-  if (nblk * nonempty < 2 * (int64_t)cu_count())  // the schedule rule of launch_ptrs_t
-    hipLaunchKernelGGL((k_ptrs_group<V, NT, true>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G, ds,
-                       xcd);
+// the pytree plan of nblk entries times G slots; the schedule rule of launch_ptrs_t over every
+// non-empty slot's workgroups
+template <class F, int V, bool NT>
+int launch_ptrs_group_t(const F& f, int64_t nblk, int G, int64_t nonempty, hipStream_t s) {
+  const dim3 grid((unsigned)nblk, (unsigned)G);
+  if (nblk * nonempty < 2 * (int64_t)cu_count())
+    f.launch(F::template kern<V, NT, true>(), grid, s);
   else
-    hipLaunchKernelGGL((k_ptrs_group<V, NT, false>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G, ds,
-                       xcd);
-  return check_launch("k_ptrs_group");
+    f.launch(F::template kern<V, NT, false>(), grid, s);
+  return check_launch(F::kName);
 }
+template <class F>
+int launch_ptrs_group(const F& f, bool vec, bool nt, int64_t nblk, int G, int64_t nonempty, hipStream_t s) {
+  if (vec)
+    return nt ? launch_ptrs_group_t<F, 4, true>(f, nblk, G, nonempty, s)
+              : launch_ptrs_group_t<F, 4, false>(f, nblk, G, nonempty, s);
+  return nt ? launch_ptrs_group_t<F, 1, true>(f, nblk, G, nonempty, s)
+            : launch_ptrs_group_t<F, 1, false>(f, nblk, G, nonempty, s);
+}
+
+// the member-order tables of a grouped pytree fold (k_ptrs_group)
+struct GroupPtrsArgs {
+  const int64_t* img;
+  int L;
+  int64_t M;
+  const int32_t* seg;
+  const float *wperm, *gscale;
+  const int32_t* gorder;
+  int G;
+};
+
+struct GroupDense {
+  static constexpr const char* kName = "k_dense_group";
+  template <int V, int E, int U, bool NT, bool BURST>
+  static auto kern() { return k_dense_group<V, E, U, NT, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, hipStream_t s, const GroupArgs& a, int64_t S) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
+                       a.gscale, a.gorder, a.G, a.do_scale, a.out, a.out_stride, S);
+  }
+};
+struct GroupPtrs {
+  GroupPtrsArgs p;
+  int ds;
+  static constexpr const char* kName = "k_ptrs_group";
+  template <int V, bool NT, bool BURST>
+  static auto kern() { return k_ptrs_group<V, NT, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, p.img, p.L, p.M, p.seg, p.wperm, p.gscale, p.gorder, p.G, ds);
+  }
+};
 }  // extern "C++"
 }  // namespace
 
@@ -3795,8 +3593,8 @@ int fjagg_wsum_group_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t 
   a.out_stride = out_ld * 4;
   a.nonempty = nonempty;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group<true>(vec, variant, a, s)
-                                     : launch_dense_group<false>(vec, variant, a, s);
+  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group<true>(GroupDense{}, vec, variant, a, s)
+                                     : launch_dense_group<false>(GroupDense{}, vec, variant, a, s);
 }
 
 /* the kernel shape fjagg_wsum_group_dense picks for these arguments (fjagg.h); launches nothing */
@@ -3823,16 +3621,9 @@ int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t
     return fail(FJAGG_EINVAL, "null pointer argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
-  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, g = (int)G;
-  if (vec)
-    return nt ? launch_ptrs_group<4, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
-                                           nonempty, s)
-              : launch_ptrs_group<4, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
-                                            nonempty, s);
-  return nt ? launch_ptrs_group<1, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
-                                         nonempty, s)
-            : launch_ptrs_group<1, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g, ds,
-                                          nonempty, s);
+  const GroupPtrs f{{image_dev, L, M, seg_dev, wperm_dev, gscale_dev, gorder_dev, (int)G},
+                    (flags & FJAGG_SCALE) ? 1 : 0};
+  return launch_ptrs_group(f, vec, nt, nblk, (int)G, nonempty, s);
 }
 
 // ------------------------- grouped fold + per-cluster server step (fjagg.h; hyp_cluster.py:107-128)
@@ -3859,49 +3650,31 @@ int group_opt_check(int64_t G, const int32_t* seg_host, const fjagg_server_opt* 
   return FJAGG_OK;
 }
 
-// launch_dense_group_t's grid: the balanced grid of one group times G slots
-template <int V, int E, int U, bool NT, bool BURST>
-int launch_dense_group_opt_t(const GroupArgs& a, const fjagg_server_opt* opts, const int64_t* state, hipStream_t s) {
-  auto kern = k_dense_group_opt<V, E, U, NT, BURST>;
-  int64_t S = (int64_t)kThreads * E, nblk = 0;
-  balanced_grid(residency(reinterpret_cast<const void*>(kern)), a.nunits, (int64_t)kThreads * E, 1, &S, &nblk);
-  if (a.nunits == 0) nblk = 0;
-  const dim3 grid((unsigned)(nblk + (a.tail_n > 0 ? 1 : 0)), (unsigned)a.G);
-  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
-                     a.gscale, a.gorder, a.G, S, opts, state);
-  return check_launch("k_dense_group_opt");
-}
-
-// launch_dense_group's shapes and E=8 schedule rule
-template <bool NT>
-int launch_dense_group_opt(bool vec, int variant, const GroupArgs& a, const fjagg_server_opt* opts,
-                           const int64_t* state, hipStream_t s) {
-  if (!vec) return launch_dense_group_opt_t<1, 1, 8, NT, false>(a, opts, state, s);
-  if (variant == 12) {
-    const int64_t ntiles = (a.nunits + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
-    if (ntiles * a.nonempty >= 2 * (int64_t)cu_count())
-      return launch_dense_group_opt_t<4, 8, 4, NT, false>(a, opts, state, s);
-    return launch_dense_group_opt_t<4, 8, 4, NT, true>(a, opts, state, s);
+struct GroupOptDense {
+  const fjagg_server_opt* opts;
+  const int64_t* state;
+  static constexpr const char* kName = "k_dense_group_opt";
+  template <int V, int E, int U, bool NT, bool BURST>
+  static auto kern() { return k_dense_group_opt<V, E, U, NT, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, hipStream_t s, const GroupArgs& a, int64_t S) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a.x, a.ld_bytes, a.nunits, a.tail_n, a.order, a.seg, a.wperm,
+                       a.gscale, a.gorder, a.G, S, opts, state);
   }
-  if (variant == 5) return launch_dense_group_opt_t<4, 4, 4, NT, false>(a, opts, state, s);
-  return launch_dense_group_opt_t<4, 1, 8, NT, false>(a, opts, state, s);
-}
-
-// launch_ptrs_group's schedule rule
-template <int V, bool NT>
-int launch_ptrs_group_opt(const int64_t* img, int L, int64_t M, int64_t nblk, const int32_t* seg, const float* wperm,
-                          const float* gscale, const int32_t* gorder, int G, int64_t nonempty,
-                          const fjagg_server_opt* opts, const int64_t* state, hipStream_t s) {
-  const dim3 grid((unsigned)nblk, (unsigned)G), block(kThreads);
-  const int xcd = xcd_remap_bit() ? 1 : 0;
-  if (nblk * nonempty < 2 * (int64_t)cu_count())
-    hipLaunchKernelGGL((k_ptrs_group_opt<V, NT, true>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G,
-                       xcd, opts, state);
-  else
-    hipLaunchKernelGGL((k_ptrs_group_opt<V, NT, false>), grid, block, 0, s, img, L, M, seg, wperm, gscale, gorder, G,
-                       xcd, opts, state);
-  return check_launch("k_ptrs_group_opt");
-}
+};
+struct GroupOptPtrs {
+  GroupPtrsArgs p;
+  const fjagg_server_opt* opts;
+  const int64_t* state;
+  static constexpr const char* kName = "k_ptrs_group_opt";
+  template <int V, bool NT, bool BURST>
+  static auto kern() { return k_ptrs_group_opt<V, NT, BURST>; }
+  template <class Kern>
+  void launch(Kern kern, dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, p.img, p.L, p.M, p.seg, p.wperm, p.gscale, p.gorder, p.G,
+                       opts, state);
+  }
+};
 }  // extern "C++"
 }  // namespace
 
@@ -3949,8 +3722,9 @@ int fjagg_server_update_group_dense(int in_dtype, const void* x_dev, int64_t ld,
   a.out_stride = 0;
   a.nonempty = nonempty;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group_opt<true>(vec, variant, a, opts_dev, state_dev, s)
-                                     : launch_dense_group_opt<false>(vec, variant, a, opts_dev, state_dev, s);
+  const GroupOptDense f{opts_dev, state_dev};
+  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group<true>(f, vec, variant, a, s)
+                                     : launch_dense_group<false>(f, vec, variant, a, s);
 }
 
 /* the same on the pytree path (fjagg.h) */
@@ -3980,16 +3754,8 @@ int fjagg_server_update_group_ptrs(int in_dtype, const int64_t* image_dev, int L
     return fail(FJAGG_EINVAL, "null pointer argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
-  const int g = (int)G;
-  if (vec)
-    return nt ? launch_ptrs_group_opt<4, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
-                                               nonempty, opts_dev, state_dev, s)
-              : launch_ptrs_group_opt<4, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
-                                                nonempty, opts_dev, state_dev, s);
-  return nt ? launch_ptrs_group_opt<1, true>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
-                                             nonempty, opts_dev, state_dev, s)
-            : launch_ptrs_group_opt<1, false>(image_dev, L, M, nblk, seg_dev, wperm_dev, gscale_dev, gorder_dev, g,
-                                              nonempty, opts_dev, state_dev, s);
+  const GroupOptPtrs f{{image_dev, L, M, seg_dev, wperm_dev, gscale_dev, gorder_dev, (int)G}, opts_dev, state_dev};
+  return launch_ptrs_group(f, vec, nt, nblk, (int)G, nonempty, s);
 }
 
 int fjagg_fill_synth(int dtype, void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t k0,
