@@ -109,12 +109,18 @@ def _ext_unpack(code, data):  # serialization.py:164-176
 
 
 def msgpack_serialize(tree) -> bytes:
-    """serialization.py:179-192 (dicts and lists of arrays; tuples become lists)."""
+    """serialization.py:179-192: dicts and lists of arrays and scalars. A tuple raises
+    ``TypeError``, as in the reference, which packs with ``strict_types=True`` and so hands
+    a tuple to its ``default`` hook, which returns it unpacked (serialization.py:17-19 asks
+    callers to turn tuples into lists first). Host tensors serialize as their numpy /
+    :class:`BF16Array` equivalent, every array as its C-order bytes."""
     return msgpack.packb(tree, default=_ext_pack, strict_types=True)
 
 
 def msgpack_deserialize(encoded: bytes):
-    """serialization.py:195-208; arrays are zero-copy views of ``encoded``."""
+    """serialization.py:195-208: msgpack's own unpacker with the reference's ext hook. Arrays
+    are read-only views of the bytes objects it creates (one copy of every payload);
+    :func:`msgpack_deserialize_view` returns the same values without that copy."""
     return msgpack.unpackb(encoded, ext_hook=_ext_unpack, raw=False)
 
 
@@ -124,24 +130,65 @@ import struct as _struct
 _U8, _U16, _U32, _U64 = (_struct.Struct(f) for f in (">B", ">H", ">I", ">Q"))
 _I8, _I16, _I32, _I64 = (_struct.Struct(f) for f in (">b", ">h", ">i", ">q"))
 _F32, _F64 = _struct.Struct(">f"), _struct.Struct(">d")
+_MAX_DEPTH = 512  # containers nested deeper are refused (one Python frame per level)
 
 
-def _read(buf: memoryview, i: int):
-    """One msgpack object at buf[i:] -> (value, next index). bin / ext payloads stay
-    memoryviews into ``buf``; ndarray ext payloads decode to numpy views (no copy)."""
+def _span(buf: memoryview, i: int, n: int) -> memoryview:
+    """buf[i:i + n], refusing a length that runs past the end (a slice would shorten silently)."""
+    if n > len(buf) - i:
+        raise ValueError(f"truncated msgpack input: {n} bytes declared at offset {i}, {len(buf) - i} left")
+    return buf[i:i + n]
+
+
+def _text(buf: memoryview, i: int, n: int) -> str:
+    try:
+        return str(_span(buf, i, n), "utf-8")
+    except UnicodeDecodeError:
+        raise ValueError(f"malformed msgpack input: the str at offset {i} is not UTF-8") from None
+
+
+def _read(buf: memoryview, i: int, depth: int = 0, copy_bin: bool = True):
+    """One msgpack object at buf[i:] -> (value, next index), with the values and types of
+    :func:`msgpack_deserialize`: str -> str, bin -> bytes (copied), ndarray ext payloads ->
+    numpy views into ``buf`` (no copy; their triple is read with ``copy_bin=False``, which
+    leaves bin a memoryview). A header or length field cut short raises IndexError
+    or struct.error, which :func:`msgpack_deserialize_view` turns into ValueError."""
     b = buf[i]
     i += 1
     if b <= 0x7F:
         return b, i
     if b >= 0xE0:
         return b - 0x100, i
-    if 0x80 <= b <= 0x8F:
-        return _read_map(buf, i, b & 0x0F)
-    if 0x90 <= b <= 0x9F:
-        return _read_array(buf, i, b & 0x0F)
     if 0xA0 <= b <= 0xBF:
         n = b & 0x1F
-        return bytes(buf[i:i + n]).decode(), i + n
+        return _text(buf, i, n), i + n
+    if b <= 0x9F or 0xDC <= b <= 0xDF:  # array / map: fix, 16, 32
+        if b <= 0x9F:
+            n = b & 0x0F
+            is_map = b <= 0x8F
+        else:
+            st = _U32 if b & 1 else _U16
+            n = st.unpack_from(buf, i)[0]
+            i += st.size
+            is_map = b >= 0xDE
+        if n > len(buf) - i:  # every entry takes at least one byte
+            raise ValueError(f"truncated msgpack input: {n} entries declared at offset {i}, {len(buf) - i} bytes left")
+        if depth >= _MAX_DEPTH:
+            raise ValueError(f"malformed msgpack input: containers nested deeper than {_MAX_DEPTH}")
+        depth += 1
+        if is_map:
+            out = {}
+            for _ in range(n):
+                k, i = _read(buf, i, depth, copy_bin)
+                if type(k) is not str and type(k) is not bytes:  # msgpack's strict_map_key
+                    raise ValueError(f"{type(k).__name__} is not allowed for map key")
+                out[k], i = _read(buf, i, depth, copy_bin)
+            return out, i
+        out = []
+        for _ in range(n):
+            v, i = _read(buf, i, depth, copy_bin)
+            out.append(v)
+        return out, i
     if b == 0xC0:
         return None, i
     if b in (0xC2, 0xC3):
@@ -150,19 +197,20 @@ def _read(buf: memoryview, i: int):
         st = (_U8, _U16, _U32)[b - 0xC4]
         n = st.unpack_from(buf, i)[0]
         i += st.size
-        return buf[i:i + n], i + n
+        v = _span(buf, i, n)
+        return (bytes(v) if copy_bin else v), i + n
     if b in (0xC7, 0xC8, 0xC9):  # ext 8/16/32
         st = (_U8, _U16, _U32)[b - 0xC7]
         n = st.unpack_from(buf, i)[0]
         i += st.size
         code = _I8.unpack_from(buf, i)[0]
         i += 1
-        return _ext(code, buf[i:i + n]), i + n
+        return _ext(code, _span(buf, i, n)), i + n
     if b in (0xD4, 0xD5, 0xD6, 0xD7, 0xD8):  # fixext 1..16
         n = 1 << (b - 0xD4)
         code = _I8.unpack_from(buf, i)[0]
         i += 1
-        return _ext(code, buf[i:i + n]), i + n
+        return _ext(code, _span(buf, i, n)), i + n
     if b == 0xCA:
         return _F32.unpack_from(buf, i)[0], i + 4
     if b == 0xCB:
@@ -174,59 +222,83 @@ def _read(buf: memoryview, i: int):
         st = (_U8, _U16, _U32)[b - 0xD9]
         n = st.unpack_from(buf, i)[0]
         i += st.size
-        return bytes(buf[i:i + n]).decode(), i + n
-    if b in (0xDC, 0xDD):
-        st = _U16 if b == 0xDC else _U32
-        return _read_array(buf, i + st.size, st.unpack_from(buf, i)[0])
-    if b in (0xDE, 0xDF):
-        st = _U16 if b == 0xDE else _U32
-        return _read_map(buf, i + st.size, st.unpack_from(buf, i)[0])
-    raise ValueError(f"unsupported msgpack byte 0x{b:02x}")
-
-
-def _read_array(buf, i, n):
-    out = []
-    for _ in range(n):
-        v, i = _read(buf, i)
-        out.append(v)
-    return out, i
-
-
-def _read_map(buf, i, n):
-    out = {}
-    for _ in range(n):
-        k, i = _read(buf, i)
-        v, i = _read(buf, i)
-        out[bytes(k).decode() if isinstance(k, memoryview) else k] = v
-    return out, i
+        return _text(buf, i, n), i + n
+    raise ValueError(f"malformed msgpack input: unsupported byte 0x{b:02x}")
 
 
 def _ext(code: int, payload: memoryview):
-    if code in (_Ext.ndarray, _Ext.npscalar):
-        (shape, name, data), _ = _read(payload, 0)
-        name = bytes(name).decode() if isinstance(name, memoryview) else name
-        if name == "bfloat16":
-            a = BF16Array(np.frombuffer(data, dtype=np.uint16).reshape(shape))
-        else:
-            a = np.frombuffer(data, dtype=np.dtype(name)).reshape(shape)
-        return a[()] if code == _Ext.npscalar else a
-    return _ext_unpack(code, bytes(payload))
+    if code not in (_Ext.ndarray, _Ext.npscalar):  # small: copied, decoded as msgpack_deserialize does
+        try:
+            return _ext_unpack(code, bytes(payload))
+        except Exception as e:  # msgpack's own errors, or a payload of the wrong structure
+            raise ValueError(f"malformed ext payload of type {code}: {e}") from None
+    try:
+        triple, end = _read(payload, 0, 0, False)
+    except (IndexError, _struct.error):
+        raise ValueError("malformed ndarray ext payload: cut short inside its (shape, dtype, data)") from None
+    if end != len(payload):
+        raise ValueError(f"malformed ndarray ext payload: {len(payload) - end} bytes after its (shape, dtype, data)")
+    if type(triple) is not list or len(triple) != 3:
+        raise ValueError("malformed ndarray ext payload: not a (shape, dtype, data) triple")
+    shape, name, data = triple
+    if type(name) is memoryview:
+        name = _text(name, 0, len(name))
+    if (type(shape) is not list or type(name) is not str or type(data) is not memoryview
+            or any(type(d) is not int or d < 0 for d in shape)):
+        raise ValueError("malformed ndarray ext payload: (shape, dtype, data) of the wrong types")
+    if name == "bfloat16":
+        dtype = np.dtype(np.uint16)
+    else:
+        try:
+            dtype = np.dtype(name)
+        except Exception:  # (TypeError for most names, others for what numpy tries to parse)
+            raise ValueError(f"malformed ndarray ext payload: unknown dtype {name!r}") from None
+        if dtype.hasobject:
+            raise ValueError(f"malformed ndarray ext payload: dtype {name!r} holds objects")
+    count = 1
+    for d in shape:
+        count *= d
+    if count * dtype.itemsize != len(data):
+        raise ValueError(f"malformed ndarray ext payload: shape {tuple(shape)} of {name} needs "
+                         f"{count * dtype.itemsize} bytes, {len(data)} given")
+    a = np.frombuffer(data, dtype=dtype).reshape(shape)
+    if name == "bfloat16":
+        a = BF16Array(a)
+    return a[()] if code == _Ext.npscalar else a
 
 
 def msgpack_deserialize_view(encoded) -> Any:
-    """msgpack_deserialize without copying array payloads: ndarray leaves are
-    read-only numpy views into ``encoded`` (keep it alive while they are used)."""
+    """:func:`msgpack_deserialize` without copying array payloads: the same values and Python
+    types (str keys stay str, bin keys and values are ``bytes`` copies, a map key that is
+    neither is refused), except that ndarray leaves are read-only numpy views into ``encoded``
+    (keep it alive while they are used). Anything but one complete msgpack object, whether
+    truncated, malformed or followed by more bytes, raises ``ValueError`` and nothing else."""
     buf = memoryview(encoded).cast("B")
-    v, i = _read(buf, 0)
+    try:
+        v, i = _read(buf, 0)
+    except (IndexError, _struct.error):
+        raise ValueError("truncated msgpack input: it ends inside an object") from None
+    except RecursionError:
+        raise ValueError("malformed msgpack input: containers nested too deep") from None
     if i != len(buf):
-        raise ValueError("trailing bytes after the msgpack object")
+        raise ValueError(f"{len(buf) - i} trailing bytes after the msgpack object")
     return v
 
 
 # ------------------------------------------------------------------------ ingestion
+def _as_f32(a: np.ndarray) -> np.ndarray:
+    """jnp canonicalisation (float64 -> float32, round to nearest): a value beyond float32's
+    range becomes an infinity, as it does there, without numpy's warning."""
+    a = np.asarray(a)
+    if a.dtype == np.float32:
+        return a
+    with np.errstate(over="ignore", invalid="ignore"):
+        return a.astype(np.float32)
+
+
 def _f32_to_bf16_bits(a: np.ndarray) -> np.ndarray:
     """Round-to-nearest-even float32 -> bfloat16 bits (NaN stays NaN)."""
-    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    u = np.ascontiguousarray(_as_f32(a)).view(np.uint32)
     nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
     r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
     return np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x40)).astype(np.uint16), r)
@@ -237,18 +309,19 @@ def _host_view(x, slab_dtype: torch.dtype) -> np.ndarray:
     if isinstance(x, torch.Tensor):
         if x.is_cuda:
             raise ValueError("DeltaIngestor takes host deltas; device deltas go to slab.set_client")
-        t = x.detach().contiguous()
-        if t.dtype != slab_dtype:
-            t = t.to(slab_dtype)
-        return t.view(torch.uint8).numpy().reshape(-1) if t.numel() else np.empty(0, np.uint8)
+        # as its numpy / BF16Array equivalent: one conversion whatever the container
+        # (Tensor.to(bfloat16) writes 0xFFFF for every NaN; _f32_to_bf16_bits keeps the
+        # sign and sets the quiet bit, the device's f32_to_bf16)
+        t = x.detach()
+        x = BF16Array(t.view(torch.int16).numpy().view(np.uint16)) if t.dtype == torch.bfloat16 else t.numpy()
     if slab_dtype == torch.bfloat16:
         a = np.asarray(x, np.uint16) if isinstance(x, BF16Array) else _f32_to_bf16_bits(np.asarray(x))
     else:
         a = np.asarray(x)
         if isinstance(x, BF16Array):
             a = (np.asarray(x, np.uint32) << np.uint32(16)).view(np.float32)
-        elif a.dtype != np.float32:
-            a = a.astype(np.float32)  # jnp canonicalisation (float64 -> float32)
+        else:
+            a = _as_f32(a)
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
@@ -256,10 +329,24 @@ class DeltaIngestor:
     """Pipelined host -> slab copies through ``depth`` pinned staging rows.
 
     ``put(k, delta)`` takes a host pytree (numpy / host tensors / BF16Array
-    leaves, in the slab's dtype) or msgpack bytes; it packs the leaves into a
-    pinned row (one host memcpy per leaf) and enqueues the H2D copy into slab row
-    k on the copy stream. ``ready()`` makes the current stream wait for every copy
-    enqueued so far.
+    leaves, converted to the slab's dtype on the host: one conversion whatever the
+    container) or msgpack bytes; it packs the leaves into a pinned row (one host
+    memcpy per leaf) and enqueues the H2D copy into slab row k on the copy stream.
+    ``ready()`` makes the current stream wait for every copy enqueued so far.
+
+    What the ring guarantees (tests/test_gpu_ingest.py):
+
+    * slot reuse: a staging row is rewritten only after the copy that last read it has
+      finished (``put`` blocks on that slot's event);
+    * earlier readers: the first ``put`` after construction or after ``ready()`` orders the
+      copy stream behind everything already enqueued on the current stream, so the next
+      round's copies cannot overtake the previous round's fold;
+    * ``ready()``: work enqueued on the current stream afterwards sees every row put so far;
+    * staging is synchronous on the host: the payload and the leaves may be released or
+      overwritten as soon as ``put`` returns;
+    * a ``put`` that raises (structure, leaf size, device leaf, bad payload, ``k`` out of
+      range) has enqueued nothing and leaves the ring, ``n`` and torch's thread count as
+      they were; only the padding-free ``num_params`` elements of a row are ever written.
     """
 
     def __init__(self, slab: ClientDeltaSlab, depth: Optional[int] = None, copy_threads: int = 4):
@@ -281,6 +368,8 @@ class DeltaIngestor:
         self._after_compute = False  # copy stream ordered after prior slab readers?
 
     def put(self, k: int, delta: Union[bytes, bytearray, memoryview, Any]) -> None:
+        if not 0 <= k < self.slab.num_clients:  # (storage[-1] would be the last client's row)
+            raise IndexError(f"client {k} is not a row of a slab of {self.slab.num_clients} clients")
         if isinstance(delta, (bytes, bytearray, memoryview)):
             delta = msgpack_deserialize_view(delta)
         leaves = pytree.flatten_as(self.slab.treedef, _tuples_as_lists(delta, self.slab.treedef))

@@ -93,6 +93,87 @@ def test_f32_to_bf16_rounding():
     assert back[3] == -2.0 and np.isinf(back[4]) and np.isnan(back[5])
 
 
+def _bf16_grid():
+    """All 65536 high halves x the low halves that decide a rounding."""
+    hi = np.arange(65536, dtype=np.uint32)[:, None] << np.uint32(16)
+    lo = np.array([0x0000, 0x0001, 0x7FFF, 0x8000, 0x8001, 0xFFFF], np.uint32)[None, :]
+    return (hi | lo).reshape(-1)
+
+
+def test_f32_to_bf16_bits_against_the_neighbour_reference():
+    """``_f32_to_bf16_bits`` (add 0x7FFF + lsb, shift) against tests/ingest_cases.ref_bf16_bits
+    (the nearer of the two neighbouring bfloat16 values, distances in float64, ties to even,
+    the overflow neighbour +-2^128) on every finite pattern of the grid."""
+    from tests.ingest_cases import ref_bf16_bits
+    u = _bf16_grid()
+    finite = (u & np.uint32(0x7FFFFFFF)) < np.uint32(0x7F800000)
+    assert int(finite.sum()) == 391_680
+    got = ingest._f32_to_bf16_bits(u.view(np.float32))
+    assert got.dtype == np.uint16 and got.shape == u.shape
+    want = ref_bf16_bits(u)
+    bad = np.flatnonzero((got != want) & finite)
+    assert bad.size == 0, [(hex(u[i]), hex(got[i]), hex(want[i])) for i in bad[:5]]
+
+
+def test_f32_to_bf16_bits_non_finite_and_overflow():
+    u = _bf16_grid()
+    got = ingest._f32_to_bf16_bits(u.view(np.float32)).astype(np.uint32)
+    mag = u & np.uint32(0x7FFFFFFF)
+    nan, inf = mag > np.uint32(0x7F800000), mag == np.uint32(0x7F800000)
+    assert int(nan.sum()) == 1534 and int(inf.sum()) == 2
+    # every NaN stays a NaN with its sign; every infinity stays
+    assert np.all((got[nan] & 0x7FFF) > 0x7F80)
+    assert np.array_equal(got[nan] & 0x8000, (u[nan] >> np.uint32(16)) & 0x8000)
+    assert np.array_equal(got[inf], u[inf] >> np.uint32(16))
+    # the first value that rounds up out of the finite range, and its neighbour below
+    edge = ingest._f32_to_bf16_bits(np.array([0x7F7F8000, 0x7F7F7FFF, 0xFF7F8000], np.uint32).view(np.float32))
+    assert edge.tolist() == [0x7F80, 0x7F7F, 0xFF80]
+
+
+@pytest.mark.parametrize("slab_dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_host_view_matrix(slab_dtype):
+    """Every leaf container and value of tests/ingest_cases.leaf_cases through ``_host_view``,
+    against bytes worked out in the test module (numpy's cast to float32, the neighbour
+    reference to bfloat16), never by ``_host_view`` itself."""
+    from tests import ingest_cases as ic
+    for name, leaf in ic.leaf_cases().items():
+        got = ingest._host_view(leaf, slab_dtype)
+        want = ic.expected_bytes(leaf, slab_dtype)
+        assert got.dtype == np.uint8 and got.ndim == 1 and got.flags.c_contiguous, name
+        assert got.tobytes() == want.tobytes(), name
+
+
+@pytest.mark.parametrize("slab_dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_same_values_same_bytes_whatever_the_container(slab_dtype):
+    """numpy, host torch and msgpack-decoded leaves of the same values give one row, NaNs
+    included (a host torch float32 leaf used to reach a bfloat16 slab through Tensor.to,
+    which writes 0xFFFF for every NaN)."""
+    from tests import ingest_cases as ic
+    f32 = ic.F32_BITS.view(np.float32).reshape(4, 6)
+    f64 = np.concatenate([ic.F64_BITS.view(np.float64), np.float64([1.5, -0.0, np.inf, 1e-40])]).reshape(4, 4)
+    for a in (f32, f64, _bf16_grid()[::97].view(np.float32)):
+        want = ingest._host_view(a, slab_dtype).tobytes()
+        assert want == ic.expected_bytes(a, slab_dtype).tobytes()
+        t = torch.from_numpy(a.copy())
+        assert ingest._host_view(t, slab_dtype).tobytes() == want
+        assert ingest._host_view(t.t(), slab_dtype).tobytes() == ingest._host_view(a.T, slab_dtype).tobytes()
+        back = ingest.msgpack_deserialize_view(ingest.msgpack_serialize({"x": t}))["x"]
+        assert ingest._host_view(back, slab_dtype).tobytes() == want
+    bits = ic.BF16_BITS.reshape(4, 6)
+    t = torch.from_numpy(bits.view(np.int16).copy()).view(torch.bfloat16)
+    for leaf, ref in ((t, bits), (t.t(), bits.T), (t[::2], bits[::2])):
+        assert ingest._host_view(leaf, slab_dtype).tobytes() == ingest._host_view(
+            ingest.BF16Array(ref), slab_dtype).tobytes()
+
+
+def test_host_view_refuses_device_tensors():
+    class OnDevice(torch.Tensor):  # a host stand-in that says it lives on the device
+        is_cuda = True
+
+    with pytest.raises(ValueError, match="DeltaIngestor takes host deltas; device deltas go to slab.set_client"):
+        ingest._host_view(torch.zeros(3).as_subclass(OnDevice), torch.float32)
+
+
 @pytest.mark.gpu
 def test_ingest_msgpack_into_slab_then_mean(cuda, coracle):
     import fedjax_amd
