@@ -102,6 +102,13 @@ _SIGNATURES = {
     "fjagg_gram_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _vp, _i64, _i32, _vp]),
     "fjagg_gram_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "fjagg_gram_chunk_columns": (_i64, [_i64, _i64]),
+    "fjagg_l2sq_rows_centered": (_i32, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "fjagg_center_fold_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_center_fold_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _i32, _vp]),
+    "fjagg_center_clip_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "fjagg_center_clip_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp,
+                                       _vp, _i64, _i32, _vp]),
+    "fjagg_center_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

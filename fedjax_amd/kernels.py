@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -967,6 +967,209 @@ def gram_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, out: Optional[
     _lib.call("fjagg_gram_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, out.data_ptr(), ws.data_ptr(),
               ws.numel(), _lib.UNALIGNED if unaligned else 0, _stream_handle(dev))
     return out
+
+
+CENTER_MAX_CLIENTS = 4096  # fjagg_center_*: the clipped fold's client limit (fjagg.h)
+_CENTER_WS = {}  # (device index, stream handle) -> workspace of a centered-clipping round
+
+
+def _center_workspace(dev: torch.device, need: int) -> torch.Tensor:
+    """The workspace of a centered-clipping round on ``dev``'s current stream (squared norms and
+    their block partials), cached like :func:`_gram_workspace`; under stream capture a tensor of
+    the graph's own pool, which is not kept. Never zeroed, nothing carried between calls."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    key = (dev.index, _stream_handle(dev))
+    ws = _CENTER_WS.get(key)
+    if ws is None and len(_CENTER_WS) >= 16:
+        _CENTER_WS.clear()
+    if ws is None or ws.numel() < need:
+        ws = _CENTER_WS[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def check_center_args(K: int, tau, iterations) -> Tuple[float, int]:
+    """``(f32(tau), iterations)`` of a centered-clipping round over ``K`` clients, checked: ``tau``
+    a number that is finite and > 0 as float32, ``iterations`` an int >= 1, ``1 <= K <= 4096``.
+    A bool is refused for both. Nothing here touches the library."""
+    if isinstance(tau, (bool, np.bool_)) or not isinstance(tau, (int, float, np.integer, np.floating)):
+        raise TypeError(f"tau must be a number, not {type(tau).__name__}")
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
+        raise TypeError("iterations must be an int")
+    with np.errstate(over="ignore"):
+        t = float(np.float32(tau))
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError(f"tau must be finite and > 0 (as float32), got {tau}")
+    if int(iterations) < 1:
+        raise ValueError(f"iterations must be >= 1, got {iterations}")
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"centered clipping needs at least 1 client, got K = {K}")
+    if K > CENTER_MAX_CLIENTS:
+        raise ValueError(f"centered clipping supports K <= {CENTER_MAX_CLIENTS} clients, got K = {K}")
+    return t, int(iterations)
+
+
+def _check_center_slab(x: torch.Tensor) -> Tuple[int, int]:
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"centered clipping takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("centered clipping takes rows of up to 1 GiB")
+    return K, P
+
+
+def _check_center_vectors(center: torch.Tensor, out: Optional[torch.Tensor], P: int, dev: torch.device) -> torch.Tensor:
+    """The centre and the output of a dense centered fold: contiguous float32 [P]; ``out`` may be
+    ``center`` itself (the same storage from the same address), never a partial overlap."""
+    if not isinstance(center, torch.Tensor) or center.dtype != torch.float32:
+        raise TypeError("center must be a float32 tensor")
+    if center.dim() != 1 or center.numel() != P or not center.is_contiguous():
+        raise ValueError(f"center must be a contiguous float32 tensor of {P} elements")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=dev)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+        raise TypeError("out must be a float32 tensor")
+    if out.dim() != 1 or out.numel() != P or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of {P} elements")
+    a, b = center.data_ptr(), out.data_ptr()
+    if a != b and a < b + 4 * P and b < a + 4 * P:
+        raise ValueError("out may be center itself, but must not overlap it in part")
+    return out
+
+
+def _check_center_image(image_dev: torch.Tensor, L: int, K: int, nblk: int) -> Tuple[int, int]:
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 3 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    return L, nblk
+
+
+def center_l2sq_rows(image_dev: torch.Tensor, R: int, max_n: int, *, rows_per_group: int = 1,
+                     take_sqrt: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``fjagg_l2sq_rows`` with a centre per row: ``image_dev`` is the int64 device image ``ptrs[R] |
+    n[R] | center_ptrs[R]`` of float32 rows, and ``out[g]`` the float32 sum of ``fl((x - v)^2)``
+    over the ``rows_per_group`` rows of group ``g`` in ``fjagg_l2sq_rows``' order (its bits with a
+    zero centre), or its correctly rounded root with ``take_sqrt``. The norm pass of centered
+    clipping on its own."""
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    R, max_n, rows_per_group = int(R), int(max_n), int(rows_per_group)
+    if R < 1 or rows_per_group < 1 or R % rows_per_group or max_n < 0 or image_dev.numel() < 3 * R:
+        raise ValueError(f"bad rows: R = {R}, rows_per_group = {rows_per_group}, image of {image_dev.numel()} words")
+    if max_n * 4 > _MAX_ROW_BYTES:
+        raise ValueError("centered norms take rows of up to 1 GiB")
+    dev = _require_device(image_dev)
+    G = R // rows_per_group
+    if out is None:
+        out = torch.empty(G, dtype=torch.float32, device=dev)
+    _f32_vector("out", out, G)
+    _require_device(image_dev, out)
+    ws = _center_workspace(dev, int(_lib.load().fjagg_l2sq_rows_workspace_bytes(R, max_n)))
+    _lib.call("fjagg_l2sq_rows_centered", _lib.F32, image_dev.data_ptr(), R, max_n, rows_per_group, int(bool(take_sqrt)),
+              out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle(dev))
+    return out
+
+
+def center_fold_dense(x: torch.Tensor, c: torch.Tensor, center: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+                      nontemporal: bool = False) -> torch.Tensor:
+    """One fold of centered clipping over a float32 slab ``x[K, P]`` with any device factor vector
+    ``c`` (float32 [K]): per column, from ``s = +0`` and in client order, ``s = fl(s + t_k)`` with
+    ``t_k = fl(c_k * fl(x_k - v))`` for ``c_k > 0`` and ``+0`` otherwise (a NaN, zero or negative
+    factor: the client's bits never reach the sum), then ``out = fl(v + fl(s * f32(1/K)))``.
+    ``center`` and ``out`` are contiguous float32 [P]; ``out`` may be ``center`` itself. 16-byte
+    units when the slab, the centre and the output allow it, element units otherwise: the same
+    bits. ``K <= 4096``; everything is checked before the library is touched."""
+    K, P = _check_center_slab(x)
+    check_center_args(K, 1.0, 1)
+    _f32_vector("c", c, K)
+    out = _check_center_vectors(center, out, P, x.device)
+    dev = _require_device(x, c, center, out)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_center_fold_dense", _lib.F32, x.data_ptr(), ld, K, P, c.data_ptr(), center.data_ptr(),
+              out.data_ptr(), _lib.NONTEMPORAL if nontemporal else 0, _stream_handle(dev))
+    return out
+
+
+def center_fold_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, c: torch.Tensor, *, unaligned: bool = False,
+                     nontemporal: bool = False) -> None:
+    """:func:`center_fold_dense`'s arithmetic on every leaf of a device plan image in one launch:
+    ``in_ptrs[K*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk] | center_ptrs[L]``, the blocks of
+    :func:`ptrs_plan` for float32 leaves made with the centre pointers counted in the per-leaf
+    alignment choice. A leaf's centre may be its output. ``unaligned`` as the plan was made."""
+    check_center_args(K, 1.0, 1)
+    L, nblk = _check_center_image(image_dev, L, K, nblk)
+    _f32_vector("c", c, K)
+    dev = _require_device(image_dev, c)
+    flags = (_lib.UNALIGNED if unaligned else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    _lib.call("fjagg_center_fold_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, c.data_ptr(), flags,
+              _stream_handle(dev))
+
+
+def _center_diagnostics(iterations: int, K: int, dev: torch.device):
+    return (torch.empty(iterations, K, dtype=torch.float32, device=dev),
+            torch.empty(iterations, K, dtype=torch.float32, device=dev))
+
+
+def centered_clip_dense(x: torch.Tensor, tau, center: torch.Tensor, *, iterations: int = 1,
+                        out: Optional[torch.Tensor] = None, leaf_table: Optional[torch.Tensor] = None,
+                        max_n: Optional[int] = None, nontemporal: bool = False):
+    """A whole round of centered clipping over a float32 slab ``x[K, P]``: ``iterations`` times the
+    norm pass around the centre, the clip factors ``c = min(1, f32(tau) / n)`` on the device and
+    :func:`center_fold_dense`, the first from ``center`` into ``out`` and the later ones in place
+    on ``out`` (``fjagg_center_clip_dense``; ``out`` may be ``center``). Returns ``(out,
+    distances, factors)``, the last two float32 ``[iterations, K]``. No host synchronisation and
+    nothing uploaded: capturable. ``leaf_table``: an int64 device tensor ``off[L] | n[L]`` of the
+    row's leaves (element offsets and sizes, ``max_n`` the largest size), which makes the norms
+    add up leaf by leaf as the pytree route's do; default: the row is one leaf."""
+    K, P = _check_center_slab(x)
+    tau, iterations = check_center_args(K, tau, iterations)
+    out = _check_center_vectors(center, out, P, x.device)
+    dev = _require_device(x, center, out)
+    if leaf_table is None:
+        L, max_n, tab = 1, P, None
+    else:
+        if not isinstance(leaf_table, torch.Tensor) or leaf_table.dtype != torch.int64 or leaf_table.dim() != 1 \
+                or leaf_table.numel() < 2 or leaf_table.numel() % 2 or not leaf_table.is_contiguous():
+            raise TypeError("leaf_table must be a contiguous int64 device tensor off[L] | n[L]")
+        _require_device(x, leaf_table)
+        L = leaf_table.numel() // 2
+        if max_n is None or not 0 <= int(max_n) <= P:
+            raise ValueError("a leaf table needs max_n, its largest leaf size, in [0, P]")
+        max_n, tab = int(max_n), leaf_table.data_ptr()
+    distances, factors = _center_diagnostics(iterations, K, dev)
+    ws = _center_workspace(dev, int(_lib.load().fjagg_center_clip_workspace_bytes(K, L, max_n)))
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_center_clip_dense", _lib.F32, x.data_ptr(), ld, K, P, tab, L, max_n, tau, iterations,
+              center.data_ptr(), out.data_ptr(), distances.data_ptr(), factors.data_ptr(), ws.data_ptr(), ws.numel(),
+              _lib.NONTEMPORAL if nontemporal else 0, _stream_handle(dev))
+    return out, distances, factors
+
+
+def centered_clip_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, max_n: int, tau, *, iterations: int = 1,
+                       unaligned: bool = False, nontemporal: bool = False):
+    """:func:`centered_clip_dense` over :func:`center_fold_ptrs`' plan image
+    (``fjagg_center_clip_ptrs``): the first iteration's centre is ``center_ptrs``, every later
+    one's is ``out_ptrs``, in place. ``max_n`` is the largest ``leaf_n``. Returns ``(distances,
+    factors)``, float32 ``[iterations, K]``; the result is behind ``out_ptrs``."""
+    tau, iterations = check_center_args(K, tau, iterations)
+    L, nblk = _check_center_image(image_dev, L, K, nblk)
+    max_n = int(max_n)
+    if max_n < 0 or max_n * 4 > _MAX_ROW_BYTES:
+        raise ValueError("centered clipping takes leaves of up to 1 GiB")
+    dev = _require_device(image_dev)
+    distances, factors = _center_diagnostics(iterations, K, dev)
+    ws = _center_workspace(dev, int(_lib.load().fjagg_center_clip_workspace_bytes(K, L, max_n)))
+    flags = (_lib.UNALIGNED if unaligned else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    _lib.call("fjagg_center_clip_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, max_n, tau, iterations,
+              distances.data_ptr(), factors.data_ptr(), ws.data_ptr(), ws.numel(), flags, _stream_handle(dev))
+    return distances, factors
 
 
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:

@@ -445,6 +445,84 @@ class ClientDeltaSlab:
         median = self.grouped_mean(a32, ids, 1)[0] if (ids >= 0).any() else None
         return tree_util.GeometricMedianResult(median, a32, d, gram)
 
+    def _flat_center(self, center) -> torch.Tensor:
+        """``center`` of :meth:`centered_clip` as a flat float32 [num_params] device tensor: zeros for
+        ``None``, the tensor itself when it is flat, a fresh row filled from a pytree's leaves."""
+        P = self.num_params
+        if center is None:
+            return torch.zeros(P, dtype=torch.float32, device=self.device)
+        if isinstance(center, torch.Tensor):
+            if center.dtype != torch.float32:
+                raise TypeError(f"center must be float32, not {center.dtype}")
+            if center.dim() != 1 or center.numel() != P or not center.is_contiguous() or center.device != self.storage.device:
+                raise ValueError(f"a flat center is a contiguous float32 [{P}] tensor on {self.storage.device}")
+            return center
+        leaves = pytree.flatten_as(self.treedef, center)
+        flat = torch.empty(P, dtype=torch.float32, device=self.device)
+        for l, (dst, src, shape) in enumerate(zip(pytree.leaves_of(self.unflatten(flat)), leaves, self.shapes)):
+            if not isinstance(src, torch.Tensor) or src.dtype != torch.float32:
+                raise TypeError(f"center leaf {l} must be a float32 tensor")
+            if tuple(src.shape) != shape or src.device != self.storage.device:
+                raise ValueError(f"center leaf {l} must have shape {shape} on {self.storage.device}")
+            dst.copy_(src)
+        return flat
+
+    def _center_leaf_table(self) -> torch.Tensor:
+        """The slab's leaf-row table ``off[L] | n[L]`` on the device: constant for the slab's life,
+        so it is uploaded on first use (refused under capture, :func:`_lib.upload`) and kept. A call
+        on another stream waits for the upload through an event; a capture cannot wait on an event
+        recorded outside it, so the upload must be complete when a capture begins
+        (``torch.cuda.graph`` synchronises the device on entry)."""
+        stream = torch.cuda.current_stream(self.device)
+        cached = getattr(self, "_center_tab", None)
+        if cached is None:
+            host = np.concatenate([self.offsets[:-1], np.array(self.sizes, dtype=np.int64)]).astype(np.int64)
+            tab = _lib.upload(torch.from_numpy(host), self.device)
+            uploaded = torch.cuda.Event()
+            uploaded.record(stream)
+            cached = self._center_tab = (tab, stream, uploaded)
+        elif stream != cached[1] and not torch.cuda.is_current_stream_capturing():
+            stream.wait_event(cached[2])
+        return cached[0]
+
+    def centered_clip(self, tau, center=None, *, iterations: int = 1,
+                      out: Optional[torch.Tensor] = None) -> "tree_util.CenteredClip":
+        """Centered clipping of the K rows (Karimireddy, He and Jaggi, ICML 2021): the mean of the
+        rows, each clipped to l2 distance ``tau`` from the centre, taken around that centre,
+        ``iterations`` times from ``center`` — the previous round's aggregate: a flat float32
+        ``[num_params]`` tensor, a pytree of the template's structure, or ``None`` for zeros.
+        The arithmetic is :func:`fedjax_amd.tree_util.tree_centered_clip`'s, and the result is bit
+        for bit that function's over the same deltas (the distances add up leaf by leaf in both).
+        There are no weights.
+
+        ``out``: a flat float32 ``[num_params]`` tensor for the new centre; ``out is center`` is
+        allowed (every iteration after the first runs in place anyway), a partial overlap is not.
+        Two passes over the slab and two small launches per iteration, no host synchronisation.
+        The only upload is the slab's leaf table, once, on the first call: every later call,
+        one under stream capture included, uploads nothing — after one eager call a round with
+        ``out=center`` can be captured and replayed with rewritten deltas. A first call under
+        capture raises. Returns a :class:`~fedjax_amd.tree_util.CenteredClip` whose ``center`` is
+        the template's pytree of views into ``out``; a float32 slab of up to 4096 clients."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"centered_clip needs a float32 slab, not {self.dtype}")
+        K, P = self.num_clients, self.num_params
+        tau, iterations = kernels.check_center_args(K, tau, iterations)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
+            raise TypeError("out must be a float32 tensor")
+        if out is not None and (out.dim() != 1 or out.numel() != P or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of {P} elements")
+        if P == 0:  # a template of empty leaves: every distance is 0, nothing to launch
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            return tree_util.CenteredClip(self.unflatten(flat),
+                                          torch.zeros(iterations, K, dtype=torch.float32, device=self.device),
+                                          torch.ones(iterations, K, dtype=torch.float32, device=self.device))
+        tab = self._center_leaf_table()
+        rows = self.rows
+        flat, distances, factors = kernels.centered_clip_dense(
+            rows, tau, self._flat_center(center), iterations=iterations, out=out, leaf_table=tab,
+            max_n=max(self.sizes), nontemporal=rows.numel() * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return tree_util.CenteredClip(self.unflatten(flat), distances, factors)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

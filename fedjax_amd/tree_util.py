@@ -48,6 +48,7 @@ __all__ = [
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
     "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
     "tree_mean_around_median", "tree_bulyan", "BulyanResult",
+    "tree_centered_clip", "CenteredClip",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -2095,6 +2096,107 @@ def tree_mean_around_median(pytrees: Iterable[PyTree], keep) -> Optional[PyTree]
     return _tree_columns(trees, "tree_mean_around_median",
                          lambda image_dev, L, nblk, nt: kernels.meamed_ptrs(image_dev, L, K, nblk, keep, scale,
                                                                             nontemporal=nt))
+
+
+class CenteredClip(NamedTuple):
+    """Result of centered clipping (:func:`tree_centered_clip`,
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.centered_clip`): ``center`` — the new centre, a pytree of
+    the clients' structure; ``distances`` / ``factors`` — float32 ``[iterations, K]`` device
+    tensors, per iteration and client in input order the l2 distance ``n_k`` of the client from
+    that iteration's centre and its clip factor ``c_k = min(1, tau / n_k)`` (NaN for a client
+    holding a NaN, 0 for one at infinite distance: both were skipped)."""
+    center: Any
+    distances: Any
+    factors: Any
+
+
+def _center_leaves(center, td, row0: List[torch.Tensor], what: str) -> List[torch.Tensor]:
+    """The leaves of a centre pytree, checked against client 0's canonical leaves: the clients'
+    structure, float32 tensors on their device, their shapes. A leaf that is not contiguous is
+    copied (the centre is never written)."""
+    leaves = pytree.flatten_as(td, center)
+    out = []
+    for l, (v, x) in enumerate(zip(leaves, row0)):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+            raise TypeError(f"{what}: center leaf {l} must be a float32 tensor "
+                            f"(got {v.dtype if isinstance(v, torch.Tensor) else type(v).__name__})")
+        if v.device != x.device:
+            raise ValueError(f"{what}: center leaf {l} is on {v.device}, the clients are on {x.device}")
+        if v.size() != x.size():
+            raise ValueError(f"{what}: center leaf {l} has shape {tuple(v.shape)}, the clients have {tuple(x.shape)}")
+        out.append(v if v.is_contiguous() else v.contiguous())
+    return out
+
+
+def tree_centered_clip(pytrees: Iterable[PyTree], tau, center: Optional[PyTree] = None, *,
+                       iterations: int = 1) -> Optional[CenteredClip]:
+    """Centered clipping of client pytrees (Karimireddy, He and Jaggi, ICML 2021): the mean of the
+    clients, each clipped to l2 distance ``tau`` from the centre ``v``, taken around that centre and
+    repeated ``iterations`` times from ``v = center`` (the previous round's aggregate; ``None``:
+    zeros)::
+
+        d_k = x_k - v;  n_k = ||d_k||;  c_k = min(1, tau / n_k);  v <- v + (1/K) sum_k c_k d_k
+
+    A client moves the result by at most ``tau / K`` per iteration whatever it sends, and because the
+    centre is history, an attacker that stays inside one round's variance is clipped too. In
+    float32 with no FMA: ``d`` is rounded, the squares are summed leaf by leaf in
+    :func:`tree_l2_norms`' order, the factors are :func:`kernels.clip_scales`' (NaN propagates, a
+    zero distance gives 1), the clipped differences ``fl(c_k d_k)`` are added in client order from
+    +0, and ``v' = fl(v + fl(s * f32(1/K)))`` — the divisor is K whatever was skipped. A client whose
+    factor is NaN, 0 or negative (it holds a NaN, an inf or 1e30) contributes nothing: its bits
+    never reach the result. With a zero centre and one iteration the factors are bit for bit
+    ``tree_clipped_mean``'s for unit weights. There are no weights.
+
+    Two passes over the deltas per iteration, O(K P) and bandwidth-bound; the factors are formed
+    on the device, so nothing visits the host. The structure walk and checks are
+    :func:`tree_trimmed_mean`'s; ``center`` is a pytree of the clients' structure with float32
+    leaves on their device. The result is a fresh pytree (slices of one allocation), bit for bit
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.centered_clip` over the same deltas; the inputs and the
+    centre are never written; a one-shot iterable is consumed once. Float32 leaves, ``K <= 4096``.
+    Returns :class:`CenteredClip`; no clients: ``None``. Raises under stream capture (the plan
+    image goes through a pinned staging buffer; the slab route is capturable)."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    K = len(trees)
+    tau, iterations = kernels.check_center_args(K, tau, iterations)
+    what = "tree_centered_clip"
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"{what} needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        dev = _default_device()
+        return CenteredClip(pytree.unflatten(td, []), torch.zeros(iterations, K, dtype=torch.float32, device=dev),
+                            torch.ones(iterations, K, dtype=torch.float32, device=dev))
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    L = len(leaf_n)
+    if int(leaf_n.max()) * 4 > kernels._MAX_ROW_BYTES:
+        raise ValueError(f"{what} takes leaves of up to 1 GiB")
+    # one result row: every leaf at a 16-byte aligned offset
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)])
+    flat = torch.empty(max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = pytree.unflatten(td, [flat[o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+    if center is None:
+        zeros = torch.zeros_like(flat)
+        center_ptrs = zeros.data_ptr() + 4 * offs[:-1].astype(np.int64)
+    else:
+        held = _center_leaves(center, td, rows[0], what)  # (keeps a contiguous copy alive past the launch)
+        center_ptrs = np.array([v.data_ptr() for v in held], dtype=np.int64)
+    if not leaf_n.any():  # only empty leaves: every distance is 0, nothing to fold
+        return CenteredClip(result, torch.zeros(iterations, K, dtype=torch.float32, device=device),
+                            torch.ones(iterations, K, dtype=torch.float32, device=device))
+    in_ptrs = _ptr_table(rows)
+    out_ptrs = flat.data_ptr() + 4 * offs[:-1].astype(np.int64)
+    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, center_ptrs, device)
+    image = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, blocks, center_ptrs])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    distances, factors = kernels.centered_clip_ptrs(
+        image_dev, L, K, len(blocks) // 2, int(leaf_n.max()), tau, iterations=iterations,
+        nontemporal=int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES)
+    return CenteredClip(result, distances, factors)
 
 
 class BulyanResult(NamedTuple):

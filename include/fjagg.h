@@ -22,6 +22,7 @@
  *     (no reference row) trimmed mean / median (Yin et al. 2018) fjagg_trim_* (order statistics per coordinate)
  *     (no reference row) Krum / geometric median (Gram matrix)  fjagg_gram_* (K x K inner products, float64)
  *     (no reference row) mean around the median / Bulyan        fjagg_meamed_* (the keep values nearest the median)
+ *     (no reference row) centered clipping (Karimireddy et al. 2021) fjagg_center_* (clipped around the last aggregate)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -653,6 +654,63 @@ int fjagg_gram_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
 int64_t fjagg_gram_workspace_bytes(int64_t K, int64_t P_or_total, int64_t nblk);
 /* Columns per workgroup of the dense entry (a multiple of FJAGG_GRAM_CHAIN, a function of K and P alone). */
 int64_t fjagg_gram_chunk_columns(int64_t K, int64_t P);
+
+/*
+ * Centered clipping: the robust mean clipped around the previous round's aggregate (Karimireddy, He
+ * and Jaggi, "Learning from History for Byzantine Robust Optimization", ICML 2021). The reference has
+ * no such aggregator; the semantics are fixed here. Float32 deltas, centre and result,
+ * 1 <= K <= 4096, T = tau finite and > 0, iterations >= 1. One iteration from centre v:
+ *     d_k[p] = fl(x_k[p] - v[p])
+ *     q_k    = sum_p fl(d_k[p]^2)     float32, in fjagg_l2sq_rows' order: leaf by leaf, 64 Ki-element
+ *                                     blocks, lane / shuffle tree / wave / block / row as k_l2sq_rows
+ *     n_k, c_k = fjagg_clip_scales(q, T)      n = sqrt(q), c = min(1, T / n), NaN propagates, n = 0: c = 1
+ *     t_k[p] = c_k > 0 ? fl(c_k * d_k[p]) : +0
+ *     s = +0; s = fl(s + t_k[p]) for k = 0 .. K-1 in client order (no FMA)
+ *     v'[p] = fl(v[p] + fl(s * f32(1/K)))     the divisor is K, whatever was skipped
+ * A client holding a NaN has c = NaN, one holding inf or 1e30 has q = inf and c = 0: both contribute
+ * +0 by a select on the factor, so their bits never reach the result (their rows may be loaded).
+ * There are no weights. With a zero centre q has fjagg_l2sq_rows' bits.
+ * Every lane of the fold keeps its centre unit in registers and writes v' for its own columns only:
+ * out may be the centre itself (the same address); a partial overlap is refused. No entry visits
+ * the host or synchronises; all are capturable.
+ * Flags: FJAGG_NONTEMPORAL and, on the pytree entries, FJAGG_UNALIGNED (the flag the plan was made
+ * with). The dense entries pick 16-byte units when x_dev, ld, the centre and the output allow it and
+ * element units otherwise. Refused with nothing launched, all with the one code FJAGG_EUNSUPPORTED:
+ * a dtype other than FJAGG_F32; K < 1 or K > 4096; P < 1, ld < P; tau not finite or <= 0;
+ * iterations < 1; null pointers; rows over 1 GiB; FJAGG_SCALE, FJAGG_ACCUMULATE, FJAGG_NARROW,
+ * FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, FJAGG_UNBALANCED, a FJAGG_VARIANT byte or any other flag; a
+ * partial overlap of out and centre; a bad plan or leaf table; too small a workspace.
+ */
+/* The norm pass alone: fjagg_l2sq_rows with a centre per row. image_dev = ptrs[R] | n[R] |
+ * center_ptrs[R]; out[g] sums fl((x - v)^2) over the rows of group g. The other arguments and the
+ * workspace size (fjagg_l2sq_rows_workspace_bytes) are fjagg_l2sq_rows'; R is not limited to 65535. */
+int fjagg_l2sq_rows_centered(int in_dtype, const int64_t* image_dev, int64_t R, int64_t max_n, int64_t rows_per_group,
+                             int take_sqrt, float* out_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+/* One fold over a dense slab with any device factor vector c_dev[K] (fjagg_clip_scales makes the clip
+ * factors): client k's row at x_dev + k*ld elements; center_dev and out_dev are float[P]. */
+int fjagg_center_fold_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const float* c_dev,
+                            const void* center_dev, void* out_dev, int flags, void* stream);
+/* One fold over the plan image of fjagg_trim_ptrs followed by the L centre pointers:
+ * in_ptrs[K*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk] | center_ptrs[L]. A leaf's centre may be
+ * its output. The caller's plan must count the centre pointers in its per-leaf alignment choice. */
+int fjagg_center_fold_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, const float* c_dev,
+                           int flags, void* stream);
+/* Workspace of the two whole-round entries: K clients of L leaves, the largest of max_n elements. */
+int64_t fjagg_center_clip_workspace_bytes(int64_t K, int64_t L, int64_t max_n);
+/* The whole round over a dense slab, `iterations` times norm pass, fjagg_clip_scales and fold: the
+ * first from center_dev into out_dev, the later ones in place on out_dev. distances_dev and
+ * factors_dev are float[iterations][K]: n_k and c_k of every iteration. leaf_tab_dev = off[L] | n[L]
+ * (int64 element offsets and sizes of the row's leaves, ascending and disjoint, max_n the largest)
+ * gives the norms their leaf-by-leaf order; NULL with L = 1 takes the row as one leaf. */
+int fjagg_center_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                            const int64_t* leaf_tab_dev, int64_t L, int64_t max_n, float tau, int64_t iterations,
+                            const void* center_dev, void* out_dev, float* distances_dev, float* factors_dev,
+                            void* ws_dev, int64_t ws_bytes, int flags, void* stream);
+/* The whole round over fjagg_center_fold_ptrs' image: the first iteration's centre is center_ptrs,
+ * every later one's is out_ptrs (in place). max_n is the largest leaf_n. */
+int fjagg_center_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t max_n,
+                           float tau, int64_t iterations, float* distances_dev, float* factors_dev, void* ws_dev,
+                           int64_t ws_bytes, int flags, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
