@@ -289,7 +289,7 @@ int center_check(int in_dtype, int64_t K, int flags, int allowed) {
   return FJAGG_OK;
 }
 
-int dense_check(const void* x, int64_t ld, int64_t P, const void* center, const void* out) {
+int dense_check(const void* x, int64_t ld, int64_t K, int64_t P, const void* center, const void* out) {
   if (P < 1 || ld < P)
     return refuse(FJAGG_EUNSUPPORTED, "centered clipping: need 1 <= P <= ld (P=%lld, ld=%lld)", (long long)P,
                 (long long)ld);
@@ -298,6 +298,14 @@ int dense_check(const void* x, int64_t ld, int64_t P, const void* center, const 
   const uintptr_t a = reinterpret_cast<uintptr_t>(center), b = reinterpret_cast<uintptr_t>(out);
   if (a != b && a < b + (uintptr_t)P * 4 && b < a + (uintptr_t)P * 4)
     return refuse(FJAGG_EUNSUPPORTED, "centered clipping: out may be the centre itself, not overlap it in part");
+  // the fold's workgroups read every row while others store their columns of out: an out inside
+  // the slab's extent [x, x + ((K-1)*ld + P)*4) would be read half written (the centre is only
+  // read, so it may be a row of the slab)
+  const unsigned __int128 x0 = reinterpret_cast<uintptr_t>(x),
+                          x1 = x0 + ((unsigned __int128)(K - 1) * (uint64_t)ld + (uint64_t)P) * 4;
+  if (b < x1 && x0 < (unsigned __int128)b + (uint64_t)P * 4)
+    return refuse(FJAGG_EUNSUPPORTED,
+                  "centered clipping: out overlaps the deltas (the slab's rows are read while out is written)");
   return FJAGG_OK;
 }
 
@@ -424,7 +432,7 @@ int fjagg_center_fold_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t
                             const void* center_dev, void* out_dev, int flags, void* stream) {
   center_err[0] = 0;
   if (int rc = center_check(in_dtype, K, flags, FJAGG_NONTEMPORAL)) return rc;
-  if (int rc = dense_check(x_dev, ld, P, center_dev, out_dev)) return rc;
+  if (int rc = dense_check(x_dev, ld, K, P, center_dev, out_dev)) return rc;
   if (!c_dev) return refuse(FJAGG_EUNSUPPORTED, "centered clipping: null pointer argument");
   return launch_fold_dense(reinterpret_cast<const uint8_t*>(x_dev), ld, (int)K, P, c_dev,
                            reinterpret_cast<const uint8_t*>(center_dev), reinterpret_cast<uint8_t*>(out_dev),
@@ -453,7 +461,7 @@ int fjagg_center_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t
                             void* ws_dev, int64_t ws_bytes, int flags, void* stream) {
   center_err[0] = 0;
   if (int rc = center_check(in_dtype, K, flags, FJAGG_NONTEMPORAL)) return rc;
-  if (int rc = dense_check(x_dev, ld, P, center_dev, out_dev)) return rc;
+  if (int rc = dense_check(x_dev, ld, K, P, center_dev, out_dev)) return rc;
   if (int rc = round_check(tau, iterations, distances_dev, factors_dev)) return rc;
   if (L < 1 || L >= (1 << 22) || (!leaf_tab_dev && L != 1) || max_n < 0 || max_n > P)
     return refuse(FJAGG_EUNSUPPORTED, "centered clipping: bad leaf table (L=%lld, max_n=%lld)", (long long)L,

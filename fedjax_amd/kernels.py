@@ -1023,9 +1023,11 @@ def _check_center_slab(x: torch.Tensor) -> Tuple[int, int]:
     return K, P
 
 
-def _check_center_vectors(center: torch.Tensor, out: Optional[torch.Tensor], P: int, dev: torch.device) -> torch.Tensor:
-    """The centre and the output of a dense centered fold: contiguous float32 [P]; ``out`` may be
-    ``center`` itself (the same storage from the same address), never a partial overlap."""
+def _check_center_vectors(center: torch.Tensor, out: Optional[torch.Tensor], x: torch.Tensor) -> torch.Tensor:
+    """The centre and the output of a dense centered fold over ``x[K, P]``: contiguous float32
+    [P]; ``out`` may be ``center`` itself (the same storage from the same address), never a partial
+    overlap, and never inside the extent of ``x``, whose rows are read while ``out`` is written."""
+    (K, P), dev = x.shape, x.device
     if not isinstance(center, torch.Tensor) or center.dtype != torch.float32:
         raise TypeError("center must be a float32 tensor")
     if center.dim() != 1 or center.numel() != P or not center.is_contiguous():
@@ -1039,6 +1041,10 @@ def _check_center_vectors(center: torch.Tensor, out: Optional[torch.Tensor], P: 
     a, b = center.data_ptr(), out.data_ptr()
     if a != b and a < b + 4 * P and b < a + 4 * P:
         raise ValueError("out may be center itself, but must not overlap it in part")
+    x0 = x.data_ptr()
+    x1 = x0 + 4 * ((K - 1) * (x.stride(0) if K > 1 else P) + P)
+    if b < x1 and x0 < b + 4 * P:
+        raise ValueError("out must not overlap the deltas x: their rows are read while out is written")
     return out
 
 
@@ -1083,13 +1089,14 @@ def center_fold_dense(x: torch.Tensor, c: torch.Tensor, center: torch.Tensor, *,
     ``c`` (float32 [K]): per column, from ``s = +0`` and in client order, ``s = fl(s + t_k)`` with
     ``t_k = fl(c_k * fl(x_k - v))`` for ``c_k > 0`` and ``+0`` otherwise (a NaN, zero or negative
     factor: the client's bits never reach the sum), then ``out = fl(v + fl(s * f32(1/K)))``.
-    ``center`` and ``out`` are contiguous float32 [P]; ``out`` may be ``center`` itself. 16-byte
+    ``center`` and ``out`` are contiguous float32 [P]; ``out`` may be ``center`` itself, but must
+    not overlap ``x`` (``center``, only read, may be a row of it). 16-byte
     units when the slab, the centre and the output allow it, element units otherwise: the same
     bits. ``K <= 4096``; everything is checked before the library is touched."""
     K, P = _check_center_slab(x)
     check_center_args(K, 1.0, 1)
     _f32_vector("c", c, K)
-    out = _check_center_vectors(center, out, P, x.device)
+    out = _check_center_vectors(center, out, x)
     dev = _require_device(x, c, center, out)
     ld = x.stride(0) if K > 1 else P
     _lib.call("fjagg_center_fold_dense", _lib.F32, x.data_ptr(), ld, K, P, c.data_ptr(), center.data_ptr(),
@@ -1130,7 +1137,7 @@ def centered_clip_dense(x: torch.Tensor, tau, center: torch.Tensor, *, iteration
     add up leaf by leaf as the pytree route's do; default: the row is one leaf."""
     K, P = _check_center_slab(x)
     tau, iterations = check_center_args(K, tau, iterations)
-    out = _check_center_vectors(center, out, P, x.device)
+    out = _check_center_vectors(center, out, x)
     dev = _require_device(x, center, out)
     if leaf_table is None:
         L, max_n, tab = 1, P, None

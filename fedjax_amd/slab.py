@@ -496,7 +496,8 @@ class ClientDeltaSlab:
         There are no weights.
 
         ``out``: a flat float32 ``[num_params]`` tensor for the new centre; ``out is center`` is
-        allowed (every iteration after the first runs in place anyway), a partial overlap is not.
+        allowed (every iteration after the first runs in place anyway), a partial overlap is not, and
+        neither is an ``out`` inside the slab's own rows (they are read while ``out`` is written).
         Two passes over the slab and two small launches per iteration, no host synchronisation.
         The only upload is the slab's leaf table, once, on the first call: every later call,
         one under stream capture included, uploads nothing — after one eager call a round with

@@ -671,15 +671,18 @@ int64_t fjagg_gram_chunk_columns(int64_t K, int64_t P);
  * +0 by a select on the factor, so their bits never reach the result (their rows may be loaded).
  * There are no weights. With a zero centre q has fjagg_l2sq_rows' bits.
  * Every lane of the fold keeps its centre unit in registers and writes v' for its own columns only:
- * out may be the centre itself (the same address); a partial overlap is refused. No entry visits
- * the host or synchronises; all are capturable.
+ * out may be the centre itself (the same address); a partial overlap is refused, and so is, on the
+ * dense entries, an out that touches the slab's extent [x, x + ((K-1)*ld + P)*4): the rows are read
+ * while out is written (the centre, only read, may be a row of the slab). No entry visits the host
+ * or synchronises; all are capturable.
  * Flags: FJAGG_NONTEMPORAL and, on the pytree entries, FJAGG_UNALIGNED (the flag the plan was made
  * with). The dense entries pick 16-byte units when x_dev, ld, the centre and the output allow it and
  * element units otherwise. Refused with nothing launched, all with the one code FJAGG_EUNSUPPORTED:
  * a dtype other than FJAGG_F32; K < 1 or K > 4096; P < 1, ld < P; tau not finite or <= 0;
  * iterations < 1; null pointers; rows over 1 GiB; FJAGG_SCALE, FJAGG_ACCUMULATE, FJAGG_NARROW,
  * FJAGG_HOST_TABLES, FJAGG_ZEROED_WS, FJAGG_UNBALANCED, a FJAGG_VARIANT byte or any other flag; a
- * partial overlap of out and centre; a bad plan or leaf table; too small a workspace.
+ * partial overlap of out and centre; an out overlapping the dense deltas; a bad plan or leaf table;
+ * too small a workspace.
  */
 /* The norm pass alone: fjagg_l2sq_rows with a centre per row. image_dev = ptrs[R] | n[R] |
  * center_ptrs[R]; out[g] sums fl((x - v)^2) over the rows of group g. The other arguments and the

@@ -11,16 +11,24 @@ from a centre v, taken around that centre. One iteration of this project's contr
     v'  = fl(v + fl(s * f32(1/K)))                the divisor is K, whatever was skipped
 
 numpy's float32 ``-``, ``*``, ``+``, ``/`` and ``sqrt`` are correctly rounded IEEE operations, so
-every step below is the contract's rounding. The one thing numpy cannot restate is the ORDER in
-which the library adds the squares: ``centered_clip_ref`` without ``factors`` takes q from a
-float64 sum rounded once — a stand-in, within 2e-6 of any float32 order, and documented as such;
-with ``factors`` (the library's own) the folds are exact restatements.
+every step below is the contract's rounding. That includes the ORDER in which the library adds the
+squares: ``clipped_mean_ref.l2sq_rows_ref`` restates ``fjagg_l2sq_rows``' summation (leaf by leaf,
+64 Ki-element blocks, 256 lanes striding the block, the xor shuffle tree, the four wave sums, the
+block partials in order), and the centred norm pass is that summation applied to ``fl(x - v)``:
+``centered_l2sq_ref`` for one client, ``centered_distances_ref`` for all K rows at once (the same
+additions, vectorised over the clients). ``centered_clip_ref(x, v, tau, L, sizes=...)`` is
+therefore a closed computation of a whole round, distances, factors and centre, with nothing
+taken from the code under test; a row given whole is the one-leaf case ``sizes=[P]``. Without
+``sizes`` and ``factors`` q comes from a float64 sum rounded once — a stand-in, within 2e-6 of
+any float32 order, kept for the CPU tests of the rule itself; with ``factors`` those drive the
+folds.
 """
 import numpy as np
 
-from tests.clipped_mean_ref import clip_factors_ref
+from tests.clipped_mean_ref import clip_factors_ref, l2sq_rows_ref
 
 F32 = np.float32
+NORM_BLOCK = 65536  # elements per norm block (fjagg_l2sq_rows' partition)
 
 
 def centered_fold_ref(x, v, c):
@@ -55,16 +63,68 @@ def stand_in_norms(x, v):
         return np.sqrt(q)
 
 
-def centered_clip_ref(x, v, tau, L, factors=None):
+def centered_l2sq_ref(leaves_x, leaves_v):
+    """q of ONE client: ``l2sq_rows_ref``'s summation applied to fl(x - v), leaf by leaf (a leaf of
+    no elements adds +0). ``leaves_x`` / ``leaves_v``: the client's and the centre's leaves."""
+    with np.errstate(all="ignore"):
+        return l2sq_rows_ref([(np.asarray(a, dtype=F32).reshape(-1) - np.asarray(b, dtype=F32).reshape(-1)).astype(F32)
+                              for a, b in zip(leaves_x, leaves_v)])
+
+
+def centered_l2sq_rows_ref(x, v, sizes, wave_order=(0, 1, 2, 3)):
+    """``centered_l2sq_ref`` of every row of ``x`` [K, P] cut into leaves of ``sizes``: float32 [K].
+    The same additions in the same order, each made for all K clients at once. ``wave_order``
+    other than the library's (0, 1, 2, 3) gives a WRONG sum on purpose: a test uses it to show
+    that its data tells the orders apart."""
+    x = np.asarray(x, dtype=F32)
+    v = np.asarray(v, dtype=F32)
+    K, P = x.shape
+    assert sum(sizes) == P and v.shape == (P,)
+    s = np.zeros(K, dtype=F32)
+    o = 0
+    with np.errstate(all="ignore"):
+        for n in sizes:
+            d = (x[:, o:o + n] - v[o:o + n]).astype(F32)
+            o += n
+            for b0 in range(0, max(n, 1), NORM_BLOCK):
+                sq = (d[:, b0:b0 + NORM_BLOCK] * d[:, b0:b0 + NORM_BLOCK]).astype(F32)
+                m, full = sq.shape[1], sq.shape[1] // 256
+                acc = np.zeros((K, 256), dtype=F32)  # lane t: elements t, t + 256, ... in order from +0
+                body = sq[:, :full * 256].reshape(K, full, 256)
+                for j in range(full):
+                    acc = acc + body[:, j]
+                if m % 256:  # (a lane with no element left adds nothing: its sum is never -0)
+                    acc[:, :m % 256] = acc[:, :m % 256] + sq[:, full * 256:]
+                w = acc.reshape(K, 4, 64)
+                for step in (32, 16, 8, 4, 2, 1):  # the xor shuffle tree of a wave: lane i adds lane i ^ step
+                    pairs = w.reshape(K, 4, 32 // step, 2, step)
+                    w = (pairs + pairs[:, :, :, ::-1, :]).reshape(K, 4, 64)
+                t = w[:, wave_order[0], 0]
+                for i in wave_order[1:]:  # the four wave sums in order
+                    t = t + w[:, i, 0]
+                s = s + t  # the block partials in leaf / block order from +0
+    return s
+
+
+def centered_distances_ref(x, v, sizes):
+    """n_k = the float32 ``sqrt`` of ``centered_l2sq_rows_ref``: the library's distances, bit for bit."""
+    with np.errstate(all="ignore"):
+        return np.sqrt(centered_l2sq_rows_ref(x, v, sizes))
+
+
+def centered_clip_ref(x, v, tau, L, factors=None, sizes=None):
     """``L`` iterations from centre ``v``. Returns (centre, distances [L, K], factors [L, K]).
-    ``factors`` [L, K] given: those drive the folds (distances are then the stand-in's, for
-    information). Otherwise the factors come from ``stand_in_norms``."""
+    ``sizes`` (the row's leaf sizes; ``[P]`` for a row taken whole) given: the closed round, the
+    distances ``centered_distances_ref``'s and the factors from them. ``factors`` [L, K] given:
+    those drive the folds (distances are then the stand-in's, for information). Neither: the
+    factors come from ``stand_in_norms``."""
     x = np.asarray(x, dtype=F32)
     v = np.asarray(v, dtype=F32).copy()
     K = x.shape[0]
+    assert factors is None or sizes is None
     dist, fac = np.empty((L, K), dtype=F32), np.empty((L, K), dtype=F32)
     for l in range(L):
-        dist[l] = stand_in_norms(x, v)
+        dist[l] = stand_in_norms(x, v) if sizes is None else centered_distances_ref(x, v, sizes)
         fac[l] = clip_factors_ref(dist[l], tau) if factors is None else np.asarray(factors, dtype=F32)[l]
         v = centered_fold_ref(x, v, fac[l])
     return v, dist, fac

@@ -76,5 +76,30 @@ def f64_norms(x):
     return np.sqrt((x * x).sum(axis=1))
 
 
+def l2sq_rows_ref(leaves):
+    """fjagg_l2sq_rows's sum of one client's squares, restated in numpy float32: every leaf in
+    64 Ki-element blocks; in a block lane t of 256 adds the squares of elements t, t + 256, ... in
+    that order from +0; the 64 lanes of a wave are added by an xor butterfly (32, 16, ... 1), the
+    four waves in order; then the block partials in leaf / block order from +0."""
+    s = F32(0)
+    for a in leaves:
+        a = np.asarray(a, dtype=F32).reshape(-1)
+        for b0 in range(0, max(a.size, 1), 65536):
+            sq = a[b0:b0 + 65536] * a[b0:b0 + 65536]
+            m = np.zeros((sq.size + 255) // 256 * 256, dtype=F32)  # (+0 where a lane has no element:
+            m[:sq.size] = sq                                        # adding it changes nothing)
+            acc = np.zeros(256, dtype=F32)
+            for row in m.reshape(-1, 256):
+                acc = acc + row
+            w = acc.reshape(4, 64)
+            for o in (32, 16, 8, 4, 2, 1):
+                w = w + w[:, np.arange(64) ^ o]
+            t = w[0, 0]
+            for i in range(1, 4):
+                t = t + w[i, 0]
+            s = s + t
+    return s
+
+
 def bits(a):
     return np.ascontiguousarray(np.asarray(a, dtype=F32)).view(np.uint32)

@@ -2,12 +2,14 @@
 fjagg_center_clip_dense / _ptrs and the Python surface over them) against the numpy float32
 restatement in tests/centered_clip_ref.py.
 
-The fold is held to the restatement bit for bit for ANY device factor vector; with a zero centre
-the norm pass is held to fjagg_l2sq_rows' bits, otherwise to 2e-6 of a float64 norm, the bound the
-project holds all its norms to (their reduction order is the library's own). A whole round is
-checked closed: its factors are the restatement's function of ITS distances, and its centre is
-the restatement's fold driven by ITS factors. Bit patterns are compared with every NaN mapped to
-one pattern, as tests/test_gpu_clipped_mean.py does and for its reason.
+The fold is held to the restatement bit for bit for ANY device factor vector; the norm pass is
+held to the restated summation order bit for bit (centered_l2sq_ref), with a zero centre also to
+fjagg_l2sq_rows' own bits, and independently to 2e-6 of a float64 norm, the bound the project
+holds all its norms to. A whole round is checked closed: its distances are the restatement's of
+the restatement's own running centre, its factors the restatement's function of those, and its
+centre the restatement's fold driven by them: nothing is taken from the code under test. Bit
+patterns are compared with every NaN mapped to one pattern, as tests/test_gpu_clipped_mean.py
+does and for its reason.
 """
 import functools
 
@@ -233,17 +235,38 @@ def test_norm_pass_random_centre(cuda):
     grouped = host(kernels.center_l2sq_rows(image, 6, max(sizes), rows_per_group=3, take_sqrt=True))
     want3 = np.sqrt((want.reshape(2, 3) ** 2).sum(axis=1))
     assert (np.abs(grouped - want3) <= NORM_RTOL * want3).all()
+    # the order itself: every row, and every client's three rows in order, with and without the root
+    q1 = np.array([ref.centered_l2sq_ref([x], [v]) for row in xs for x, v in zip(row, vs[0])], dtype=F32)
+    q3 = np.array([ref.centered_l2sq_ref(row, vs[0]) for row in xs], dtype=F32)
+    for rpg, q in ((1, q1), (3, q3)):
+        assert_bits(kernels.center_l2sq_rows(image, 6, max(sizes), rows_per_group=rpg), q,
+                    f"restated order, {rpg} rows a group")
+        assert_bits(kernels.center_l2sq_rows(image, 6, max(sizes), rows_per_group=rpg, take_sqrt=True), np.sqrt(q),
+                    f"restated order, {rpg} rows a group, root")
+    # rows enough that the order of the four wave sums shows: on this data the reversed order gives
+    # other bits in a good share of the rows (on the six rows above it happens to give the same)
+    xs, held = norm_rows(cuda, [1027], 48, seed=3)
+    x48, v0 = np.stack([row[0] for row in xs]), vs[0][2]
+    q = ref.centered_l2sq_rows_ref(x48, v0, [1027])
+    assert (nbits(q) != nbits(ref.centered_l2sq_rows_ref(x48, v0, [1027], wave_order=(3, 2, 1, 0)))).sum() >= 8
+    image = torch.tensor([row[0].data_ptr() for row in held] + [1027] * 48 + [vheld[0][2].data_ptr()] * 48,
+                         dtype=torch.int64, device=cuda)
+    assert_bits(kernels.center_l2sq_rows(image, 48, 1027), q, "48 rows of 1027, restated order")
 
 
 # ------------------------------------------------------------------ 3. the whole round, closed
-def check_round(x, v, tau, L, centre, distances, factors, what):
+def check_round(x, v, tau, L, centre, distances, factors, what, sizes):
     """factors = f(distances) bit for bit; the centre is the restatement's folds driven by these
-    factors; each distance within 2e-6 of the float64 distance to the restatement's centre."""
+    factors; each distance bit for bit centered_distances_ref's, from the restatement's own running
+    centre and summed over the leaf cut `sizes` ([P]: the row as one leaf), and, independently,
+    within 2e-6 of the float64 distance to that centre."""
+    sizes = [int(n) for n in sizes]
     distances, factors = host(distances), host(factors)
     assert distances.shape == factors.shape == (L, x.shape[0]), what
     cur = np.asarray(v, dtype=F32)
     for l in range(L):
         assert_bits(factors[l], cm.clip_factors_ref(distances[l], tau), f"{what}: factors[{l}]")
+        assert_bits(distances[l], ref.centered_distances_ref(x, cur, sizes), f"{what}: distances[{l}], restated order")
         want = ref.centered_distances_f64(x, cur)
         with np.errstate(all="ignore"):
             over = np.isfinite(want) & (want * want > 3.5e38)  # the float32 squares overflow: n = inf
@@ -320,7 +343,7 @@ def test_whole_round_closed(cuda, L):
     for name, tau in taus(x, v).items():
         what = f"L={L} tau={name}"
         a = s.centered_clip(tau, vd, iterations=L)
-        check_round(x, v, tau, L, flat_of(a.center), a.distances, a.factors, what + " slab")
+        check_round(x, v, tau, L, flat_of(a.center), a.distances, a.factors, what + " slab", np.diff(offs))
         fa = host(a.factors)
         if name == "median":
             assert (fa[0] < 1).sum() in (K // 2, K // 2 + 1)
@@ -331,7 +354,7 @@ def test_whole_round_closed(cuda, L):
         b = tu.tree_centered_clip(iter(clients), tau, vtree, iterations=L)  # a one-shot iterable
         assert pytree.flatten(b.center)[1] == pytree.flatten(vtree)[1]
         assert b.center["zero"].numel() == 0 and b.center["one"].numel() == 1
-        check_round(x, v, tau, L, flat_of(b.center), b.distances, b.factors, what + " tree")
+        check_round(x, v, tau, L, flat_of(b.center), b.distances, b.factors, what + " tree", np.diff(offs))
         # the two routes, bit for bit
         assert_bits(flat_of(b.center), flat_of(a.center), what + " slab against tree")
         assert_bits(b.distances, host(a.distances), what + " distances, slab against tree")
@@ -342,12 +365,12 @@ def test_whole_round_closed(cuda, L):
         # the two C drivers on their own: the row as one leaf (another norm order, the same contract)
         xd = on_device(x, cuda, ld=x.shape[1] + 3, offset=1)
         out, dist, fac = kernels.centered_clip_dense(xd, tau, vd, iterations=L)
-        check_round(x, v, tau, L, out, dist, fac, what + " dense driver")
+        check_round(x, v, tau, L, out, dist, fac, what + " dense driver", [x.shape[1]])
         res = torch.full((x.shape[1],), float("nan"), dtype=torch.float32, device=cuda)
         rows = xd.data_ptr() + 4 * np.arange(K, dtype=np.int64)[:, None] * xd.stride(0)
         image, nblk = plan_image(rows, [res.data_ptr()], [x.shape[1]], [vd.data_ptr()], cuda)
         dist2, fac2 = kernels.centered_clip_ptrs(image, 1, K, nblk, x.shape[1], tau, iterations=L)
-        check_round(x, v, tau, L, res, dist2, fac2, what + " ptrs driver")
+        check_round(x, v, tau, L, res, dist2, fac2, what + " ptrs driver", [x.shape[1]])
         assert_bits(res, host(out), what + " the two drivers")
         assert_bits(dist2, host(dist), what + " the two drivers' distances")
     assert_bits(vd, v, "the centre is not written")
@@ -361,7 +384,8 @@ def test_default_centre_is_zeros_and_empty_rounds(cuda):
     s = emnist_slab(x, cuda)
     tau = taus(x, np.zeros(x.shape[1], F32))["median"]
     a = s.centered_clip(tau, iterations=2)
-    check_round(x, np.zeros(x.shape[1], F32), tau, 2, flat_of(a.center), a.distances, a.factors, "slab, no centre")
+    check_round(x, np.zeros(x.shape[1], F32), tau, 2, flat_of(a.center), a.distances, a.factors, "slab, no centre",
+                np.diff(offs))
     b = tu.tree_centered_clip(separate_clients(x, offs, cuda), tau, iterations=2)
     assert_bits(flat_of(b.center), flat_of(a.center), "tree, no centre")
     assert tu.tree_centered_clip([], 1.0) is None
@@ -399,7 +423,7 @@ def byzantine_bound(x, v, fac, nbyz, tau):
 
 def test_attacks(cuda):
     K = 16
-    x0, v, _ = emnist_round(K)
+    x0, v, offs = emnist_round(K)
     vd = torch.from_numpy(np.array(v)).to(cuda)
     tau = taus(x0, v)["median"]
     for name, fill in (("NaN", np.nan), ("1e30", 1e30)):
@@ -417,7 +441,7 @@ def test_attacks(cuda):
         got = s.centered_clip(tau, vd, iterations=2)
         centre = flat_of(got.center)
         assert np.isfinite(centre).all(), name
-        check_round(x, v, tau, 2, centre, got.distances, got.factors, f"{name} row")
+        check_round(x, v, tau, 2, centre, got.distances, got.factors, f"{name} row", np.diff(offs))
         f = host(got.factors)[:, 3]
         assert np.isnan(f).all() if name == "NaN" else (f == 0).all()
     rng = np.random.RandomState(5)
@@ -478,7 +502,7 @@ def test_capture_and_replay(cuda):
         eager = s.centered_clip(tau, center=buf, iterations=2, out=buf)
         assert_bits(replayed, host(buf), f"replay {seed}")
         assert_bits(rf, host(eager.factors), f"replay {seed} factors")
-        check_round(x2, v2, tau, 2, replayed, eager.distances, eager.factors, f"replay {seed}")
+        check_round(x2, v2, tau, 2, replayed, eager.distances, eager.factors, f"replay {seed}", np.diff(offs))
     clients = separate_clients(x, offs, cuda)
     vtree = s.unflatten(torch.from_numpy(np.array(v)).to(cuda))
     want = flat_of(tu.tree_centered_clip(clients, tau, vtree).center)

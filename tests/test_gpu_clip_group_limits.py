@@ -26,6 +26,7 @@ import torch
 from fedjax_amd import _lib, kernels, pytree, slab as slab_mod, tree_util as tu
 from tests import clipped_mean_ref as cref
 from tests import grouped_mean_ref as gref
+from tests.clipped_mean_ref import l2sq_rows_ref
 from tests.test_gpu_clip_group_fuzz import assert_bits, check_clipped, flat
 
 pytestmark = pytest.mark.gpu
@@ -181,31 +182,6 @@ def test_norm_pass_over_more_than_65535_rows(cuda):
     # clients on both sides of the split (row 1023 is the first launch's last) are clipped or not by
     # their OWN norm: a norm written to another client's slot would fail the 2e-6 bound above
     assert [tuple(t.shape) for t in got.mean] == [(n,) for n in sizes]
-
-
-def l2sq_rows_ref(leaves):
-    """fjagg_l2sq_rows's sum of one client's squares, restated in numpy float32: every leaf in
-    64 Ki-element blocks; in a block lane t of 256 adds the squares of elements t, t + 256, ... in
-    that order from +0; the 64 lanes of a wave are added by an xor butterfly (32, 16, ... 1), the
-    four waves in order; then the block partials in leaf / block order from +0."""
-    s = F32(0)
-    for a in leaves:
-        a = np.asarray(a, dtype=F32).reshape(-1)
-        for b0 in range(0, max(a.size, 1), 65536):
-            sq = a[b0:b0 + 65536] * a[b0:b0 + 65536]
-            m = np.zeros((sq.size + 255) // 256 * 256, dtype=F32)  # (+0 where a lane has no element:
-            m[:sq.size] = sq                                        # adding it changes nothing)
-            acc = np.zeros(256, dtype=F32)
-            for row in m.reshape(-1, 256):
-                acc = acc + row
-            w = acc.reshape(4, 64)
-            for o in (32, 16, 8, 4, 2, 1):
-                w = w + w[:, np.arange(64) ^ o]
-            t = w[0, 0]
-            for i in range(1, 4):
-                t = t + w[i, 0]
-            s = s + t
-    return s
 
 
 def test_norm_rows_keep_their_summation_order(cuda):
