@@ -109,6 +109,12 @@ _SIGNATURES = {
     "fjagg_center_clip_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp,
                                        _vp, _i64, _i32, _vp]),
     "fjagg_center_clip_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "fjagg_krum_select": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjagg_weiszfeld_select": (_i32, [_vp, _i64, _vp, ctypes.c_double, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    "fjagg_wsum_group_dense_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_wsum_group_ptrs_dev": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_gather_member_ptrs": (_i32, [_vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

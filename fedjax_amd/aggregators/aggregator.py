@@ -237,7 +237,19 @@ class KrumAggregatorState:
     scores: Dict[ClientId, float] = std_dataclasses.field(default_factory=dict)
 
 
-def krum_aggregator(num_byzantine: int, num_selected: int = 1) -> Aggregator:
+@dataclasses.dataclass
+class DeviceKrumAggregatorState:
+    """The last round's selection with ``select="device"``, still on the device: ``client_ids`` —
+    the round's ids in client order; ``selected`` — int64 device tensor of indices into them,
+    best first, -1 padded; ``count`` — int32 device scalar, how many were selected; ``scores`` —
+    float64 device tensor, one per client. Reading any of them is the caller's synchronisation."""
+    client_ids: Tuple[ClientId, ...] = ()
+    selected: Any = None
+    count: Any = None
+    scores: Any = None
+
+
+def krum_aggregator(num_byzantine: int, num_selected: int = 1, *, select: str = "host") -> Aggregator:
     """Builds the Krum (``num_selected = 1``) / multi-Krum aggregator of Blanchard et al.
     (NeurIPS 2017): :func:`fedjax_amd.tree_util.tree_krum` of the round's params — the mean of
     the ``num_selected`` clients closest to their ``K - num_byzantine - 2`` nearest neighbours.
@@ -245,7 +257,13 @@ def krum_aggregator(num_byzantine: int, num_selected: int = 1) -> Aggregator:
 
     ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
     client must not be able to scale its own vote. It returns ``None`` for a round with no
-    clients or no selectable client. Float32 params, at most 1024 clients a round."""
+    clients or no selectable client. Float32 params, at most 1024 clients a round.
+
+    ``select="device"`` runs the selection on the device (``tree_krum(..., select="device")``): no
+    host step between the two passes. The mean of a round without a selectable client is then all
+    +0 instead of ``None``, and the state is a :class:`DeviceKrumAggregatorState` of device
+    tensors."""
+    device = kernels.check_select(select)
     if isinstance(num_byzantine, (bool, np.bool_)) or not isinstance(num_byzantine, (int, np.integer)):
         raise TypeError("num_byzantine must be an int")
     if isinstance(num_selected, (bool, np.bool_)) or not isinstance(num_selected, (int, np.integer)):
@@ -258,6 +276,13 @@ def krum_aggregator(num_byzantine: int, num_selected: int = 1) -> Aggregator:
 
     def apply(clients_params_and_weights, state):
         triples = list(clients_params_and_weights)  # the weights are not used
+        if device:
+            got = tree_util.tree_krum([param for _, param, _ in triples], num_byzantine, num_selected,
+                                      select="device")
+            if got is None:
+                return None, DeviceKrumAggregatorState()
+            return got.mean, DeviceKrumAggregatorState(tuple(cid for cid, _, _ in triples), got.selected,
+                                                       got.count, got.scores)
         got = tree_util.tree_krum([param for _, param, _ in triples], num_byzantine, num_selected)
         if got is None:
             return None, KrumAggregatorState()
@@ -336,13 +361,30 @@ class GeometricMedianAggregatorState:
     weights: Dict[ClientId, float] = std_dataclasses.field(default_factory=dict)
 
 
-def geometric_median_aggregator(iterations: int = 4, nu: float = 1e-6) -> Aggregator:
+@dataclasses.dataclass
+class DeviceGeometricMedianAggregatorState:
+    """The last round's Weiszfeld weights with ``select="device"``, still on the device:
+    ``client_ids`` — the round's ids in client order; ``weights`` — float32 device tensor, one per
+    client (0 for an unusable one); ``count`` — int32 device scalar, the clients with a positive
+    weight."""
+    client_ids: Tuple[ClientId, ...] = ()
+    weights: Any = None
+    count: Any = None
+
+
+def geometric_median_aggregator(iterations: int = 4, nu: float = 1e-6, *, select: str = "host") -> Aggregator:
     """Builds the geometric-median aggregator ("RFA", Pillutla et al., IEEE TSP 2022):
     :func:`fedjax_amd.tree_util.tree_geometric_median` of the round's params with unit client
     weights, ``iterations`` smoothed Weiszfeld steps with smoothing ``nu``.
 
     ``apply`` takes the usual triples and IGNORES the weights. It returns ``None`` for a round
-    with no clients or no usable client. Float32 params, at most 1024 clients a round."""
+    with no clients or no usable client. Float32 params, at most 1024 clients a round.
+
+    ``select="device"`` runs the iteration on the device
+    (``tree_geometric_median(..., select="device")``): no host step between the two passes. The
+    median of a round without a usable client is then all +0 instead of ``None``, and the state is
+    a :class:`DeviceGeometricMedianAggregatorState` of device tensors."""
+    device = kernels.check_select(select)
     if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
         raise TypeError("iterations must be an int")
     if iterations < 0:
@@ -357,6 +399,13 @@ def geometric_median_aggregator(iterations: int = 4, nu: float = 1e-6) -> Aggreg
 
     def apply(clients_params_and_weights, state):
         triples = list(clients_params_and_weights)  # the weights are not used
+        if device:
+            got = tree_util.tree_geometric_median([param for _, param, _ in triples], iterations=iterations, nu=nu,
+                                                  select="device")
+            if got is None:
+                return None, DeviceGeometricMedianAggregatorState()
+            return got.median, DeviceGeometricMedianAggregatorState(tuple(cid for cid, _, _ in triples),
+                                                                    got.weights, got.count)
         got = tree_util.tree_geometric_median([param for _, param, _ in triples], iterations=iterations, nu=nu)
         if got is None:
             return None, GeometricMedianAggregatorState()

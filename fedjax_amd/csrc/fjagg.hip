@@ -3626,6 +3626,64 @@ int fjagg_wsum_group_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t
   return launch_ptrs_group(f, vec, nt, nblk, (int)G, nonempty, s);
 }
 
+/* ONE group whose tables a kernel wrote (fjagg_krum_select / fjagg_weiszfeld_select; fjagg.h): the
+ * fold above without the host copies, its shape picked from the bound M_max on the member count */
+int fjagg_wsum_group_dense_dev(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M_max,
+                               const int32_t* order_dev, const int32_t* seg_dev, const float* wperm_dev,
+                               const float* gscale_dev, void* out_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (K > 0x7fffffffll) return fail(FJAGG_EUNSUPPORTED, "grouped fold: K < 2^31");
+  if (M_max < 1 || M_max > K)
+    return fail(FJAGG_EINVAL, "M_max must be in [1, K] = [1, %lld] (got %lld)", (long long)K, (long long)M_max);
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld");
+  if (P * 4 > kMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "grouped fold: rows <= 1 GiB");
+  if (!x_dev || !out_dev || !order_dev || !seg_dev || !wperm_dev || ((flags & FJAGG_SCALE) && !gscale_dev))
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  const uint8_t* x = reinterpret_cast<const uint8_t*>(x_dev);
+  uint8_t* y = reinterpret_cast<uint8_t*>(out_dev);
+  const int variant = group_dense_shape(x, ld, P, M_max, 1, 1, y, P);
+  const bool vec = variant != 0;
+  const int V = vec ? 4 : 1;
+  GroupArgs a;
+  a.x = x;
+  a.ld_bytes = ld * 4;
+  a.nunits = P / V;
+  a.tail_n = (int)(P - a.nunits * V);
+  a.order = order_dev;
+  a.seg = seg_dev;
+  a.gorder = nullptr;
+  a.wperm = wperm_dev;
+  a.gscale = gscale_dev;
+  a.G = 1;
+  a.do_scale = (flags & FJAGG_SCALE) ? 1 : 0;
+  a.out = y;
+  a.out_stride = P * 4;
+  a.nonempty = 1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return (flags & FJAGG_NONTEMPORAL) ? launch_dense_group<true>(GroupDense{}, vec, variant, a, s)
+                                     : launch_dense_group<false>(GroupDense{}, vec, variant, a, s);
+}
+
+int fjagg_wsum_group_ptrs_dev(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M_max, int64_t nblk,
+                              const int32_t* seg_dev, const float* wperm_dev, const float* gscale_dev, int flags,
+                              void* stream) {
+  g_err[0] = 0;
+  if (int rc = group_flags_check(in_dtype, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (K > 0x7fffffffll) return fail(FJAGG_EUNSUPPORTED, "grouped fold: K < 2^31");
+  if (M_max < 1 || M_max > K)
+    return fail(FJAGG_EINVAL, "M_max must be in [1, K] = [1, %lld] (got %lld)", (long long)K, (long long)M_max);
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1) return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!image_dev || !seg_dev || !wperm_dev || ((flags & FJAGG_SCALE) && !gscale_dev))
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = !(flags & FJAGG_UNALIGNED), nt = (flags & FJAGG_NONTEMPORAL) != 0;
+  const GroupPtrs f{{image_dev, L, M_max, seg_dev, wperm_dev, gscale_dev, nullptr, 1}, (flags & FJAGG_SCALE) ? 1 : 0};
+  return launch_ptrs_group(f, vec, nt, nblk, 1, 1, s);
+}
+
 // ------------------------- grouped fold + per-cluster server step (fjagg.h; hyp_cluster.py:107-128)
 namespace {
 extern "C++" {

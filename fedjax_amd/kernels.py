@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -967,6 +967,146 @@ def gram_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, out: Optional[
     _lib.call("fjagg_gram_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, out.data_ptr(), ws.data_ptr(),
               ws.numel(), _lib.UNALIGNED if unaligned else 0, _stream_handle(dev))
     return out
+
+
+class DeviceGroupTables(NamedTuple):
+    """The member tables of ONE group as a select kernel wrote them (fjagg.h: ``order[M_max]``,
+    ``seg[2]``, ``wperm[M_max]``, ``gscale[1]``, all on the device) and the bound ``M_max`` on
+    the member count that the fold's kernel shape is picked from."""
+    order: torch.Tensor
+    seg: torch.Tensor
+    wperm: torch.Tensor
+    gscale: torch.Tensor
+    M_max: int
+
+
+def _check_select_gram(gram: torch.Tensor) -> int:
+    if not isinstance(gram, torch.Tensor) or gram.dim() != 2 or gram.shape[0] != gram.shape[1] \
+            or gram.dtype != torch.float64 or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous float64 [K, K] device tensor")
+    K = _check_gram_clients(gram.shape[0])
+    _require_device(gram)
+    return K
+
+
+def _select_tables(M_max: int, dev: torch.device) -> DeviceGroupTables:
+    ints = torch.empty(M_max + 2, dtype=torch.int32, device=dev)  # order | seg
+    floats = torch.empty(M_max + 1, dtype=torch.float32, device=dev)  # wperm | gscale
+    return DeviceGroupTables(ints[:M_max], ints[M_max:], floats[:M_max], floats[M_max:], M_max)
+
+
+def krum_select_device(gram: torch.Tensor, f: int, m: int):
+    """Krum / multi-Krum's selection on the device over a float64 ``[K, K]`` Gram matrix
+    (``fjagg_krum_select``): bit for bit :func:`fedjax_amd.robust.krum_scores` and
+    ``krum_select`` of the same matrix. Returns ``(scores, selected, count, tables)``, all on
+    the device: ``scores`` float64 [K]; ``selected`` int64 [m], best first, -1 padded; ``count``
+    int32 scalar, the number of finite scores taken; ``tables`` the
+    :class:`DeviceGroupTables` of :func:`grouped_sum_dense_device` (members in ascending client
+    index, unit weights, ``gscale = f32(1 / count)``). Two small launches, no host
+    synchronisation, nothing uploaded: capturable. ``K >= 2f + 3``, ``1 <= m <= K - f``."""
+    from fedjax_amd import robust
+
+    K = _check_select_gram(gram)
+    f, m = robust.check_krum_args(K, f, m)  # the host route's argument checks and exceptions
+    dev = gram.device
+    scores = torch.empty(K, dtype=torch.float64, device=dev)
+    selected = torch.empty(m, dtype=torch.int64, device=dev)
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    tables = _select_tables(m, dev)
+    _lib.call("fjagg_krum_select", gram.data_ptr(), K, f, m, scores.data_ptr(), selected.data_ptr(), count.data_ptr(),
+              tables.order.data_ptr(), tables.seg.data_ptr(), tables.wperm.data_ptr(), tables.gscale.data_ptr(),
+              _stream_handle(dev))
+    return scores, selected, count, tables
+
+
+def weiszfeld_select_device(gram: torch.Tensor, alpha=None, nu: float = 1e-6, iterations: int = 4):
+    """The smoothed Weiszfeld iteration on the device over a float64 ``[K, K]`` Gram matrix
+    (``fjagg_weiszfeld_select``; the rule of :func:`fedjax_amd.robust.weiszfeld_weights` with
+    the order of every sum pinned: over the usable clients in ascending index, sequentially).
+    ``alpha``: ``None`` for unit weights (nothing is uploaded), a float64 ``[K]`` device tensor,
+    or host numbers, which are checked as the host route checks them and uploaded once (refused
+    under stream capture). Returns ``(a, d, a32, count, tables)``, all on the device: the final
+    weights and last distances (float64 [K]), ``a32 = float32(a)``, the number of clients with
+    ``a32 > 0`` (int32 scalar) and the :class:`DeviceGroupTables` of the fold (those clients in
+    ascending index, ``wperm = a32``, ``gscale = f32(1 / sum a32)``). One launch of one
+    workgroup, no host synchronisation."""
+    from fedjax_amd import robust
+
+    K = _check_select_gram(gram)
+    dev = gram.device
+    if isinstance(alpha, torch.Tensor):
+        if alpha.dtype != torch.float64 or tuple(alpha.shape) != (K,) or not alpha.is_contiguous():
+            raise ValueError(f"a device alpha must be a contiguous float64 [{K}] tensor")
+        _require_device(gram, alpha)
+        robust.weiszfeld_weights(np.eye(1), None, nu, iterations)
+        alpha_dev = alpha
+    else:
+        host = None if alpha is None else np.asarray(alpha)
+        robust.weiszfeld_weights(np.eye(1) if host is None else np.eye(K), host, nu, 0)
+        robust.weiszfeld_weights(np.eye(1), None, nu, iterations)
+        alpha_dev = None if host is None else _lib.upload(torch.from_numpy(host.astype(np.float64)), dev)
+    a = torch.empty(K, dtype=torch.float64, device=dev)
+    d = torch.empty(K, dtype=torch.float64, device=dev)
+    a32 = torch.empty(K, dtype=torch.float32, device=dev)
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    tables = _select_tables(K, dev)
+    _lib.call("fjagg_weiszfeld_select", gram.data_ptr(), K, 0 if alpha_dev is None else alpha_dev.data_ptr(),
+              float(nu), int(iterations), a.data_ptr(), d.data_ptr(), a32.data_ptr(), count.data_ptr(),
+              tables.order.data_ptr(), tables.seg.data_ptr(), tables.wperm.data_ptr(), tables.gscale.data_ptr(),
+              _stream_handle(dev))
+    return a, d, a32, count, tables
+
+
+def grouped_sum_dense_device(x: torch.Tensor, tables: DeviceGroupTables, out: torch.Tensor, *,
+                             nontemporal: bool = False) -> torch.Tensor:
+    """The scaled exact fold of ONE group of a float32 slab ``x[K, P]`` whose member tables a
+    select kernel wrote (``fjagg_wsum_group_dense_dev``): :func:`grouped_sum_dense`'s arithmetic
+    and kernels, no host copy of the tables, nothing uploaded. ``out``: float32 ``[P]``; a group
+    without members writes nothing, so the caller zeroes ``out`` first."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the grouped fold takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if tuple(out.shape) != (P,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 [{P}] tensor")
+    dev = _require_device(x, out, tables.order, tables.seg, tables.wperm, tables.gscale)
+    _lib.call("fjagg_wsum_group_dense_dev", _lib.F32, x.data_ptr(), x.stride(0) if K > 1 else P, K, P, tables.M_max,
+              tables.order.data_ptr(), tables.seg.data_ptr(), tables.wperm.data_ptr(), tables.gscale.data_ptr(),
+              out.data_ptr(), _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), _stream_handle(dev))
+    return out
+
+
+def grouped_sum_ptrs_device(image_all: torch.Tensor, image_group: torch.Tensor, L: int, K: int, nblk: int,
+                            tables: DeviceGroupTables, *, nontemporal: bool = False) -> None:
+    """The same over a pytree plan: ``fjagg_gather_member_ptrs`` copies the members' leaf
+    pointers from ``image_all`` (``in_ptrs[K*L]``, the Gram pass's image) into ``image_group``
+    (``in_ptrs[M_max*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk]``), then
+    ``fjagg_wsum_group_ptrs_dev`` folds them into ``out_ptrs``."""
+    for name, t in (("image_all", image_all), ("image_group", image_group)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous int64 device tensor")
+    L, K, nblk, M = int(L), int(K), int(nblk), tables.M_max
+    if L < 1 or nblk < 1 or image_all.numel() < K * L or image_group.numel() < M * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, images of {image_all.numel()} and "
+                         f"{image_group.numel()} words")
+    dev = _require_device(image_all, image_group, tables.seg, tables.wperm, tables.gscale)
+    s = _stream_handle(dev)
+    _lib.call("fjagg_gather_member_ptrs", image_all.data_ptr(), L, K, tables.order.data_ptr(), tables.seg.data_ptr(),
+              M, image_group.data_ptr(), s)
+    _lib.call("fjagg_wsum_group_ptrs_dev", _lib.F32, image_group.data_ptr(), L, K, M, nblk, tables.seg.data_ptr(),
+              tables.wperm.data_ptr(), tables.gscale.data_ptr(),
+              _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), s)
+
+
+def check_select(select) -> bool:
+    """``select="host" | "device"`` of the Krum and geometric-median surfaces: True for the
+    device route; ValueError for anything else."""
+    if select == "host":
+        return False
+    if select == "device":
+        return True
+    raise ValueError(f'select must be "host" or "device", got {select!r}')
 
 
 CENTER_MAX_CLIENTS = 4096  # fjagg_center_*: the clipped fold's client limit (fjagg.h)

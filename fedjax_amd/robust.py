@@ -25,7 +25,8 @@ from typing import Tuple
 
 import numpy as np
 
-__all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "bulyan_select", "weiszfeld_weights"]
+__all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "check_krum_args", "bulyan_select",
+           "weiszfeld_weights"]
 
 
 def _gram(G) -> np.ndarray:
@@ -103,6 +104,17 @@ def krum_select(G, f, m=1) -> np.ndarray:
     order = np.argsort(scores, kind="stable")
     order = order[np.isfinite(scores[order])]
     return order[:m].astype(np.int64)
+
+
+def check_krum_args(K: int, f, m) -> Tuple[int, int]:
+    """:func:`krum_select`'s conditions on the client count alone, with its exceptions and
+    nothing computed: int ``f >= 0`` and ``m`` (a bool is refused), ``K >= 2f + 3``,
+    ``1 <= m <= K - f``. Returns ``(f, m)``."""
+    f = _check_krum(K, f)
+    m = _int("num_selected", m)
+    if not (1 <= m <= K - f):
+        raise ValueError(f"num_selected must be in [1, K - f] = [1, {K - f}], got {m}")
+    return f, m
 
 
 def check_bulyan(K: int, f) -> int:

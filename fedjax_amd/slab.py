@@ -401,7 +401,19 @@ class ClientDeltaSlab:
             return kernels._check_gram_out(out, K, self.device).zero_()
         return kernels.gram_dense(self.rows, out=out)
 
-    def krum(self, num_byzantine, num_selected=1) -> "tree_util.KrumResult":
+    def _fold_selected(self, tables: "kernels.DeviceGroupTables") -> PyTree:
+        """The device routes' second pass: a zeroed result (a fill kernel, so a graph replay zeroes
+        too), then the grouped fold over the member tables a select kernel wrote
+        (:func:`kernels.grouped_sum_dense_device`), which writes nothing for an empty group."""
+        out = torch.empty(self.row_stride, dtype=torch.float32, device=self.device)
+        out.zero_()
+        if self.num_params:  # (a template of empty leaves: nothing to fold)
+            nbytes = tables.M_max * self.num_params * 4
+            kernels.grouped_sum_dense_device(self.rows, tables, out[: self.num_params],
+                                             nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return self.unflatten(out)
+
+    def krum(self, num_byzantine, num_selected=1, *, select: str = "host"):
         """Krum (``num_selected = 1``) and multi-Krum (Blanchard et al., NeurIPS 2017) over the
         rows: client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
         other clients, ``f = num_byzantine``, and the ``num_selected`` clients of smallest
@@ -413,7 +425,22 @@ class ClientDeltaSlab:
         1e30 cannot reach the result. ``num_selected = 1`` gives the chosen client's delta
         (times f32(1), from a +0 start). There are no client weights. Returns a
         :class:`~fedjax_amd.tree_util.KrumResult`; ``mean`` is ``None`` when no client has a
-        finite score. A float32 slab of up to 1024 clients. Raises under stream capture."""
+        finite score. A float32 slab of up to 1024 clients. Raises under stream capture.
+
+        ``select="device"`` keeps the round on the device: :meth:`gram`, ``fjagg_krum_select``
+        (the same scores and winners, bit for bit), the result zeroed, then the grouped fold over
+        the member tables the kernel wrote. No device-to-host copy, no synchronisation, nothing
+        uploaded: the round can be captured into a graph and replayed over rewritten deltas, and
+        each replay selects afresh. The argument checks and their exceptions are the same.
+        Returns a :class:`~fedjax_amd.tree_util.DeviceKrumResult` of device tensors; ``mean`` is
+        all +0 when no client has a finite score (never ``None``)."""
+        if kernels.check_select(select):
+            if self.dtype != torch.float32:
+                raise TypeError(f"krum needs a float32 slab, not {self.dtype}")
+            tree_util._check_krum_args_only(self.num_clients, num_byzantine, num_selected)
+            gram = self.gram()
+            scores, selected, count, tables = kernels.krum_select_device(gram, num_byzantine, num_selected)
+            return tree_util.DeviceKrumResult(self._fold_selected(tables), selected, count, scores, gram)
         kernels.refuse_capture("krum", kernels._TWO_PASS)
         if self.dtype != torch.float32:
             raise TypeError(f"krum needs a float32 slab, not {self.dtype}")
@@ -424,7 +451,7 @@ class ClientDeltaSlab:
         return tree_util.KrumResult(mean, selected, scores, gram)
 
     def geometric_median(self, weights: Optional[Sequence] = None, *, iterations=4,
-                         nu=1e-6) -> "tree_util.GeometricMedianResult":
+                         nu=1e-6, select: str = "host"):
         """The geometric median of the rows by the smoothed Weiszfeld algorithm ("RFA", Pillutla
         et al., IEEE TSP 2022), ``weights`` the clients' positive weights alpha (default all 1).
         All ``iterations`` run on the host over the Gram matrix
@@ -434,7 +461,26 @@ class ClientDeltaSlab:
         with a non-finite value. ``iterations = 0`` is the alpha-weighted mean of the usable
         clients. Returns a :class:`~fedjax_amd.tree_util.GeometricMedianResult`; ``median`` is
         ``None`` when no client is usable. A float32 slab of up to 1024 clients. Raises under
-        stream capture."""
+        stream capture.
+
+        ``select="device"`` keeps the round on the device: :meth:`gram`,
+        ``fjagg_weiszfeld_select`` (the same rule with the order of every sum pinned, so the
+        weights agree with the host route's to a few float64 roundings, not bit for bit), the
+        result zeroed, then the grouped fold over the tables the kernel wrote. No device-to-host
+        copy and no synchronisation; ``weights`` are uploaded once (which a capture refuses),
+        ``None`` uploads nothing and can be captured. The argument checks and their exceptions
+        are the same. Returns a :class:`~fedjax_amd.tree_util.DeviceGeometricMedianResult`;
+        ``median`` is all +0 when no client is usable (never ``None``)."""
+        if kernels.check_select(select):
+            if self.dtype != torch.float32:
+                raise TypeError(f"geometric_median needs a float32 slab, not {self.dtype}")
+            weights = None if weights is None else list(weights)
+            tree_util._check_median_args(self.num_clients, weights, iterations, nu)
+            tree_util._check_median_iterations(iterations, nu)
+            alpha = None if weights is None else np.array([tree_util._host_weight(w) for w in weights], np.float64)
+            gram = self.gram()
+            _, d, a32, count, tables = kernels.weiszfeld_select_device(gram, alpha, nu, iterations)
+            return tree_util.DeviceGeometricMedianResult(self._fold_selected(tables), a32, d, count, gram)
         kernels.refuse_capture("geometric_median", kernels._TWO_PASS)
         if self.dtype != torch.float32:
             raise TypeError(f"geometric_median needs a float32 slab, not {self.dtype}")

@@ -47,6 +47,7 @@ __all__ = [
     "tree_dp_clipped_mean",
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
     "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
+    "DeviceKrumResult", "DeviceGeometricMedianResult",
     "tree_mean_around_median", "tree_bulyan", "BulyanResult",
     "tree_centered_clip", "CenteredClip",
 ]
@@ -2285,6 +2286,33 @@ class GeometricMedianResult(NamedTuple):
     gram: Any
 
 
+class DeviceKrumResult(NamedTuple):
+    """Result of Krum / multi-Krum with ``select="device"``: nothing of it has visited the host.
+    ``mean`` — the plain mean of the selected clients' deltas, all +0 when none could be
+    selected (never ``None``: the count is not known on the host); ``selected`` — int64 device
+    tensor [num_selected], best first, padded with -1; ``count`` — int32 device scalar, how many
+    were selected; ``scores`` — float64 device tensor [K]; ``gram`` — the float64 ``[K, K]``
+    Gram matrix. Read ``count`` when you want to: that is the only synchronisation."""
+    mean: Any
+    selected: Any
+    count: Any
+    scores: Any
+    gram: Any
+
+
+class DeviceGeometricMedianResult(NamedTuple):
+    """Result of the geometric median with ``select="device"``: ``median`` — ``sum_k a_k x_k``,
+    all +0 when no client is usable (never ``None``); ``weights`` — the float32 ``a_k`` the fold
+    used (device tensor [K]); ``distances`` — the last iteration's ``|v - x_k|`` (float64
+    device tensor [K]); ``count`` — int32 device scalar, the clients with a positive weight;
+    ``gram`` — the float64 ``[K, K]`` Gram matrix."""
+    median: Any
+    weights: Any
+    distances: Any
+    count: Any
+    gram: Any
+
+
 def _krum_plan(G: np.ndarray, num_byzantine, num_selected):
     """(selected, scores, fold weights, fold ids) of a Krum round over the host Gram ``G``."""
     from fedjax_amd import robust
@@ -2315,6 +2343,14 @@ def _check_krum_args(K: int, num_byzantine, num_selected) -> None:
     robust.krum_select(np.eye(K), num_byzantine, num_selected)
 
 
+def _check_krum_args_only(K: int, num_byzantine, num_selected) -> None:
+    """:func:`_check_krum_args` with nothing computed (the device route: no Krum of an identity)."""
+    from fedjax_amd import robust
+
+    kernels._check_gram_clients(K)
+    robust.check_krum_args(K, num_byzantine, num_selected)
+
+
 def _check_median_args(K: int, weights, iterations, nu) -> None:
     from fedjax_amd import robust
 
@@ -2323,6 +2359,14 @@ def _check_median_args(K: int, weights, iterations, nu) -> None:
         raise ValueError(f"need {K} weights, got {len(weights)}")
     alpha = None if weights is None else np.array([_host_weight(w) for w in weights], dtype=np.float64)
     robust.weiszfeld_weights(np.eye(1) if alpha is None else np.eye(K), alpha, nu, 0)
+
+
+def _check_median_iterations(iterations, nu) -> None:
+    """``iterations`` as the host route's selection checks it after the Gram pass; the device
+    route asks before any launch."""
+    from fedjax_amd import robust
+
+    robust.weiszfeld_weights(np.eye(1), None, nu, iterations)
 
 
 def tree_gram(pytrees: Iterable[PyTree]) -> Optional[torch.Tensor]:
@@ -2361,7 +2405,51 @@ def _tree_gram(trees: list):
     return kernels.gram_ptrs(image_dev, L, K, len(blocks) // 2), td, rows
 
 
-def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1) -> Optional[KrumResult]:
+def _tree_fold_selected(trees: list, M_max: int, select):
+    """The device route of :func:`tree_krum` / :func:`tree_geometric_median`: the Gram pass, then
+    ``select(gram)`` — a :mod:`kernels` select call, whose outputs end with the
+    :class:`kernels.DeviceGroupTables` of at most ``M_max`` members — then the zeroed result and
+    the grouped fold over the members the kernel chose, their leaf pointers gathered on the
+    device. ONE upload holds both plan images (so the call raises under stream capture, as
+    :func:`tree_gram` does); nothing comes back to the host. Returns ``(gram, result pytree,
+    select's outputs)``."""
+    K = kernels._check_gram_clients(len(trees))
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"the Gram matrix needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    device = rows[0][0].device if rows[0] else _default_device()
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    L = len(leaf_n)
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)]).astype(np.int64)
+    flat = torch.empty(max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = pytree.unflatten(td, [flat[o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+    if not leaf_n.any():  # no elements: every inner product is the empty sum, nothing to fold
+        gram = torch.zeros(K, K, dtype=torch.float64, device=device)
+        got = select(gram)
+        flat.zero_()
+        return gram, result, got
+    in_ptrs = _ptr_table(rows)
+    out_ptrs = flat.data_ptr() + 4 * offs[:-1]
+    gram_blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, device)
+    fold_blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)  # any client may become a member
+    all_words = K * L + 2 * L + len(gram_blocks)
+    # in_ptrs[K*L] | (out_ptrs, unread) | leaf_n | blocks, then the group image, whose member slots
+    # in_ptrs[M_max*L] the gather kernel fills
+    image = np.concatenate([in_ptrs.ravel(), np.zeros(L, np.int64), leaf_n, gram_blocks,
+                            np.zeros(M_max * L, np.int64), out_ptrs, leaf_n, fold_blocks])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    image_all, image_group = image_dev[:all_words], image_dev[all_words:]
+    gram = kernels.gram_ptrs(image_all, L, K, len(gram_blocks) // 2)
+    got = select(gram)
+    flat.zero_()
+    nt = int(leaf_n.sum()) * M_max * 4 >= NONTEMPORAL_MIN_BYTES
+    kernels.grouped_sum_ptrs_device(image_all, image_group, L, K, len(fold_blocks) // 2, got[-1], nontemporal=nt)
+    return gram, result, got
+
+
+def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1, *, select: str = "host"):
     """Krum (``num_selected = 1``) and multi-Krum over client pytrees (Blanchard et al., NeurIPS
     2017): client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
     other clients, ``f = num_byzantine``; the ``num_selected`` clients of smallest score are
@@ -2373,7 +2461,22 @@ def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1) -> Optio
     for all others — which are never loaded, so a client full of NaN, inf or 1e30 touches
     nothing. Such a client has a non-finite or huge norm and is not selected. There are no
     client weights: a client must not scale its own vote. Float32 leaves, ``K <= 1024``.
-    Returns a :class:`KrumResult`; no clients: ``None``. Raises under stream capture."""
+    Returns a :class:`KrumResult`; no clients: ``None``. Raises under stream capture.
+
+    ``select="device"`` keeps the round on the device: the Gram pass, ``fjagg_krum_select`` (the
+    same scores and the same winners, bit for bit), the result zeroed, then the grouped fold over
+    member tables the kernel wrote — no device-to-host copy, no synchronisation. The argument
+    checks and their exceptions are the same. Returns a :class:`DeviceKrumResult` whose ``mean``
+    is all +0 when no client could be selected (never ``None``); still raises under stream
+    capture, because the plan image goes through a pinned staging buffer."""
+    if kernels.check_select(select):
+        trees = pytrees if type(pytrees) is list else list(pytrees)
+        if not trees:
+            return None
+        _check_krum_args_only(len(trees), num_byzantine, num_selected)
+        gram, mean, (scores, selected, count, _) = _tree_fold_selected(
+            trees, int(num_selected), lambda g: kernels.krum_select_device(g, num_byzantine, num_selected))
+        return DeviceKrumResult(mean, selected, count, scores, gram)
     kernels.refuse_capture("tree_krum", kernels._TWO_PASS)
     trees = pytrees if type(pytrees) is list else list(pytrees)
     if not trees:
@@ -2386,7 +2489,7 @@ def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1) -> Optio
 
 
 def tree_geometric_median(pytrees: Iterable[PyTree], weights=None, *, iterations=4,
-                          nu=1e-6) -> Optional[GeometricMedianResult]:
+                          nu=1e-6, select: str = "host"):
     """The geometric median of client pytrees by the smoothed Weiszfeld algorithm ("RFA",
     Pillutla et al., IEEE TSP 2022): from ``a = alpha / sum(alpha)`` (``weights``, default all 1),
     ``iterations`` times ``beta_k = alpha_k / max(nu, |v - x_k|)``, ``a = beta / sum(beta)`` with
@@ -2397,7 +2500,26 @@ def tree_geometric_median(pytrees: Iterable[PyTree], weights=None, *, iterations
     ``fl(sum_k x_k f32(a_k)) * f32(1 / sum_k f32(a_k))``, the fold's own normalisation. A client
     with a non-finite value is unusable: weight 0, group -1, never loaded. ``iterations = 0`` is
     the weighted mean of the usable clients. Float32 leaves, ``K <= 1024``. Returns a
-    :class:`GeometricMedianResult`; no clients: ``None``. Raises under stream capture."""
+    :class:`GeometricMedianResult`; no clients: ``None``. Raises under stream capture.
+
+    ``select="device"`` keeps the round on the device: the Gram pass, ``fjagg_weiszfeld_select``
+    (the same rule with the order of every sum pinned: the weights agree with the host route's to
+    a few float64 roundings, not bit for bit), the result zeroed, then the grouped fold over the
+    tables the kernel wrote. ``weights`` are uploaded once; ``None`` uploads nothing. The
+    argument checks and their exceptions are the same. Returns a
+    :class:`DeviceGeometricMedianResult` whose ``median`` is all +0 when no client is usable;
+    still raises under stream capture (the plan image goes through a pinned staging buffer)."""
+    if kernels.check_select(select):
+        trees = pytrees if type(pytrees) is list else list(pytrees)
+        if not trees:
+            return None
+        weights = None if weights is None else list(weights)
+        _check_median_args(len(trees), weights, iterations, nu)
+        _check_median_iterations(iterations, nu)
+        alpha = None if weights is None else np.array([_host_weight(w) for w in weights], dtype=np.float64)
+        gram, median, (_, d, a32, count, _) = _tree_fold_selected(
+            trees, len(trees), lambda g: kernels.weiszfeld_select_device(g, alpha, nu, iterations))
+        return DeviceGeometricMedianResult(median, a32, d, count, gram)
     kernels.refuse_capture("tree_geometric_median", kernels._TWO_PASS)
     trees = pytrees if type(pytrees) is list else list(pytrees)
     if not trees:

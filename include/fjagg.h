@@ -21,6 +21,7 @@
  *     (no reference row) DP-FedAvg's Gaussian mechanism      fjagg_wsum_clip_noise_* (clipped mean + noise)
  *     (no reference row) trimmed mean / median (Yin et al. 2018) fjagg_trim_* (order statistics per coordinate)
  *     (no reference row) Krum / geometric median (Gram matrix)  fjagg_gram_* (K x K inner products, float64)
+ *     (no reference row) Krum / Weiszfeld selection on the device fjagg_krum_select, fjagg_weiszfeld_select
  *     (no reference row) mean around the median / Bulyan        fjagg_meamed_* (the keep values nearest the median)
  *     (no reference row) centered clipping (Karimireddy et al. 2021) fjagg_center_* (clipped around the last aggregate)
  *
@@ -620,8 +621,9 @@ int fjagg_meamed_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, 
  * geometric median (Pillutla, Kakade and Harchaoui, "Robust Aggregation for Federated Learning",
  * IEEE Trans. Signal Processing 2022) is v = sum_j a_j x_j, so |v - x_k|^2 = a'Ga - 2 (Ga)_k + G_kk.
  * The reference has neither aggregator, so there are no reference lines to cite; the semantics
- * are fixed here. The selection itself runs on the host over G
- * (fedjax_amd/robust.py); the final mean is a grouped fold that never loads an excluded client.
+ * are fixed here. The selection itself runs over G, on the host
+ * (fedjax_amd/robust.py) or on the device (fjagg_krum_select, fjagg_weiszfeld_select below); the
+ * final mean is a grouped fold that never loads an excluded client.
  * Float32 deltas, 1 <= K <= 1024, one GPU. Arithmetic:
  *     the columns of a row are cut into chains of at most FJAGG_GRAM_CHAIN consecutive columns
  *       (dense: from column 0, and a workgroup's chunk, fjagg_gram_chunk_columns, is whole chains;
@@ -654,6 +656,69 @@ int fjagg_gram_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
 int64_t fjagg_gram_workspace_bytes(int64_t K, int64_t P_or_total, int64_t nblk);
 /* Columns per workgroup of the dense entry (a multiple of FJAGG_GRAM_CHAIN, a function of K and P alone). */
 int64_t fjagg_gram_chunk_columns(int64_t K, int64_t P);
+
+/*
+ * Krum's and the smoothed Weiszfeld algorithm's selection on the device, over the Gram matrix above
+ * (double[K][K], bitwise symmetric), writing the member tables of ONE group where the grouped fold
+ * reads them: a round is fjagg_gram_* -> select -> fjagg_wsum_group_*_dev with no host visit, no
+ * synchronisation and nothing uploaded, so it can be captured. The reference has neither aggregator;
+ * the semantics are fixed here and in fedjax_amd/csrc/fjselect_dev.h. All arithmetic is
+ * float64 in separate IEEE operations (no FMA, correctly rounded divide and square root); there are
+ * no floating-point atomics, and the order of every sum is a function of (K, f, m) or of
+ * (K, iterations) alone: two runs give the same bits. 1 <= K <= 1024.
+ *     usable_k = isfinite(G_kk)
+ * Krum / multi-Krum (fjagg_krum_select; bit for bit fedjax_amd.robust.krum_scores / krum_select):
+ *     d2(i,j)  = fl(fl(G_ii + G_jj) - fl(2 G_ij)); finite: max(d2, +0), else +inf; +inf when either
+ *                client is unusable; j = i is left out
+ *     score_i  = the K - f - 2 smallest d2(i, .) added in ascending order from 0.0; +inf if unusable
+ *     selected = the m smallest FINITE scores, ties to the lower index; count = how many (0 .. m)
+ *     scores[K]; selected[m] best first, -1 padded; count[1];
+ *     order[m] the selected clients in ASCENDING client index (0 padded); seg = {0, count};
+ *     wperm[m] = 1.0f; gscale[0] = count > 0 ? (float)(1.0 / (double)count) : 0.0f
+ * Two launches: one workgroup per row sorts its K uint64 keys in LDS (the bits of a non-negative
+ * double order as it does) and one lane adds; one workgroup ranks (score, index).
+ * Smoothed Weiszfeld (fjagg_weiszfeld_select), alpha[K] float64 weights (NULL: ones), nu finite
+ * and > 0, iterations >= 0. Every sum runs over the usable clients in ascending index,
+ * sequentially, from 0.0:
+ *     S = sum alpha_k; a_k = alpha_k / S; then `iterations` times
+ *     (Ga)_k = sum_j fl(G_kj a_j);  q = sum_k fl(a_k (Ga)_k);  r_k = fl(fl(q - fl(2 (Ga)_k)) + G_kk)
+ *     d_k = sqrt(r_k > 0 ? r_k : (r_k == r_k ? 0 : r_k));  beta_k = alpha_k / max(nu, d_k) (a NaN
+ *     propagates);  B = sum beta_k;  a_k = beta_k / B
+ *     a[K] (0 if unusable); d[K] (inf if unusable; 0 with iterations = 0); a32[k] = (float)a_k;
+ *     order[K] the clients with usable && a32 > 0, ascending (0 padded); seg = {0, count};
+ *     wperm[j] = that client's a32 (0 padded); gscale[0] = W > 0 ? (float)(1.0 / W) : 0, W the
+ *     sequential float64 sum of the members' a32 in member order
+ * One launch of one workgroup runs all iterations; alpha is not checked (the caller passes finite
+ * positive weights).
+ * Refused on the host with nothing launched: K < 1, f < 0, K < 2f + 3, m outside [1, K - f],
+ * iterations < 0, nu not finite or <= 0, M_max < 1 or M_max > K, L < 1, null pointers (FJAGG_EINVAL);
+ * K > 1024 (FJAGG_EUNSUPPORTED). fjagg_last_error names the limit.
+ */
+int fjagg_krum_select(const double* gram_dev, int64_t K, int64_t f, int64_t m, double* scores_dev,
+                      int64_t* selected_dev, int32_t* count_dev, int32_t* order_dev, int32_t* seg_dev,
+                      float* wperm_dev, float* gscale_dev, void* stream);
+int fjagg_weiszfeld_select(const double* gram_dev, int64_t K, const double* alpha_dev, double nu, int64_t iterations,
+                           double* a_dev, double* d_dev, float* a32_dev, int32_t* count_dev, int32_t* order_dev,
+                           int32_t* seg_dev, float* wperm_dev, float* gscale_dev, void* stream);
+/* fjagg_wsum_group_dense / _ptrs for ONE group (G = 1, no gorder) whose tables a kernel wrote: no
+ * host copies of seg and order, nothing checked against them. The kernel shape comes from the
+ * caller's bound M_max on the member count (m for Krum, K for the geometric median) in place of
+ * M; the count folded is seg_dev[1] - seg_dev[0] <= M_max. The same kernels as the entries above:
+ * the folds are exact and sequential, so every shape gives the same bits. A count of 0 writes
+ * nothing. The flags and the other refusals are those entries'. The pytree image is laid out for
+ * M_max members: in_ptrs[M_max*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk], slots past the count
+ * never read. */
+int fjagg_wsum_group_dense_dev(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t M_max,
+                               const int32_t* order_dev, const int32_t* seg_dev, const float* wperm_dev,
+                               const float* gscale_dev, void* out_dev, int flags, void* stream);
+int fjagg_wsum_group_ptrs_dev(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t M_max, int64_t nblk,
+                              const int32_t* seg_dev, const float* wperm_dev, const float* gscale_dev, int flags,
+                              void* stream);
+/* Fills the in_ptrs of such an image: slot j < count gets the L leaf pointers of client order_dev[j]
+ * from image_all_dev = in_ptrs[K*L] (the image fjagg_gram_ptrs reads). An order entry outside
+ * [0, K) copies nothing. */
+int fjagg_gather_member_ptrs(const int64_t* image_all_dev, int L, int64_t K, const int32_t* order_dev,
+                             const int32_t* seg_dev, int64_t M_max, int64_t* image_group_dev, void* stream);
 
 /*
  * Centered clipping: the robust mean clipped around the previous round's aggregate (Karimireddy, He
