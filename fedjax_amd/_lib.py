@@ -115,6 +115,10 @@ _SIGNATURES = {
     "fjagg_wsum_group_dense_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_wsum_group_ptrs_dev": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_gather_member_ptrs": (_i32, [_vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "fjagg_bulyan_select_workspace_bytes": (_i64, [_i64]),
+    "fjagg_bulyan_select": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjagg_meamed_dense_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_meamed_ptrs_dev": (_i32, [_i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

@@ -1,7 +1,8 @@
 // fjrobust.hip — coordinate-wise trimmed mean and median over the client axis
 // (include/fjagg.h: fjagg_trim_dense, fjagg_trim_ptrs; Yin et al., ICML 2018) and the mean
 // around the median (fjagg_meamed_dense, fjagg_meamed_ptrs; Xie et al. 2018), Bulyan's second
-// stage.
+// stage, also with its counts and row table read from device memory (fjagg_meamed_dense_dev,
+// fjagg_meamed_ptrs_dev), where fjagg_bulyan_select wrote them.
 //
 // Not a fold: every coordinate needs two order statistics of its K client values. One lane
 // owns one column (fjrobust_dev.h has the per-column routine and the reasons for its shape):
@@ -166,6 +167,78 @@ __global__ __launch_bounds__(TrimShape<N>::TPB) void k_meamed_ptrs(const int64_t
   });
 }
 
+// The same column routine with M, keep, scale and the row table read from device memory, where a
+// select kernel wrote them (fjagg_bulyan_select): all uniform over the grid. The width N comes
+// from the caller's bound M_max <= N. No address is formed from an unchecked table value: the
+// count is clamped into [0, M_max], keep into [0, count], every row index into [0, K_rows), so a
+// stale table can give a wrong result but never an access outside the slab. keep < 1 stores +0
+// and loads no client row.
+struct MeamedDevTables {
+  int M, keep;
+  float scale;
+};
+__device__ __forceinline__ MeamedDevTables meamed_tables(const int32_t* __restrict__ count_dev,
+                                                         const int32_t* __restrict__ keep_dev,
+                                                         const float* __restrict__ scale_dev, int M_max) {
+  int M = count_dev[0], keep = keep_dev[0];
+  M = M < 0 ? 0 : (M > M_max ? M_max : M);
+  keep = keep < 0 ? 0 : (keep > M ? M : keep);
+  return MeamedDevTables{M, keep, scale_dev[0]};
+}
+
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_meamed_dense_dev(
+    const uint32_t* __restrict__ x, int64_t ld, int K_rows, int M_max, int64_t P,
+    const int32_t* __restrict__ rows_dev, const int32_t* __restrict__ count_dev,
+    const int32_t* __restrict__ keep_dev, const float* __restrict__ scale_dev, int do_scale,
+    uint32_t* __restrict__ out) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const int64_t col0 = (int64_t)blockIdx.x * TPB, col = col0 + threadIdx.x;
+  const bool valid = col < P;
+  const MeamedDevTables tb = meamed_tables(count_dev, keep_dev, scale_dev, M_max);
+  if (tb.keep < 1) {  // uniform over the grid
+    if (valid) store_bits(out + col, 0u);
+    return;
+  }
+  const uint32_t off = valid ? threadIdx.x : (uint32_t)(P - 1 - col0);
+  const uint32_t* base = x + col0;
+  auto load = [=](int k) {  // k < M <= M_max: inside the table; the row clamped into the slab
+    int r = rows_dev[k];
+    r = r < 0 ? 0 : (r >= K_rows ? K_rows - 1 : r);
+    return load_bits<NT>(base + (int64_t)r * ld, off);
+  };
+  const uint32_t y =
+      fjrobust::around_median_column<N, TPB>(load, tb.M, tb.keep, do_scale != 0, tb.scale, lane_tile<N, TPB>());
+  if (valid) store_bits(out + col, y);
+}
+
+// The image is laid out for M_max members; k_gather_rows has filled every slot.
+template <int N, bool NT>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_meamed_ptrs_dev(
+    const int64_t* __restrict__ img, int L, int M_max, int V, const int32_t* __restrict__ count_dev,
+    const int32_t* __restrict__ keep_dev, const float* __restrict__ scale_dev, int do_scale) {
+  const MeamedDevTables tb = meamed_tables(count_dev, keep_dev, scale_dev, M_max);
+  ptrs_walk<N, NT>(img, L, M_max, V, [=](auto load, fjrobust::KeyPair* tile) {
+    if (tb.keep < 1) return 0u;  // uniform: +0, nothing loaded
+    return fjrobust::around_median_column<N, TrimShape<N>::TPB>(load, tb.M, tb.keep, do_scale != 0, tb.scale, tile);
+  });
+}
+
+// Slot j of the group image (in_ptrs[M_max*L]) gets the L leaf pointers of client rows_dev[j],
+// clamped into [0, K), from all = in_ptrs[K*L]. The select kernel repeats its last row past the
+// count, so EVERY slot holds a client's pointers, whatever the count turns out to be.
+__global__ __launch_bounds__(256) void k_gather_rows(const int64_t* __restrict__ all, int L, int K,
+                                                     const int32_t* __restrict__ rows_dev, int M_max,
+                                                     int64_t* __restrict__ group) {
+  const int64_t n = (int64_t)M_max * L;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * 256) {
+    const int64_t j = idx / L, l = idx - j * L;
+    int r = rows_dev[j];
+    r = r < 0 ? 0 : (r >= K ? K - 1 : r);
+    group[idx] = all[(int64_t)r * L + l];
+  }
+}
+
 // what both aggregates refuse: the dtype, the flags and the client count
 int column_check(const char* who, int in_dtype, int64_t K, int flags, int allowed) {
   if (in_dtype != FJAGG_F32) return fail(FJAGG_EUNSUPPORTED, "%s: float32 deltas and output only", who);
@@ -234,9 +307,45 @@ int launch_meamed_ptrs(const int64_t* img, int L, int K, int64_t nblk, int V, in
   return check_launch("k_meamed_ptrs");
 }
 
+struct MeamedDevArgs {
+  const int32_t *rows, *count, *keep;
+  const float* scale;
+};
+
+template <int N, bool NT>
+int launch_meamed_dense_dev(const uint32_t* x, int64_t ld, int K_rows, int M_max, int64_t P, const MeamedDevArgs& t,
+                            int ds, uint32_t* y, hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)((P + TPB - 1) / TPB));
+  hipLaunchKernelGGL((k_meamed_dense_dev<N, NT>), grid, dim3(TPB), 0, s, x, ld, K_rows, M_max, P, t.rows, t.count,
+                     t.keep, t.scale, ds, y);
+  return check_launch("k_meamed_dense_dev");
+}
+
+template <int N, bool NT>
+int launch_meamed_ptrs_dev(const int64_t* img, int L, int M_max, int64_t nblk, int V, const MeamedDevArgs& t, int ds,
+                           hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)nblk, 256 / TPB);
+  hipLaunchKernelGGL((k_meamed_ptrs_dev<N, NT>), grid, dim3(TPB), 0, s, img, L, M_max, V, t.count, t.keep, t.scale, ds);
+  return check_launch("k_meamed_ptrs_dev");
+}
+
+// fjagg_meamed_*'s refusals with M_max in place of M (keep is the device's)
+int meamed_dev_check(int in_dtype, int64_t K_rows, int64_t M_max, int flags, int allowed) {
+  if (int rc = column_check("mean around median", in_dtype, M_max, flags, allowed)) return rc;
+  if (K_rows < 1 || K_rows > kMeamedMaxSlabRows)
+    return fail(K_rows < 1 ? FJAGG_EINVAL : FJAGG_EUNSUPPORTED,
+                "mean around median: a slab of 1 <= K_rows <= %d rows (got %lld)", kMeamedMaxSlabRows, (long long)K_rows);
+  if (M_max > K_rows)
+    return fail(FJAGG_EINVAL, "mean around median: M_max <= K_rows (M_max=%lld, K_rows=%lld)", (long long)M_max,
+                (long long)K_rows);
+  return FJAGG_OK;
+}
+
 }  // namespace
 
-#define FJ_TRIM_WIDTH(FN, NTV, ...)                    \
+#define FJ_TRIM_WIDTH(FN, NTV, ...)                \
   (K <= 16   ? FN<16, NTV>(__VA_ARGS__)                \
    : K <= 32 ? FN<32, NTV>(__VA_ARGS__)                \
    : K <= 64 ? FN<64, NTV>(__VA_ARGS__)                \
@@ -316,6 +425,48 @@ int fjagg_meamed_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, 
   return (flags & FJAGG_NONTEMPORAL)
              ? FJ_TRIM_WIDTH(launch_meamed_ptrs, true, image_dev, L, k, nblk, V, kp, scale, ds, s)
              : FJ_TRIM_WIDTH(launch_meamed_ptrs, false, image_dev, L, k, nblk, V, kp, scale, ds, s);
+}
+
+int fjagg_meamed_dense_dev(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P, int64_t M_max,
+                           const int32_t* rows_dev, const int32_t* count_dev, const int32_t* keep_dev,
+                           const float* scale_dev, void* out_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = meamed_dev_check(in_dtype, K_rows, M_max, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld (P=%lld, ld=%lld)", (long long)P, (long long)ld);
+  if (P * 4 > kTrimMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "mean around median: rows <= 1 GiB");
+  if (!x_dev || !out_dev || !rows_dev || !count_dev || !keep_dev || !scale_dev)
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(x_dev);
+  uint32_t* y = reinterpret_cast<uint32_t*>(out_dev);
+  const MeamedDevArgs t{rows_dev, count_dev, keep_dev, scale_dev};
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, K = (int)M_max, kr = (int)K_rows;  // K: the width's bound
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_meamed_dense_dev, true, x, ld, kr, K, P, t, ds, y, s)
+                                     : FJ_TRIM_WIDTH(launch_meamed_dense_dev, false, x, ld, kr, K, P, t, ds, y, s);
+}
+
+int fjagg_meamed_ptrs_dev(int in_dtype, const int64_t* image_all_dev, int64_t* image_group_dev, int L, int64_t K_rows,
+                          int64_t M_max, int64_t nblk, const int32_t* rows_dev, const int32_t* count_dev,
+                          const int32_t* keep_dev, const float* scale_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = meamed_dev_check(in_dtype, K_rows, M_max, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED))
+    return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1 || L >= (1 << 22))
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!image_all_dev || !image_group_dev || !rows_dev || !count_dev || !keep_dev || !scale_dev)
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int64_t blocks = (M_max * L + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)blocks), dim3(256), 0, s, image_all_dev, L, (int)K_rows, rows_dev,
+                     (int)M_max, image_group_dev);
+  if (int rc = check_launch("k_gather_rows")) return rc;
+  const MeamedDevArgs t{rows_dev, count_dev, keep_dev, scale_dev};
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, K = (int)M_max;  // K: the width's bound
+  const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
+  const int64_t* img = image_group_dev;
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_meamed_ptrs_dev, true, img, L, K, nblk, V, t, ds, s)
+                                     : FJ_TRIM_WIDTH(launch_meamed_ptrs_dev, false, img, L, K, nblk, V, t, ds, s);
 }
 
 }  // extern "C"

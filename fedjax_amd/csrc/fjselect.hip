@@ -12,6 +12,11 @@
 //   k_weiszfeld       one workgroup of 1024 lanes runs all iterations: lane k owns client k and
 //                     walks column k of G (row k's bits, coalesced), a in LDS
 //   k_gather_members  copies the selected clients' leaf pointers into a grouped plan image
+//   k_bulyan_sort     (fjagg_bulyan_select, K <= 252) one workgroup per row: its (key, index) pairs
+//                     sorted in LDS, written position-major into the workspace
+//   k_bulyan_steps    one workgroup of 256 lanes runs all K - 2f steps: lane i walks row i's sorted
+//                     list past the clients already chosen, then an argmin on (score bits, index);
+//                     writes the row table, count, keep and scale that fjagg_meamed_*_dev read
 // No floating-point atomics; two runs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -185,6 +190,110 @@ __global__ __launch_bounds__(kThreads) void k_gather_members(const int64_t* __re
   }
 }
 
+// Bulyan's first launch: row i's K - 1 (key, index) pairs sorted by (key, index) in LDS and written
+// position-major, position p of row i at p*K + i.
+__global__ __launch_bounds__(kBulyanLanes) void k_bulyan_sort(const double* __restrict__ G, int K,
+                                                              uint64_t* __restrict__ skeys,
+                                                              uint8_t* __restrict__ sidx) {
+  __shared__ uint64_t keys[kBulyanLanes];
+  __shared__ uint8_t idx[kBulyanLanes];
+  const int i = blockIdx.x, t = threadIdx.x, N = pow2_at_least(K);
+  const double gii = G[(int64_t)i * K + i];
+  const bool ok_i = finite(gii);
+  if (t < N) {
+    keys[t] = krum_key(G, K, i, t, gii, ok_i);
+    idx[t] = (uint8_t)t;
+  }
+  __syncthreads();
+  for (int k = 2; k <= N; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (t < N) bitonic_cx_pair(keys, idx, t, j, k);
+      __syncthreads();
+    }
+  if (t < K - 1) {  // the pads (i itself, t >= K) sort last and stay behind
+    skeys[(int64_t)t * K + i] = keys[t];
+    sidx[(int64_t)t * K + i] = idx[t];
+  }
+}
+
+// Bulyan's second launch: ONE workgroup runs all theta steps, lane i owns client i. A step: every
+// live lane adds its first c live neighbours, the wave and then the workgroup reduce (score bits,
+// index) to its minimum, the winner leaves R. Every lane reads the same four wave minima, so the
+// winner and the decision to stop are uniform.
+__global__ __launch_bounds__(kBulyanLanes) void k_bulyan_steps(
+    const double* __restrict__ G, int K, int f, const uint64_t* __restrict__ skeys, const uint8_t* __restrict__ sidx,
+    int64_t* __restrict__ selected, int32_t* __restrict__ count, double* __restrict__ step_scores,
+    int32_t* __restrict__ keep_out, float* __restrict__ scale_out, int32_t* __restrict__ rows) {
+  constexpr int kWaves = kBulyanLanes / 64;
+  __shared__ uint8_t alive[kBulyanLanes], chosen[kBulyanLanes];
+  __shared__ uint64_t wave_best[kWaves];
+  __shared__ int wave_who[kWaves];
+  __shared__ int live0, last_row;
+  const int i = threadIdx.x, theta = K - 2 * f;
+  const bool ok_i = i < K && finite(G[(int64_t)i * K + i]);
+  alive[i] = ok_i;
+  chosen[i] = 0;
+  if (i == 0) last_row = 0;
+  __syncthreads();
+  if (i == 0) live0 = flags_below(alive, K);
+  __syncthreads();
+  int n = live0, c = 0;
+  bool live = ok_i;
+  for (; c < theta; ++c) {
+    const double s = live ? bulyan_score(skeys, sidx, K, i, bulyan_neighbours(n, f), alive) : 0.0;
+    uint64_t best = bulyan_candidate(s, live);
+    int who = i;
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint64_t ob = __shfl_xor((unsigned long long)best, off);
+      const int ow = __shfl_xor(who, off);
+      if (bulyan_before(ob, ow, best, who)) {
+        best = ob;
+        who = ow;
+      }
+    }
+    if ((i & 63) == 0) {
+      wave_best[i >> 6] = best;
+      wave_who[i >> 6] = who;
+    }
+    __syncthreads();
+    best = wave_best[0];
+    who = wave_who[0];
+    for (int w = 1; w < kWaves; ++w)
+      if (bulyan_before(wave_best[w], wave_who[w], best, who)) {
+        best = wave_best[w];
+        who = wave_who[w];
+      }
+    if (best == kPadKey) break;  // R is empty, or no score is finite (uniform)
+    if (i == who) {
+      selected[c] = who;
+      step_scores[c] = double_of(best);
+      alive[i] = 0;
+      chosen[i] = 1;
+      live = false;
+    }
+    --n;
+    __syncthreads();
+  }
+  __syncthreads();
+  if (i < K && chosen[i]) {
+    const int slot = flags_below(chosen, i);
+    rows[slot] = i;
+    if (slot == c - 1) last_row = i;
+  }
+  __syncthreads();
+  if (i >= c && i < theta) {
+    selected[i] = -1;
+    step_scores[i] = double_of(kInfBits);
+    rows[i] = last_row;
+  }
+  if (i == 0) {
+    const int keep = bulyan_keep(c, f);
+    *count = c;
+    *keep_out = keep;
+    *scale_out = bulyan_scale(keep);
+  }
+}
+
 int check_clients(const char* what, int64_t K) {
   if (K < 1) return fail(FJAGG_EINVAL, "%s: K must be >= 1 (got %lld)", what, (long long)K);
   if (K > kMaxClients)
@@ -234,6 +343,41 @@ int fjagg_weiszfeld_select(const double* gram_dev, int64_t K, const double* alph
   hipLaunchKernelGGL(k_weiszfeld, dim3(1), dim3(kWideThreads), 0, s, gram_dev, (int)K, alpha_dev, nu, (int)iterations,
                      a_dev, d_dev, a32_dev, count_dev, order_dev, seg_dev, wperm_dev, gscale_dev);
   return check_launch("k_weiszfeld");
+}
+
+int64_t fjagg_bulyan_select_workspace_bytes(int64_t K) {
+  if (K < 3 || K > kBulyanMaxClients) return 0;
+  return K * (K - 1) * 9;  // the sorted keys (8 bytes) and their client indices (1 byte)
+}
+
+int fjagg_bulyan_select(const double* gram_dev, int64_t K, int64_t f, void* ws_dev, int64_t ws_bytes,
+                        int64_t* selected_dev, int32_t* count_dev, double* step_scores_dev, int32_t* keep_dev,
+                        float* scale_dev, int32_t* rows_dev, void* stream) {
+  g_err[0] = 0;
+  if (int rc = check_clients("bulyan select", K)) return rc;
+  if (f < 0) return fail(FJAGG_EINVAL, "bulyan select: f must be >= 0 (got %lld)", (long long)f);
+  if (f > K || K < 4 * f + 3)
+    return fail(FJAGG_EINVAL, "bulyan select: needs K >= 4f + 3 clients (K=%lld, f=%lld)", (long long)K, (long long)f);
+  if (K - 2 * f > kBulyanMaxSelected)
+    return fail(FJAGG_EUNSUPPORTED, "bulyan select: K - 2f <= %d selected clients (K=%lld, f=%lld)", kBulyanMaxSelected,
+                (long long)K, (long long)f);
+  // K >= 4f + 3 and K - 2f <= 128: 2f <= (K - 3) / 2, so K <= 128 + (K - 3) / 2 and K <= 252 (checked again
+  // because the kernels' LDS arrays and the byte indices rest on it)
+  if (K > kBulyanMaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "bulyan select: K <= %d clients (got %lld)", kBulyanMaxClients, (long long)K);
+  if (!gram_dev || !ws_dev || !selected_dev || !count_dev || !step_scores_dev || !keep_dev || !scale_dev || !rows_dev)
+    return fail(FJAGG_EINVAL, "null pointer argument");
+  if (ws_bytes < fjagg_bulyan_select_workspace_bytes(K) || (reinterpret_cast<uintptr_t>(ws_dev) & 7))
+    return fail(FJAGG_EINVAL, "bulyan select: workspace of %lld bytes, 8-byte aligned (got %lld)",
+                (long long)fjagg_bulyan_select_workspace_bytes(K), (long long)ws_bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint64_t* skeys = reinterpret_cast<uint64_t*>(ws_dev);
+  uint8_t* sidx = reinterpret_cast<uint8_t*>(skeys + K * (K - 1));
+  hipLaunchKernelGGL(k_bulyan_sort, dim3((unsigned)K), dim3(kBulyanLanes), 0, s, gram_dev, (int)K, skeys, sidx);
+  if (int rc = check_launch("k_bulyan_sort")) return rc;
+  hipLaunchKernelGGL(k_bulyan_steps, dim3(1), dim3(kBulyanLanes), 0, s, gram_dev, (int)K, (int)f, skeys, sidx,
+                     selected_dev, count_dev, step_scores_dev, keep_dev, scale_dev, rows_dev);
+  return check_launch("k_bulyan_steps");
 }
 
 int fjagg_gather_member_ptrs(const int64_t* image_all_dev, int L, int64_t K, const int32_t* order_dev,

@@ -1,8 +1,9 @@
-// fjselect_dev.h — the selection rules of the two whole-vector robust aggregates over the K x K
+// fjselect_dev.h — the selection rules of the whole-vector robust aggregates over the K x K
 // float64 Gram matrix G of the client deltas (include/fjagg.h: fjagg_krum_select,
-// fjagg_weiszfeld_select), and the member tables of the grouped fold that follows them. Plain C++
-// that also compiles for the host, so the rules can be run against numpy without a GPU
-// (tests/select_device_host.cpp); fjselect.hip is its only user in the library.
+// fjagg_weiszfeld_select, fjagg_bulyan_select), and the tables of the second pass that follows
+// them. Plain C++ that also compiles for the host, so the rules can be run against numpy without
+// a GPU (tests/select_device_host.cpp, tests/bulyan_select_host.cpp); fjselect.hip is its only
+// user in the library.
 //
 // Every function here is the work of ONE index (a client, a key position) or of the one lane
 // that adds a sequential sum; the kernels give the indices to lanes and put barriers between the
@@ -210,6 +211,81 @@ FJS_HD double member_total(const float* a32, const uint8_t* member, int K) {
 }
 FJS_HD float total_gscale(double W) { return W > 0.0 ? (float)div_rn(1.0, W) : 0.0f; }
 
+// ------------------------------------------------------------------------------------ Bulyan
+// Bulyan's first stage (include/fjagg.h: fjagg_bulyan_select; fedjax_amd.robust.bulyan_select bit
+// for bit): theta = K - 2f times, the client of smallest finite score among the set R of usable
+// clients not yet chosen, which then leaves R. With n = |R| and c = max(n - f - 2, 1), score_i is
+// the c smallest d2(i, j), j in R without i, added in ascending order from 0.0 (0.0 when n = 1);
+// d2 is krum_key's value. K >= 4f + 3 and theta <= 128 bound K at 252 (kBulyanMaxClients): a
+// client index fits a byte and one workgroup of 256 lanes owns one row per lane.
+//
+// Every row's K - 1 (key, index) pairs are sorted ONCE, by (key, index), and stored position-major
+// (position p of row i at p*K + i), so the lanes of a wave walk consecutive words. A step takes a
+// live row's first c live neighbours in that order: the sums of a fresh sort per step. Two
+// neighbours at the same distance contribute the same term whichever is taken, so the sort need
+// only order by the key; index order among equal keys cannot change any sum (it is there to make
+// the sorted table itself a function of G alone).
+constexpr int kBulyanMaxClients = 252;
+constexpr int kBulyanMaxSelected = 128;  // theta: what the second stage's column routine takes
+constexpr int kBulyanLanes = 256;
+constexpr int kBulyanBatch = 16;  // loads in flight per lane in a step's walk
+
+// bitonic_cx over (key, index) pairs
+FJS_HD void bitonic_cx_pair(uint64_t* keys, uint8_t* idx, int t, int j, int k) {
+  const int u = t ^ j;
+  if (u > t) {
+    const uint64_t a = keys[t], b = keys[u];
+    const uint8_t ia = idx[t], ib = idx[u];
+    if ((a > b || (a == b && ia > ib)) == ((t & k) == 0)) {
+      keys[t] = b;
+      keys[u] = a;
+      idx[t] = ib;
+      idx[u] = ia;
+    }
+  }
+}
+
+// neighbours a step needs of each of n remaining clients
+FJS_HD int bulyan_neighbours(int n, int f) { return n - f - 2 > 1 ? n - f - 2 : 1; }
+
+// Row i's score in a step: its first c live neighbours of the sorted tables, added in order from
+// 0.0. Sixteen positions are loaded before the sixteen additions (as seq_sum does with eight); a position past the
+// c-th live one is loaded and dropped. With no live neighbour (n = 1) the sum is 0.0.
+FJS_HD double bulyan_score(const uint64_t* __restrict__ skeys, const uint8_t* __restrict__ sidx, int K, int i, int c,
+                           const uint8_t* alive) {
+  double s = 0.0;
+  int taken = 0;
+  for (int p0 = 0; p0 < K - 1 && taken < c; p0 += kBulyanBatch) {
+    uint64_t kv[kBulyanBatch];
+    uint8_t jv[kBulyanBatch];
+#pragma unroll
+    for (int u = 0; u < kBulyanBatch; ++u) {
+      const int p = p0 + u < K - 1 ? p0 + u : K - 2;
+      kv[u] = skeys[(int64_t)p * K + i];
+      jv[u] = sidx[(int64_t)p * K + i];
+    }
+#pragma unroll
+    for (int u = 0; u < kBulyanBatch; ++u) {
+      const bool take = p0 + u < K - 1 && taken < c && alive[jv[u]] != 0;
+      s = take ? add_rn(s, double_of(kv[u])) : s;
+      taken += take;
+    }
+  }
+  return s;
+}
+
+// What a client brings to a step's argmin: its score's bits (a score is never negative or NaN),
+// or the pad when it is not in R or its score is not finite, so that a pad can never win.
+FJS_HD uint64_t bulyan_candidate(double score, bool live) {
+  return live && finite(score) ? bits_of(score) : kPadKey;
+}
+// (bits a, client ia) before (bits b, client ib): the smaller score, ties to the lower index
+FJS_HD bool bulyan_before(uint64_t a, int ia, uint64_t b, int ib) { return a < b || (a == b && ia < ib); }
+
+FJS_HD int bulyan_keep(int count, int f) { return count - 2 * f >= 1 ? count - 2 * f : 0; }
+// the bits the host route passes: np.float32(1 / keep)
+FJS_HD float bulyan_scale(int keep) { return keep > 0 ? (float)div_rn(1.0, (double)keep) : 0.0f; }
+
 // ---------------------------------------------------- the whole rules as loops (host builds)
 #if !defined(__HIP_DEVICE_COMPILE__)
 // fjagg_krum_select's two launches. The first: scores[K] from G[K][K]; keys: scratch of
@@ -303,6 +379,73 @@ inline void weiszfeld_select_host(const double* G, int K, const double* alpha, d
   seg[0] = 0;
   seg[1] = c;
   gscale[0] = total_gscale(member_total(a32, member, K));
+}
+
+// fjagg_bulyan_select's two launches from G[K][K] and f (3 <= 4f + 3 <= K <= kBulyanMaxClients,
+// theta = K - 2f <= kBulyanMaxSelected). skeys / sidx: the workspace, K * (K - 1) words and bytes.
+// Outputs: selected[theta] (selection order, -1 padded), *count, step_scores[theta] (+inf padded),
+// *keep, *scale, rows[theta] (the chosen clients ascending, then the last one repeated; 0s if none).
+inline void bulyan_select_host(const double* G, int K, int f, uint64_t* skeys, uint8_t* sidx, int64_t* selected,
+                               int32_t* count, double* step_scores, int32_t* keep, float* scale, int32_t* rows) {
+  const int N = pow2_at_least(K), theta = K - 2 * f;
+  uint64_t keys[kBulyanLanes];
+  uint8_t idx[kBulyanLanes], alive[kBulyanLanes], chosen[kBulyanLanes];
+  // the first launch: one workgroup per row
+  for (int i = 0; i < K; ++i) {
+    const double gii = G[(int64_t)i * K + i];
+    const bool ok_i = finite(gii);
+    for (int t = 0; t < N; ++t) {
+      keys[t] = krum_key(G, K, i, t, gii, ok_i);
+      idx[t] = (uint8_t)t;
+    }
+    for (int k = 2; k <= N; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1)
+        for (int t = 0; t < N; ++t) bitonic_cx_pair(keys, idx, t, j, k);
+    for (int p = 0; p < K - 1; ++p) {  // the pads (i itself, t >= K) sort last and stay behind
+      skeys[(int64_t)p * K + i] = keys[p];
+      sidx[(int64_t)p * K + i] = idx[p];
+    }
+  }
+  // the second: one workgroup, lane i owns client i
+  int n = 0, c = 0;
+  for (int i = 0; i < K; ++i) {
+    alive[i] = finite(G[(int64_t)i * K + i]);
+    chosen[i] = 0;
+    n += alive[i];
+  }
+  for (; c < theta; ++c) {
+    uint64_t best = kPadKey;
+    int who = K;
+    const int take = bulyan_neighbours(n, f);
+    for (int i = 0; i < K; ++i) {
+      const double s = alive[i] ? bulyan_score(skeys, sidx, K, i, take, alive) : 0.0;
+      const uint64_t cand = bulyan_candidate(s, alive[i] != 0);
+      if (bulyan_before(cand, i, best, who)) {
+        best = cand;
+        who = i;
+      }
+    }
+    if (best == kPadKey) break;  // R is empty, or no score is finite
+    selected[c] = who;
+    step_scores[c] = double_of(best);
+    alive[who] = 0;
+    chosen[who] = 1;
+    --n;
+  }
+  int last = 0;
+  for (int i = 0; i < K; ++i)
+    if (chosen[i]) {
+      rows[flags_below(chosen, i)] = i;
+      last = i;
+    }
+  for (int r = c; r < theta; ++r) {
+    selected[r] = -1;
+    step_scores[r] = double_of(kInfBits);
+    rows[r] = last;
+  }
+  *count = c;
+  *keep = bulyan_keep(c, f);
+  *scale = bulyan_scale(*keep);
 }
 #endif
 

@@ -1099,6 +1099,143 @@ def grouped_sum_ptrs_device(image_all: torch.Tensor, image_group: torch.Tensor, 
               _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), s)
 
 
+BULYAN_MAX_SELECTED = TRIM_MAX_CLIENTS  # theta = K - 2f: what the second stage's column routine takes
+_BULYAN_WS = {}  # (device index, stream handle) -> workspace of fjagg_bulyan_select (the sorted rows)
+
+
+class DeviceRowTables(NamedTuple):
+    """What ``fjagg_bulyan_select`` leaves for the second stage (fjagg.h), all on the device:
+    ``rows`` int32 [M_max], the chosen slab rows ascending, the last repeated past the count;
+    ``count`` / ``keep`` int32 scalars; ``scale`` float32 scalar, f32(1 / keep) or 0; and the
+    bound ``M_max`` on the count that the second stage's kernel width is picked from."""
+    rows: torch.Tensor
+    count: torch.Tensor
+    keep: torch.Tensor
+    scale: torch.Tensor
+    M_max: int
+
+
+def _bulyan_workspace(dev: torch.device, need: int) -> torch.Tensor:
+    """The select's workspace on ``dev``'s current stream, cached like :func:`_gram_workspace`;
+    under stream capture a tensor of the graph's own pool, which is not kept. Never zeroed,
+    nothing carried between calls."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    key = (dev.index, _stream_handle(dev))
+    ws = _BULYAN_WS.get(key)
+    if ws is None and len(_BULYAN_WS) >= 16:
+        _BULYAN_WS.clear()
+    if ws is None or ws.numel() < need:
+        ws = _BULYAN_WS[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def check_bulyan_args(K: int, f) -> int:
+    """Bulyan's conditions on the client count alone, with the host route's exceptions and
+    nothing computed: ``1 <= K <= 1024``, an int ``f >= 0`` (a bool is refused),
+    ``K >= 4f + 3`` and ``K - 2f <= 128``. Returns ``f``."""
+    from fedjax_amd import robust
+
+    _check_gram_clients(K)
+    f = robust.check_bulyan(K, f)
+    if K - 2 * f > BULYAN_MAX_SELECTED:
+        raise ValueError(f"Bulyan's second stage takes K - 2f <= {BULYAN_MAX_SELECTED} selected clients, "
+                         f"got K = {K}, f = {f}")
+    return f
+
+
+def bulyan_select_device(gram: torch.Tensor, f: int):
+    """Bulyan's first stage on the device over a float64 ``[K, K]`` Gram matrix
+    (``fjagg_bulyan_select``): bit for bit :func:`fedjax_amd.robust.bulyan_select` of the same
+    matrix. Returns ``(selected, count, step_scores, tables)``, all on the device: ``selected``
+    int64 [theta], selection order, -1 padded (``theta = K - 2f``); ``count`` int32 scalar;
+    ``step_scores`` float64 [theta], each step's winning score, +inf padded; ``tables`` the
+    :class:`DeviceRowTables` of :func:`meamed_dense_device` (``keep = count - 2f`` or 0). Two
+    small launches, no host synchronisation, nothing uploaded: capturable. ``K >= 4f + 3``,
+    ``K - 2f <= 128``."""
+    K = _check_select_gram(gram)
+    f = check_bulyan_args(K, f)  # the host route's argument checks and exceptions
+    dev, theta = gram.device, K - 2 * f
+    selected = torch.empty(theta, dtype=torch.int64, device=dev)
+    step_scores = torch.empty(theta, dtype=torch.float64, device=dev)
+    ints = torch.empty(theta + 2, dtype=torch.int32, device=dev)  # rows | count | keep
+    scale = torch.empty((), dtype=torch.float32, device=dev)
+    tables = DeviceRowTables(ints[:theta], ints[theta], ints[theta + 1], scale, theta)
+    need = int(_lib.load().fjagg_bulyan_select_workspace_bytes(K))
+    ws = _bulyan_workspace(dev, need)
+    _lib.call("fjagg_bulyan_select", gram.data_ptr(), K, f, ws.data_ptr(), ws.numel(), selected.data_ptr(),
+              tables.count.data_ptr(), step_scores.data_ptr(), tables.keep.data_ptr(), scale.data_ptr(),
+              tables.rows.data_ptr(), _stream_handle(dev))
+    return selected, tables.count, step_scores, tables
+
+
+def _check_row_tables(tables: DeviceRowTables) -> int:
+    M = int(tables.M_max)
+    if not (1 <= M <= TRIM_MAX_CLIENTS):
+        raise ValueError(f"the mean around the median supports 1 <= M_max <= {TRIM_MAX_CLIENTS} participating "
+                         f"clients, got M_max = {M}")
+    for name, t, dtype, n in (("rows", tables.rows, torch.int32, M), ("count", tables.count, torch.int32, 1),
+                              ("keep", tables.keep, torch.int32, 1), ("scale", tables.scale, torch.float32, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"tables.{name} must be a contiguous {dtype} device tensor of at least {n} elements")
+    return M
+
+
+def meamed_dense_device(x: torch.Tensor, tables: DeviceRowTables, *, out: Optional[torch.Tensor] = None,
+                        nontemporal: bool = False) -> torch.Tensor:
+    """:func:`meamed_dense` over a float32 slab ``x[K, P]`` with the participating rows, their
+    count, the keep count and the scale read from device memory (``fjagg_meamed_dense_dev``):
+    the same column routine and bits, no host copy of the tables, nothing uploaded. The kernel
+    clamps the count into ``[0, M_max]``, keep into ``[0, count]`` and every row into ``[0, K)``;
+    ``keep < 1`` writes +0 everywhere and loads no row. Checked before the library is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the mean around the median takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if not (1 <= K <= MEAMED_MAX_SLAB_ROWS):
+        raise ValueError(f"a row table selects from a slab of 1 <= K <= {MEAMED_MAX_SLAB_ROWS} rows, got K = {K}")
+    M = _check_row_tables(tables)
+    if M > K:
+        raise ValueError(f"M_max must be <= K = {K}, got {M}")
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the mean around the median takes rows of up to 1 GiB")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.dim() != 1 or out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, out, tables.rows, tables.count, tables.keep, tables.scale)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_meamed_dense_dev", _lib.F32, x.data_ptr(), ld, K, P, M, tables.rows.data_ptr(),
+              tables.count.data_ptr(), tables.keep.data_ptr(), tables.scale.data_ptr(), out.data_ptr(),
+              _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), _stream_handle(dev))
+    return out
+
+
+def meamed_ptrs_device(image_all: torch.Tensor, image_group: torch.Tensor, L: int, K: int, nblk: int,
+                       tables: DeviceRowTables, *, nontemporal: bool = False) -> None:
+    """The same over a pytree plan (``fjagg_meamed_ptrs_dev``): the chosen clients' leaf pointers
+    are gathered on the device from ``image_all`` (``in_ptrs[K*L]``, the Gram pass's image) into
+    every member slot of ``image_group`` (``in_ptrs[M_max*L] | out_ptrs[L] | leaf_n[L] |
+    blocks[2*nblk]``), then one launch covers every leaf."""
+    for name, t in (("image_all", image_all), ("image_group", image_group)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous int64 device tensor")
+    M = _check_row_tables(tables)
+    L, K, nblk = int(L), int(K), int(nblk)
+    if not (1 <= K <= MEAMED_MAX_SLAB_ROWS) or M > K:
+        raise ValueError(f"need 1 <= M_max <= K <= {MEAMED_MAX_SLAB_ROWS}, got M_max = {M}, K = {K}")
+    if L < 1 or nblk < 1 or image_all.numel() < K * L or image_group.numel() < M * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, images of {image_all.numel()} and "
+                         f"{image_group.numel()} words")
+    dev = _require_device(image_all, image_group, tables.rows, tables.count, tables.keep, tables.scale)
+    _lib.call("fjagg_meamed_ptrs_dev", _lib.F32, image_all.data_ptr(), image_group.data_ptr(), L, K, M, nblk,
+              tables.rows.data_ptr(), tables.count.data_ptr(), tables.keep.data_ptr(), tables.scale.data_ptr(),
+              _lib.SCALE | (_lib.NONTEMPORAL if nontemporal else 0), _stream_handle(dev))
+
+
 def check_select(select) -> bool:
     """``select="host" | "device"`` of the Krum and geometric-median surfaces: True for the
     device route; ValueError for anything else."""

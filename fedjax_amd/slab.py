@@ -361,7 +361,7 @@ class ClientDeltaSlab:
                                     nontemporal=M * self.num_params * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
         return self.unflatten(flat)
 
-    def bulyan(self, num_byzantine) -> "tree_util.BulyanResult":
+    def bulyan(self, num_byzantine, *, select: str = "host"):
         """Bulyan (El Mhamdi, Guerraoui and Rouault, ICML 2018) over the rows: Krum iterated
         ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
         (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then
@@ -375,7 +375,30 @@ class ClientDeltaSlab:
         coordinate-wise stage. There are no client weights. Returns a
         :class:`~fedjax_amd.tree_util.BulyanResult`; ``mean`` is ``None`` when fewer than
         ``2f + 1`` clients could be selected. A float32 slab of up to 1024 clients with
-        ``K - 2f <= 128``. Raises under stream capture."""
+        ``K - 2f <= 128``. Raises under stream capture.
+
+        ``select="device"`` keeps the round on the device: :meth:`gram`, ``fjagg_bulyan_select``
+        (the same selection, bit for bit), then the second stage reading its row table, count,
+        keep count and scale from device memory (``fjagg_meamed_dense_dev``: the same column
+        routine, so the same bits as the host route's mean). No device-to-host copy, no
+        synchronisation, nothing uploaded: the round can be captured into a graph and replayed
+        over rewritten deltas, and each replay selects afresh. The argument checks and their
+        exceptions are the same. Returns a :class:`~fedjax_amd.tree_util.DeviceBulyanResult` of
+        device tensors; ``mean`` is all +0 when fewer than ``2f + 1`` clients could be selected
+        (never ``None``)."""
+        if kernels.check_select(select):
+            if self.dtype != torch.float32:
+                raise TypeError(f"bulyan needs a float32 slab, not {self.dtype}")
+            f = tree_util._check_bulyan_args(self.num_clients, num_byzantine)
+            gram = self.gram()
+            selected, count, step_scores, tables = kernels.bulyan_select_device(gram, f)
+            out = torch.empty(self.row_stride, dtype=torch.float32, device=self.device)
+            if self.num_params:
+                nbytes = tables.M_max * self.num_params * 4
+                kernels.meamed_dense_device(self.rows, tables, out=out[: self.num_params],
+                                            nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+            # (a template of empty leaves: nothing to launch; the padding past num_params is never shown)
+            return tree_util.DeviceBulyanResult(self.unflatten(out), selected, count, tables.keep, step_scores, gram)
         kernels.refuse_capture("bulyan", kernels._TWO_PASS)
         if self.dtype != torch.float32:
             raise TypeError(f"bulyan needs a float32 slab, not {self.dtype}")

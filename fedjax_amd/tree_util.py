@@ -48,7 +48,7 @@ __all__ = [
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
     "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
     "DeviceKrumResult", "DeviceGeometricMedianResult",
-    "tree_mean_around_median", "tree_bulyan", "BulyanResult",
+    "tree_mean_around_median", "tree_bulyan", "BulyanResult", "DeviceBulyanResult",
     "tree_centered_clip", "CenteredClip",
 ]
 
@@ -2236,7 +2236,23 @@ def _bulyan_plan(G: np.ndarray, f: int):
     return selected, sorted(int(k) for k in selected), (keep if keep >= 1 else 0)
 
 
-def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine) -> Optional[BulyanResult]:
+class DeviceBulyanResult(NamedTuple):
+    """Result of Bulyan with ``select="device"``: nothing of it has visited the host. ``mean`` —
+    the mean around the median over the selected clients, all +0 when fewer than ``2f + 1``
+    could be selected (never ``None``: the count is not known on the host); ``selected`` — int64
+    device tensor [K - 2f], selection order, padded with -1; ``count`` — int32 device scalar, how
+    many were selected; ``keep`` — int32 device scalar, ``count - 2f`` or 0 with no mean;
+    ``step_scores`` — float64 device tensor [K - 2f], each step's winning score, padded with
+    +inf; ``gram`` — the float64 ``[K, K]`` Gram matrix."""
+    mean: Any
+    selected: Any
+    count: Any
+    keep: Any
+    step_scores: Any
+    gram: Any
+
+
+def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine, *, select: str = "host"):
     """Bulyan over client pytrees (El Mhamdi, Guerraoui and Rouault, ICML 2018): Krum iterated
     ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
     (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then, per coordinate, the
@@ -2250,7 +2266,25 @@ def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine) -> Optional[BulyanResu
     holding NaN, inf or 1e30 has a non-finite squared norm: it is unusable and never selected;
     with more than ``theta - 2f - 1`` such clients the selection is too short and ``mean`` is
     ``None``. There are no client weights. Float32 leaves, ``K <= 1024`` and ``K - 2f <= 128``.
-    Returns a :class:`BulyanResult`; no clients: ``None``. Raises under stream capture."""
+    Returns a :class:`BulyanResult`; no clients: ``None``. Raises under stream capture.
+
+    ``select="device"`` keeps the round on the device: the Gram pass, ``fjagg_bulyan_select`` (the
+    same selection, bit for bit), then ``fjagg_meamed_ptrs_dev``, which gathers the chosen
+    clients' leaf pointers on the device and reads its counts there (the same column routine,
+    so the same bits) — no device-to-host copy, no synchronisation. The argument checks and
+    their exceptions are the same. Returns a :class:`DeviceBulyanResult` whose ``mean`` is all +0
+    when too few clients could be selected (never ``None``); still raises under stream capture,
+    because the plan images go through a pinned staging buffer."""
+    if kernels.check_select(select):
+        trees = pytrees if type(pytrees) is list else list(pytrees)
+        if not trees:
+            return None
+        f = _check_bulyan_args(len(trees), num_byzantine)
+        gram, mean, (selected, count, step_scores, tables) = _tree_fold_selected(
+            trees, len(trees) - 2 * f, lambda g: kernels.bulyan_select_device(g, f),
+            lambda image_all, image_group, L, K, nblk, tables, nt: kernels.meamed_ptrs_device(
+                image_all, image_group, L, K, nblk, tables, nontemporal=nt))
+        return DeviceBulyanResult(mean, selected, count, tables.keep, step_scores, gram)
     kernels.refuse_capture("tree_bulyan", kernels._TWO_PASS)
     trees = pytrees if type(pytrees) is list else list(pytrees)
     if not trees:
@@ -2405,14 +2439,15 @@ def _tree_gram(trees: list):
     return kernels.gram_ptrs(image_dev, L, K, len(blocks) // 2), td, rows
 
 
-def _tree_fold_selected(trees: list, M_max: int, select):
+def _tree_fold_selected(trees: list, M_max: int, select, fold=None):
     """The device route of :func:`tree_krum` / :func:`tree_geometric_median`: the Gram pass, then
     ``select(gram)`` — a :mod:`kernels` select call, whose outputs end with the
     :class:`kernels.DeviceGroupTables` of at most ``M_max`` members — then the zeroed result and
     the grouped fold over the members the kernel chose, their leaf pointers gathered on the
     device. ONE upload holds both plan images (so the call raises under stream capture, as
     :func:`tree_gram` does); nothing comes back to the host. Returns ``(gram, result pytree,
-    select's outputs)``."""
+    select's outputs)``. ``fold(image_all, image_group, L, K, nblk, tables, nontemporal)`` replaces
+    the zeroing and the grouped fold (Bulyan's second stage, which writes every element itself)."""
     K = kernels._check_gram_clients(len(trees))
     bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
                   if _CANONICAL.get(x.dtype) != torch.float32})
@@ -2428,7 +2463,7 @@ def _tree_fold_selected(trees: list, M_max: int, select):
     if not leaf_n.any():  # no elements: every inner product is the empty sum, nothing to fold
         gram = torch.zeros(K, K, dtype=torch.float64, device=device)
         got = select(gram)
-        flat.zero_()
+        flat.zero_()  # (empty leaves: views of no element; zeroed whatever fold would write)
         return gram, result, got
     in_ptrs = _ptr_table(rows)
     out_ptrs = flat.data_ptr() + 4 * offs[:-1]
@@ -2443,8 +2478,11 @@ def _tree_fold_selected(trees: list, M_max: int, select):
     image_all, image_group = image_dev[:all_words], image_dev[all_words:]
     gram = kernels.gram_ptrs(image_all, L, K, len(gram_blocks) // 2)
     got = select(gram)
-    flat.zero_()
     nt = int(leaf_n.sum()) * M_max * 4 >= NONTEMPORAL_MIN_BYTES
+    if fold is not None:
+        fold(image_all, image_group, L, K, len(fold_blocks) // 2, got[-1], nt)
+        return gram, result, got
+    flat.zero_()
     kernels.grouped_sum_ptrs_device(image_all, image_group, L, K, len(fold_blocks) // 2, got[-1], nontemporal=nt)
     return gram, result, got
 

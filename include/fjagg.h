@@ -23,6 +23,7 @@
  *     (no reference row) Krum / geometric median (Gram matrix)  fjagg_gram_* (K x K inner products, float64)
  *     (no reference row) Krum / Weiszfeld selection on the device fjagg_krum_select, fjagg_weiszfeld_select
  *     (no reference row) mean around the median / Bulyan        fjagg_meamed_* (the keep values nearest the median)
+ *     (no reference row) Bulyan on the device                   fjagg_bulyan_select, fjagg_meamed_*_dev
  *     (no reference row) centered clipping (Karimireddy et al. 2021) fjagg_center_* (clipped around the last aggregate)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
@@ -719,6 +720,66 @@ int fjagg_wsum_group_ptrs_dev(int in_dtype, const int64_t* image_dev, int L, int
  * [0, K) copies nothing. */
 int fjagg_gather_member_ptrs(const int64_t* image_all_dev, int L, int64_t K, const int32_t* order_dev,
                              const int32_t* seg_dev, int64_t M_max, int64_t* image_group_dev, void* stream);
+
+/*
+ * Bulyan on the device (El Mhamdi, Guerraoui and Rouault, ICML 2018): the first stage's selection over
+ * the Gram matrix above, and the second stage (the mean around the median, fjagg_meamed_* above) with
+ * its member count, keep count, scale and row table read from device memory where the selection wrote
+ * them. A round is fjagg_gram_* -> fjagg_bulyan_select -> fjagg_meamed_*_dev with no host visit, no
+ * synchronisation and nothing uploaded, so the dense round can be captured. The semantics are fixed
+ * here and in fedjax_amd/csrc/fjselect_dev.h; the selection is bit for bit
+ * fedjax_amd.robust.bulyan_select. Float64 in separate IEEE operations, no FMA, no atomics: the result
+ * is a function of (G, K, f) alone and two runs give the same bits.
+ *     theta    = K - 2f;  usable_k = isfinite(G_kk);  d2(i,j) as Krum's above (clamped at +0, +inf when
+ *                not finite or when either client is unusable)
+ *     R        = the usable clients not yet chosen; n = |R|; c = max(n - f - 2, 1)
+ *     score_i  = for i in R, the c smallest d2(i,j) over j in R \ {i}, added in ascending order from
+ *                0.0 (0.0 when n = 1). Neighbours at the same distance add the same term whichever is
+ *                taken, so the order among equal distances cannot change a sum.
+ *     a step   = the smallest FINITE score wins, ties to the lower client index; the winner leaves R
+ *     the selection stops after theta steps, or earlier when R is empty or no score is finite
+ *     selected[theta]    int64, selection order, -1 padded;       count[1] int32, the steps made
+ *     step_scores[theta] float64, each step's winning score, +inf padded
+ *     keep[1]  = count - 2f if that is >= 1, else 0;  scale[1] = keep > 0 ? (float)(1.0 / (double)keep) : 0.0f
+ *     rows[theta] int32: the chosen clients in ASCENDING client index; entries past count repeat the last
+ *                chosen row (0 when count = 0), so every entry is a row of the slab
+ * Limits: K >= 4f + 3 and theta <= 128 (the second stage's width). Together: 2f <= (K - 3) / 2, so
+ * K <= 128 + (K - 3) / 2, K <= 253; K = 253 would need f <= 62 and theta = 129, so K <= 252 (f = 62).
+ * A client index fits a byte, and one workgroup of 256 lanes owns one row per lane.
+ * Two launches: one workgroup per row sorts its (key, index) pairs once in LDS and writes them
+ * position-major into the workspace (K (K - 1) * 9 bytes, 8-byte aligned, never zeroed, nothing
+ * carried between calls); one workgroup then runs all theta steps, lane i walking row i's sorted list
+ * past the clients already chosen, then an argmin on (score bits, index).
+ * Refused on the host with nothing launched: K < 1, f < 0, K < 4f + 3, null pointers, a workspace under
+ * fjagg_bulyan_select_workspace_bytes or not 8-byte aligned (FJAGG_EINVAL); K > 1024 and K - 2f > 128
+ * (FJAGG_EUNSUPPORTED). fjagg_last_error names the limit.
+ *
+ * The second stage from device tables: fjagg_meamed_*'s arithmetic, column routine and walks, with
+ * M = count_dev[0], keep = keep_dev[0] and scale = scale_dev[0] (used with FJAGG_SCALE) read by the
+ * kernel; all three are uniform over the grid. The kernel width 16 / 32 / 64 / 128 comes from the caller's
+ * bound M_max (Bulyan: theta); the routine ranks by (key, client index) and adds the kept values in
+ * client order, so its bits do not depend on the width. Dense: participating client k is slab row
+ * rows_dev[k]. Pytree: image_group_dev is laid out for M_max members (in_ptrs[M_max*L] | out_ptrs[L] |
+ * leaf_n[L] | blocks[2*nblk]); a first small launch fills ALL M_max slots from image_all_dev =
+ * in_ptrs[K_rows*L] (the image fjagg_gram_ptrs reads) by rows_dev, so every slot holds a client's
+ * pointers; slots past the count are never read. keep < 1: every output element is +0, written by the
+ * kernel itself (a graph replay zeroes too), and no client row is loaded.
+ * The kernels form no address from an unchecked table value: count is clamped into [0, M_max], keep into
+ * [0, count], every row index into [0, K_rows). A stale table can give a wrong result, never an access
+ * outside the slab or the table. The refusals are fjagg_meamed_*'s with M_max in place of M (M_max < 1,
+ * M_max > K_rows, K_rows < 1, P < 1, ld < P, a bad plan, null pointers: FJAGG_EINVAL; M_max > 128,
+ * K_rows > 1024, rows over 1 GiB, the dtype and the flags: FJAGG_EUNSUPPORTED).
+ */
+int64_t fjagg_bulyan_select_workspace_bytes(int64_t K); /* 0 for K outside [3, 252] */
+int fjagg_bulyan_select(const double* gram_dev, int64_t K, int64_t f, void* ws_dev, int64_t ws_bytes,
+                        int64_t* selected_dev, int32_t* count_dev, double* step_scores_dev, int32_t* keep_dev,
+                        float* scale_dev, int32_t* rows_dev, void* stream);
+int fjagg_meamed_dense_dev(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P, int64_t M_max,
+                           const int32_t* rows_dev, const int32_t* count_dev, const int32_t* keep_dev,
+                           const float* scale_dev, void* out_dev, int flags, void* stream);
+int fjagg_meamed_ptrs_dev(int in_dtype, const int64_t* image_all_dev, int64_t* image_group_dev, int L, int64_t K_rows,
+                          int64_t M_max, int64_t nblk, const int32_t* rows_dev, const int32_t* count_dev,
+                          const int32_t* keep_dev, const float* scale_dev, int flags, void* stream);
 
 /*
  * Centered clipping: the robust mean clipped around the previous round's aggregate (Karimireddy, He
