@@ -48,6 +48,7 @@ TREE_ORDERED = 1 << 10  # FJTREE_ORDERED: norm combine by release/acquire atomic
 COMP_UNIFORM, COMP_TERNGRAD, COMP_BINARY = 1, 2, 3
 WHT_PLAIN, WHT_ROTATE, WHT_UNROTATE, WHT_UNROTATE_DRIVE = 0, 1, 2, 3
 STATS_CHUNK = 16384
+TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
 _i64, _i32, _f32, _vp, _u64 = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64
@@ -137,6 +138,13 @@ _SIGNATURES = {
                                  _vp, _vp]),
     "fjcomp_wht_tiles": (_i64, [_i32, _i32]),
     "fjcomp_wht": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "fjcomp_topk_workspace_bytes": (_i64, [_i64]),
+    "fjcomp_topk_select_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "fjcomp_topk_select_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32,
+                                       _vp]),
+    "fjcomp_topk_mean_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "fjcomp_topk_mean_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp,
+                                     _i64, _i32, _vp]),
     # include/fjcomm.h
     "fjcomm_abi_version": (_i32, []),
     "fjcomm_unique_id": (_i32, [_vp]),

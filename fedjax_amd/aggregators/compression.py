@@ -313,7 +313,47 @@ def terngrad_quantizer(rng) -> aggregator.Aggregator:
     return aggregator.Aggregator(init, apply)
 
 
-__all__ = ["CompressionState", "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",
+@dataclasses.dataclass
+class SparsifierState:
+    """State of :func:`top_k_sparsifier`: the bits transmitted so far, ``0.0`` at first and a 0-d
+    float64 device tensor after the first non-empty round (reading it is the only synchronisation)."""
+    num_bits: Any
+
+
+def top_k_sparsifier(k) -> aggregator.Aggregator:
+    """Top-k sparsification: every client sends only its ``k`` largest-magnitude coordinates
+    (``k`` an int count or a float fraction of the model size, :func:`fedjax_amd.kernels.topk_count`),
+    and the server takes the weighted mean of the sparsified deltas
+    (:func:`fedjax_amd.tree_util.tree_topk_mean`: a global threshold per client, all ties kept, a NaN
+    kept first). There is no reference counterpart; the mean is ``tree_mean``'s over the
+    sparsified deltas, bit for bit.
+
+    Each round adds ``mean_k(sent_k) * (32 + ceil(log2 P))`` to ``num_bits``: a float32 value and
+    an index per transmitted coordinate, averaged over the clients, formed with torch ops on the
+    stream from the device counts. An empty round returns ``None`` and leaves the state as it is."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
+        raise TypeError(f"k must be an int count or a float fraction in (0, 1], not {type(k).__name__}")
+
+    def init():
+        return SparsifierState(0.0)
+
+    def apply(clients_params_and_weights, aggregator_state):
+        trees, weights = _consume(clients_params_and_weights)
+        if not trees:
+            return None, aggregator_state
+        res = tree_util.tree_topk_mean(list(zip(trees, weights)), k)
+        P = sum(int(x.numel()) for x in map(tree_util._to_tensor, pytree.leaves_of(trees[0])))
+        if P == 0:
+            return res.mean, aggregator_state
+        per_coordinate = 32 + (P - 1).bit_length()  # value bits + ceil(log2 P) index bits
+        new_bits = res.sent.to(torch.float64).mean() * per_coordinate
+        return res.mean, SparsifierState(aggregator_state.num_bits + new_bits)
+
+    return aggregator.Aggregator(init, apply)
+
+
+__all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier",
+           "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",
            "num_leaves", "rotated_uniform_stochastic_quantizer", "structured_drive_quantizer", "terngrad_quantize",
            "terngrad_quantize_pytree", "terngrad_quantizer", "uniform_stochastic_quantize",
            "uniform_stochastic_quantize_pytree", "uniform_stochastic_quantizer"]

@@ -1456,6 +1456,213 @@ def centered_clip_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, max_n
     return distances, factors
 
 
+TOPK_MAX_CLIENTS = _lib.TOPK_MAX_CLIENTS  # fjcomp_topk_*: the clipped fold's client limit (fjcomp.h)
+TOPK_CHUNK = _lib.TOPK_CHUNK  # elements of one row a histogram workgroup counts (FJCOMP_TOPK_CHUNK)
+TOPK_MAX_PARAMS = (1 << 31) - 1  # P < 2^31: the counts and ranks of the select are 32-bit
+_TOPK_WS = {}  # (device index, stream handle) -> workspace of the top-k select (histograms, prefixes, ranks)
+
+
+def topk_count(k, P: int) -> int:
+    """The keep count ``c`` of a top-k sparsifier over rows of ``P`` coordinates, checked: ``k`` is
+    an int count ``1 <= k <= P`` taken as is, or a float fraction ``0 < beta <= 1`` giving
+    ``c = max(1, floor(beta * P))`` (in double precision). Raises ``TypeError`` for a bool or a
+    non-number, ``ValueError`` for ``P < 1``, ``P >= 2^31``, a count outside ``[1, P]`` or a
+    fraction outside ``(0, 1]``. Nothing here touches the library."""
+    if isinstance(k, (bool, np.bool_)):
+        raise TypeError("k must be an int count or a float fraction in (0, 1], not a bool")
+    P = int(P)
+    if P < 1:
+        raise ValueError(f"a top-k sparsifier needs at least 1 coordinate, got P = {P}")
+    if P > TOPK_MAX_PARAMS:
+        raise ValueError(f"the top-k select supports P < 2^31 coordinates per client, got P = {P}")
+    if isinstance(k, (int, np.integer)):
+        c = int(k)
+        if not 1 <= c <= P:
+            raise ValueError(f"a keep count needs 1 <= k <= P = {P}, got k = {c}")
+        return c
+    if isinstance(k, (float, np.floating)):
+        beta = float(k)
+        if not (0.0 < beta <= 1.0):
+            raise ValueError(f"a keep fraction must be in (0, 1], got {k}")
+        return max(1, int(math.floor(beta * P)))
+    raise TypeError(f"k must be an int count or a float fraction in (0, 1], not {type(k).__name__}")
+
+
+def check_topk_clients(K: int) -> int:
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"a top-k sparsified mean needs at least 1 client, got K = {K}")
+    if K > TOPK_MAX_CLIENTS:
+        raise ValueError(f"the top-k sparsified mean supports K <= {TOPK_MAX_CLIENTS} clients, got K = {K}")
+    return K
+
+
+def _topk_workspace(dev: torch.device, K: int) -> torch.Tensor:
+    """The select's workspace on ``dev``'s current stream, cached like :func:`_center_workspace`;
+    under stream capture a tensor of the graph's own pool. The entry zeroes it on the stream."""
+    need = int(_lib.load().fjcomp_topk_workspace_bytes(K))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    key = (dev.index, _stream_handle(dev))
+    ws = _TOPK_WS.get(key)
+    if ws is None and len(_TOPK_WS) >= 16:
+        _TOPK_WS.clear()
+    if ws is None or ws.numel() < need:
+        ws = _TOPK_WS[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _check_topk_slab(x: torch.Tensor) -> Tuple[int, int]:
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the top-k sparsified mean takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    check_topk_clients(K)
+    return K, P
+
+
+def _check_topk_keep(c, P: int) -> int:
+    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+        raise TypeError("c must be an int keep count (kernels.topk_count makes one)")
+    return topk_count(int(c), P) if P else 0
+
+
+def _topk_diagnostics(K: int, dev: torch.device, zero: bool = False):
+    make = torch.zeros if zero else torch.empty
+    return make(K, dtype=torch.float32, device=dev), make(K, dtype=torch.int32, device=dev)
+
+
+def topk_select_dense(x: torch.Tensor, c: int):
+    """``(thresholds, sent)`` of a float32 slab ``x[K, P]``: per client the ``c``-th largest
+    magnitude key ``bits & 0x7fffffff`` of its row as a float (float32 [K]) and the count of its
+    keys ``>= max(T, 1)`` (int32 [K]); exact (a three-level radix select, ``fjcomp_topk_select_dense``).
+    Three passes over the slab and four small launches, no host synchronisation, nothing
+    uploaded. ``K <= 4096``, ``P < 2^31``, ``1 <= c <= P``; ``P = 0`` launches nothing and gives
+    zeros. Everything is checked before the library is touched."""
+    K, P = _check_topk_slab(x)
+    c = _check_topk_keep(c, P)
+    dev = _require_device(x)
+    if P == 0:
+        return _topk_diagnostics(K, dev, zero=True)
+    thr, sent = _topk_diagnostics(K, dev)
+    ws = _topk_workspace(dev, K)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjcomp_topk_select_dense", _lib.F32, x.data_ptr(), ld, K, P, c, thr.data_ptr(), sent.data_ptr(),
+              ws.data_ptr(), ws.numel(), _stream_handle(dev))
+    return thr, sent
+
+
+def topk_mean_dense(x: torch.Tensor, w: torch.Tensor, c: int, *, scale: float, out: Optional[torch.Tensor] = None):
+    """``(out, thresholds, sent)``: :func:`topk_select_dense`, then the exact fold of the slab with
+    every coordinate below its client's threshold taken as ``+0``: ``s = fl(x~_0 w_0)``,
+    ``s = fl(s + fl(x~_k w_k))`` in client order, ``out = fl(s * f32(scale))``, the multiply and the
+    add separate (``fjcomp_topk_mean_dense``). All ties at the threshold are kept; a NaN has the
+    largest magnitude and is kept first. ``w``: device float32 [K]. No sparsified copy, no host
+    synchronisation, nothing uploaded. ``P = 0`` launches nothing."""
+    K, P = _check_topk_slab(x)
+    c = _check_topk_keep(c, P)
+    _f32_vector("w", w, K)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+        raise TypeError("out must be a float32 tensor")
+    if out.dim() != 1 or out.numel() != P or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of {P} elements")
+    dev = _require_device(x, w, out)
+    if P == 0:
+        return (out,) + _topk_diagnostics(K, dev, zero=True)
+    thr, sent = _topk_diagnostics(K, dev)
+    ws = _topk_workspace(dev, K)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjcomp_topk_mean_dense", _lib.F32, x.data_ptr(), ld, K, P, c, w.data_ptr(), float(np.float32(scale)),
+              out.data_ptr(), thr.data_ptr(), sent.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle(dev))
+    return out, thr, sent
+
+
+class TopKTables:
+    """The tables of the pytree route on the host: one int64 image ``in_ptrs[K*L] | out_ptrs[L] |
+    leaf_n[L] | chunk_prefix[L+1] | w`` (the float32 weights packed two to a word; ``out_ptrs`` and
+    ``w`` may be absent for a select) and what the entries need beside it. A histogram chunk
+    never spans two leaves: leaf ``l`` owns ``ceil(leaf_n[l] / TOPK_CHUNK)`` chunks."""
+
+    def __init__(self, in_ptrs: np.ndarray, leaf_n, out_ptrs=None, w=None):
+        in_ptrs = np.ascontiguousarray(in_ptrs, dtype=np.int64)
+        if in_ptrs.ndim != 2:
+            raise ValueError("in_ptrs must be a [K, L] table of leaf pointers")
+        self.K, self.L = in_ptrs.shape
+        check_topk_clients(self.K)
+        leaf_n = np.asarray(leaf_n, dtype=np.int64)
+        if leaf_n.shape != (self.L,) or self.L < 1 or (leaf_n < 0).any():
+            raise ValueError(f"leaf_n must hold {self.L} sizes >= 0")
+        self.P = int(leaf_n.sum())
+        prefix = np.concatenate([[0], np.cumsum((leaf_n + TOPK_CHUNK - 1) // TOPK_CHUNK)]).astype(np.int64)
+        self.nchunks = int(prefix[-1])
+        out_ptrs = np.zeros(self.L, np.int64) if out_ptrs is None else np.asarray(out_ptrs, dtype=np.int64)
+        if out_ptrs.shape != (self.L,):
+            raise ValueError(f"out_ptrs must hold {self.L} pointers")
+        live = leaf_n > 0
+        self.unaligned = bool((in_ptrs[:, live] % 16).any() or (out_ptrs[live] % 16).any())
+        if w is None:
+            words = np.zeros(0, np.int64)
+        else:
+            w = np.asarray(w, dtype=np.float32)
+            if w.shape != (self.K,):
+                raise ValueError(f"need {self.K} weights, got {w.size}")
+            words = np.zeros((self.K + 1) // 2, dtype=np.int64)
+            words.view(np.float32)[: self.K] = w
+        self.has_w = w is not None
+        self.host = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, prefix, words])
+
+    def upload(self, device: torch.device) -> "TopKTables":
+        """The image on ``device`` through the pinned upload (refused under stream capture)."""
+        self.image_dev = _lib.upload(torch.from_numpy(self.host), device)
+        base, KL, L = self.image_dev.data_ptr(), self.K * self.L, self.L
+        self.in_p, self.out_p, self.n_p, self.prefix_p = base, base + 8 * KL, base + 8 * (KL + L), base + 8 * (KL + 2 * L)
+        self.w_p = base + 8 * (KL + 3 * L + 1)
+        return self
+
+
+def _topk_ptrs_args(tables: TopKTables, c: int):
+    if not isinstance(tables, TopKTables) or not hasattr(tables, "image_dev"):
+        raise TypeError("tables must be uploaded TopKTables")
+    c = _check_topk_keep(c, tables.P)
+    return c, _require_device(tables.image_dev)
+
+
+def topk_select_ptrs(tables: TopKTables, c: int):
+    """:func:`topk_select_dense` over uploaded :class:`TopKTables`: client ``k``'s row is its ``L``
+    leaves back to back, and ONE histogram per client spans all of them (a global top-k, not a
+    per-leaf one). ``fjcomp_topk_select_ptrs``."""
+    c, dev = _topk_ptrs_args(tables, c)
+    if tables.P == 0:
+        return _topk_diagnostics(tables.K, dev, zero=True)
+    thr, sent = _topk_diagnostics(tables.K, dev)
+    ws = _topk_workspace(dev, tables.K)
+    _lib.call("fjcomp_topk_select_ptrs", _lib.F32, tables.in_p, tables.K, tables.L, tables.n_p, tables.prefix_p,
+              tables.nchunks, tables.P, c, thr.data_ptr(), sent.data_ptr(), ws.data_ptr(), ws.numel(),
+              _lib.UNALIGNED if tables.unaligned else 0, _stream_handle(dev))
+    return thr, sent
+
+
+def topk_mean_ptrs(tables: TopKTables, c: int, *, scale: float):
+    """:func:`topk_mean_dense`'s arithmetic over uploaded :class:`TopKTables` made with output
+    pointers and weights: the result goes behind ``out_ptrs``; returns ``(thresholds, sent)``.
+    ``fjcomp_topk_mean_ptrs``."""
+    c, dev = _topk_ptrs_args(tables, c)
+    if not tables.has_w:
+        raise ValueError("topk_mean_ptrs needs tables made with weights and output pointers")
+    if tables.P == 0:
+        return _topk_diagnostics(tables.K, dev, zero=True)
+    thr, sent = _topk_diagnostics(tables.K, dev)
+    ws = _topk_workspace(dev, tables.K)
+    _lib.call("fjcomp_topk_mean_ptrs", _lib.F32, tables.in_p, tables.K, tables.L, tables.n_p, tables.prefix_p,
+              tables.nchunks, tables.P, c, tables.w_p, float(np.float32(scale)), tables.out_p, thr.data_ptr(),
+              sent.data_ptr(), ws.data_ptr(), ws.numel(), _lib.UNALIGNED if tables.unaligned else 0,
+              _stream_handle(dev))
+    return thr, sent
+
+
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:
     """Synthetic deltas x[k, p] = amp * u(seed, k0 + k, p) (tests/bench only)."""
     if x.dim() != 2 or x.stride(1) != 1:

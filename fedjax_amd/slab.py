@@ -593,6 +593,85 @@ class ClientDeltaSlab:
             max_n=max(self.sizes), nontemporal=rows.numel() * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
         return tree_util.CenteredClip(self.unflatten(flat), distances, factors)
 
+    def _topk_weight_vector(self, weights: Sequence) -> torch.Tensor:
+        """The float32 weights on the device for :meth:`topk_mean`. The vector of the latest call
+        stays on the device, so a capture with the SAME weights (after one eager call) launches
+        without an upload; any other capture is refused by the pinned upload, as in
+        :meth:`grouped_mean` (whose notes on streams and capture apply)."""
+        w = self.host_weights(weights)
+        key = w.tobytes()
+        cached = getattr(self, "_topk_weights", None)
+        stream = torch.cuda.current_stream(self.device)
+        if cached is not None and cached[0] == key:
+            w_dev, up_stream, uploaded = cached[1:]
+            if torch.cuda.is_current_stream_capturing():  # the graph reads this buffer on every replay
+                self._captured_tables = getattr(self, "_captured_tables", []) + [w_dev]
+            elif stream != up_stream:
+                stream.wait_event(uploaded)
+            return w_dev
+        w_dev = _lib.upload(torch.from_numpy(w), self.device)  # (refused under capture)
+        uploaded = torch.cuda.Event()
+        uploaded.record(stream)
+        self._topk_weights = (key, w_dev, stream, uploaded)
+        return w_dev
+
+    def _topk_keep(self, what: str, k) -> int:
+        if self.dtype != torch.float32:
+            raise TypeError(f"{what} needs a float32 slab, not {self.dtype}")
+        kernels.check_topk_clients(self.num_clients)
+        if self.num_params == 0:  # a template of empty leaves: nothing to select from
+            if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
+                raise TypeError("k must be an int count or a float fraction in (0, 1], not "
+                                f"{type(k).__name__}")
+            return 0
+        return kernels.topk_count(k, self.num_params)
+
+    def topk_thresholds(self, k):
+        """``(thresholds, sent)`` of :meth:`topk_mean` alone: per client the magnitude threshold of
+        its ``k`` largest coordinates (float32 [K]) and the number of coordinates it would transmit
+        (int32 [K]). Three passes over the slab, nothing uploaded, no host synchronisation:
+        graph-capturable."""
+        c = self._topk_keep("topk_thresholds", k)
+        return kernels.topk_select_dense(self.rows, c)
+
+    def topk_mean(self, weights: Sequence, k, *, out: Optional[torch.Tensor] = None) -> "tree_util.TopKMean":
+        """Weighted mean of the K rows with every client's delta sparsified to its ``k``
+        largest-magnitude coordinates first (top-k sparsification, the most widely used
+        compression rule of federated learning). ``k`` is an int count ``1 <= k <= num_params`` or
+        a float fraction ``0 < beta <= 1`` giving ``max(1, floor(beta * num_params))``; a bool is
+        refused. The selection is over the client's whole row (all leaves together).
+
+        The magnitude of ``v`` is the integer ``bits(v) & 0x7fffffff``, so ``|NaN| > inf > ... >
+        subnormals > 0``; ``T_k`` is the exact ``k``-th largest magnitude of row ``k`` and a
+        coordinate is kept iff its magnitude is ``>= T_k``: all ties at the threshold are kept (at
+        least ``k`` coordinates survive), and a NaN is kept first — this is compression, not
+        robustness. A dropped coordinate counts as ``+0`` in :meth:`mean`'s fold (a kept ``-0``
+        passes verbatim), with the same ``W`` and ``f32(1/W)``: the result is bit for bit
+        ``mean(weights)`` of a slab holding the sparsified rows, and ``k = num_params`` is bit for
+        bit ``mean(weights)``.
+
+        Three histogram passes and one fold over the slab and four small launches; no sort, no
+        sparsified copy, no host synchronisation. The only upload is the weight vector, kept on
+        the device: after one eager call a round with the same weights can be captured into a
+        graph and replayed over rewritten deltas, and every replay selects afresh. Returns a
+        :class:`~fedjax_amd.tree_util.TopKMean` of the template's pytree (views into ``out`` if
+        given: float32, ``num_params`` elements) and the device diagnostics ``thresholds`` and
+        ``sent``. A float32 slab of up to 4096 clients, fewer than 2^31 parameters."""
+        c = self._topk_keep("topk_mean", k)
+        W = 0.0
+        for x in weights:
+            W += tree_util._host_weight(x)
+        scale = tree_util._inverse(W)
+        if self.num_params == 0:
+            if len(weights) != self.num_clients:
+                raise ValueError(f"need {self.num_clients} weights, got {len(weights)}")
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            thr = torch.zeros(self.num_clients, dtype=torch.float32, device=self.device)
+            return tree_util.TopKMean(self.unflatten(flat), thr, torch.zeros_like(thr, dtype=torch.int32))
+        w_dev = self._topk_weight_vector(weights)
+        flat, thr, sent = kernels.topk_mean_dense(self.rows, w_dev, c, scale=scale, out=out)
+        return tree_util.TopKMean(self.unflatten(flat), thr, sent)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))

@@ -50,6 +50,7 @@ __all__ = [
     "DeviceKrumResult", "DeviceGeometricMedianResult",
     "tree_mean_around_median", "tree_bulyan", "BulyanResult", "DeviceBulyanResult",
     "tree_centered_clip", "CenteredClip",
+    "tree_topk_mean", "TopKMean",
 ]
 
 # Non-temporal loads pay off once the deltas cannot stay in the 256 MiB Infinity
@@ -2059,6 +2060,65 @@ def _tree_columns(trees: list, what: str, launch) -> PyTree:
     image_dev = _lib.upload(torch.from_numpy(image), device)
     launch(image_dev, L, len(blocks) // 2, int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES)
     return result
+
+
+class TopKMean(NamedTuple):
+    """Result of a top-k sparsified mean (:func:`tree_topk_mean`,
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.topk_mean`): the mean pytree and, per client in input
+    order as device tensors, the magnitude threshold ``T_k`` (float32 [K]: the bits of the
+    ``c``-th largest ``bits & 0x7fffffff`` of the client's whole delta, viewed as a float) and
+    ``sent`` (int32 [K]): how many coordinates the client would transmit, those with magnitude
+    ``>= max(T_k, 1)`` — ties at the threshold are all kept, zeros are never counted."""
+    mean: Any
+    thresholds: Any
+    sent: Any
+
+
+def tree_topk_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], k) -> TopKMean:
+    """Weighted mean of client pytrees, each sparsified to its ``k`` largest-magnitude
+    coordinates first (top-k sparsification; ``k`` an int count or a float fraction of the
+    client's total size, :func:`kernels.topk_count`). The selection is global per client: one
+    threshold over all its leaves, not one per leaf. A coordinate is kept iff its magnitude key
+    ``bits & 0x7fffffff`` is at least the client's ``c``-th largest, so all ties at the threshold
+    are kept and a NaN, the largest magnitude there is, is kept first: this is compression, not
+    robustness. A dropped coordinate counts as ``+0`` in :func:`tree_mean`'s fold, with the same
+    ``W`` and ``f32(1/W)``: bit for bit ``tree_mean`` over the sparsified deltas, and bit for
+    bit :meth:`fedjax_amd.slab.ClientDeltaSlab.topk_mean` over the same deltas.
+
+    The structure walk and checks are :func:`tree_trimmed_mean`'s; one table image is uploaded,
+    then three histogram passes, three scans and one fold, no host synchronisation and no
+    sparsified copy. Float32 leaves, ``K <= 4096``, fewer than 2^31 coordinates per client. No
+    clients: all ``None``. Raises under stream capture (the tables go through a pinned staging
+    buffer)."""
+    trees, weights, sum_weight = _collect_pairs(pytrees_and_weights)
+    if not trees:
+        return TopKMean(None, None, None)
+    K = kernels.check_topk_clients(len(trees))
+    if isinstance(k, (bool, np.bool_)):
+        raise TypeError("k must be an int count or a float fraction in (0, 1], not a bool")
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"tree_topk_mean needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        z = torch.zeros(K, dtype=torch.float32, device=_default_device())
+        return TopKMean(pytree.unflatten(td, []), z, torch.zeros_like(z, dtype=torch.int32))
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    # one result row: every leaf at a 16-byte aligned offset
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)])
+    flat = torch.empty(max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = pytree.unflatten(td, [flat[o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+    if not leaf_n.any():
+        z = torch.zeros(K, dtype=torch.float32, device=device)
+        return TopKMean(result, z, torch.zeros_like(z, dtype=torch.int32))
+    c = kernels.topk_count(k, int(leaf_n.sum()))
+    w = weights.f32 if isinstance(weights, _Weights) else np.array([np.float32(x) for x in weights], np.float32)
+    out_ptrs = flat.data_ptr() + 4 * offs[:-1].astype(np.int64)
+    tables = kernels.TopKTables(_ptr_table(rows), leaf_n, out_ptrs, w).upload(device)
+    thr, sent = kernels.topk_mean_ptrs(tables, c, scale=_inverse(sum_weight))
+    return TopKMean(result, thr, sent)
 
 
 def tree_median(pytrees: Iterable[PyTree]) -> Optional[PyTree]:

@@ -174,6 +174,41 @@ int fjcomp_wht(const fjcomp_wht_job* jobs, const int64_t* pass_prefix, int64_t J
 /* tiles of pass p for a job of 2^log2d (host helper, mirrors the kernel's tiling) */
 int64_t fjcomp_wht_tiles(int log2d, int pass);
 
+/* ---- top-k sparsified mean (fjsparse.hip) ----
+ * Client k's row is its leaves back to back, P float32 elements. With the magnitude key
+ * m(v) = bits(v) & 0x7fffffff compared as uint32 (|NaN| > inf > finite > subnormal > 0: a NaN is
+ * kept first; this is compression, not robustness), T_k is the c-th largest key of row k, exact,
+ * and coordinate i of client k is kept iff m(x_k[i]) >= T_k: all ties at the threshold are kept.
+ *   thresholds[k] = T_k's bits as a float;   sent[k] = #{i : m(x_k[i]) >= max(T_k, 1)}
+ *   x~ = kept ? x : +0;  s = fl(x~_0 w_0);  s = fl(s + fl(x~_k w_k));  out = fl(s * scale)
+ * the multiply and the add separate, in client order: fjagg_wsum_dense's exact fold over x~.
+ * The selection is a three-level radix select over integer histograms (fjsparse_dev.h), so
+ * thresholds and sent do not depend on the order of its atomics. float32 only, 1 <= K <=
+ * FJCOMP_TOPK_MAX_CLIENTS, P < 2^31, 1 <= c <= P; P == 0 launches nothing. All launches are
+ * asynchronous on `stream`, nothing visits the host, and the workspace
+ * (fjcomp_topk_workspace_bytes(K) bytes, any contents) is zeroed on the stream by the call.
+ *
+ * _dense: rows x + k * ld (elements). _ptrs: in_ptrs[K*L] client-major and leaf_n[L] as in
+ * fjcomp_quant_fold, chunk_prefix[L+1] the running sum of ceil(leaf_n / FJCOMP_TOPK_CHUNK) and
+ * nchunks its last entry (all device), P the sum of leaf_n; one histogram per client spans all
+ * its leaves. flags: FJAGG_UNALIGNED unless every in_ptrs and out_ptrs entry is 16-byte aligned.
+ * _select: thresholds and sent alone. _mean: the selection, then the masked fold with w[K]. */
+#define FJCOMP_TOPK_CHUNK 16384
+#define FJCOMP_TOPK_MAX_CLIENTS 4096
+int64_t fjcomp_topk_workspace_bytes(int64_t K);
+int fjcomp_topk_select_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t c,
+                             float* thresholds_dev, int32_t* sent_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+int fjcomp_topk_select_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, int64_t L, const int64_t* leaf_n,
+                            const int64_t* chunk_prefix, int64_t nchunks, int64_t P, int64_t c, float* thresholds_dev,
+                            int32_t* sent_dev, void* ws_dev, int64_t ws_bytes, int flags, void* stream);
+int fjcomp_topk_mean_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t c,
+                           const float* w_dev, float scale, float* out_dev, float* thresholds_dev, int32_t* sent_dev,
+                           void* ws_dev, int64_t ws_bytes, void* stream);
+int fjcomp_topk_mean_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, int64_t L, const int64_t* leaf_n,
+                          const int64_t* chunk_prefix, int64_t nchunks, int64_t P, int64_t c, const float* w_dev,
+                          float scale, float* const* out_ptrs, float* thresholds_dev, int32_t* sent_dev, void* ws_dev,
+                          int64_t ws_bytes, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
