@@ -5,9 +5,6 @@ table, every refusal of the Python surfaces and of the C entries, the new names,
 unchanged ABI versions."""
 import os
 import re
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +13,7 @@ import torch
 from fedjax_amd import _lib, aggregators, kernels, tree_util
 from fedjax_amd.aggregators import compression
 from fedjax_amd.slab import ClientDeltaSlab
+from tests import topk_host
 from tests import topk_ref as ref
 
 F32 = np.float32
@@ -56,40 +54,15 @@ def test_reference_mean_is_tree_mean_of_the_masked_rows():
 
 
 # ----------------------------------------------------------- the device rules, built for the host
-def _compiler():
-    for name in ("c++", "g++", "clang++"):
-        if shutil.which(name):
-            return shutil.which(name)
-    return shutil.which("clang++", path="/opt/rocm/llvm/bin")
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    cxx = _compiler()
+    cxx = topk_host.compiler()
     if cxx is None:
         pytest.skip("no C++ compiler")
-    exe = str(tmp_path_factory.mktemp("topk_select") / "topk_select_host")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "fedjax_amd", "csrc"), os.path.join(ROOT, "tests", "topk_select_host.cpp"),
-           "-o", exe]
-    if subprocess.run(cmd, capture_output=True).returncode != 0:  # a toolchain without the sanitizer runtimes
-        cmd = [c for c in cmd if "sanitize" not in c]
-        subprocess.run(cmd, check=True, capture_output=True)
-    return exe
+    return topk_host.build_host_program(cxx, tmp_path_factory.mktemp("topk_select"))
 
 
-def _run_host(exe, cases, tmp_path):
-    """cases: (row float32 or uint32 [P], c). Returns per case (T, sent, trace[6])."""
-    blob = [struct.pack("<i", len(cases))]
-    for row, c in cases:
-        b = np.ascontiguousarray(row).view(np.uint32).ravel()
-        blob += [struct.pack("<2i", b.size, c), b.tobytes()]
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(b"".join(blob))
-    done = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True)
-    assert done.returncode == 0, (done.returncode, done.stderr[-2000:])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32).reshape(len(cases), 8)
-    return [(int(r[0]), int(r[1].view(np.int32)), r[2:].tolist()) for r in out]
+_run_host = topk_host.run_host  # (moved to tests/topk_host.py, shared with tests/test_topk_cases.py)
 
 
 def _check(exe, cases, tmp_path):
