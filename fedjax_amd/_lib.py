@@ -120,6 +120,15 @@ _SIGNATURES = {
     "fjagg_bulyan_select": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fjagg_meamed_dense_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_meamed_ptrs_dev": (_i32, [_i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "fjagg_dotsq_rows_workspace_bytes": (_i64, [_i64, _i64]),
+    "fjagg_dotsq_rows": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "fjagg_dotsq_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "fjagg_fltrust_select": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjagg_fltrust_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "fjagg_fltrust_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _i64, _i32, _vp]),
+    "fjagg_fltrust_ptrs": (_i32, [_i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _i64, _i32, _vp]),
     "fjagg_fill_synth": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _u64, _f32, _vp]),
     # include/fjcomp.h
     "fjcomp_abi_version": (_i32, []),

@@ -24,7 +24,10 @@ Mirror of google/fedjax 0.0.17 ``fedjax/aggregators/aggregator.py``:
   :func:`fedjax_amd.tree_util.tree_mean_around_median` / :func:`fedjax_amd.tree_util.tree_bulyan`;
 * :func:`centered_clip_aggregator` — centered clipping around the previous round's aggregate
   (Karimireddy et al., ICML 2021; no reference counterpart), the one aggregator here whose state
-  carries the aggregate itself, :func:`fedjax_amd.tree_util.tree_centered_clip`.
+  carries the aggregate itself, :func:`fedjax_amd.tree_util.tree_centered_clip`;
+* :func:`fltrust_aggregator` — FLTrust's trust-weighted mean against the server's own delta (Cao et
+  al., NDSS 2021; no reference counterpart), whose state carries that delta,
+  :func:`fedjax_amd.tree_util.tree_fltrust`.
 """
 
 import dataclasses as std_dataclasses
@@ -481,5 +484,52 @@ def centered_clip_aggregator(tau: float, iterations: int = 1) -> Aggregator:
             return None, state
         return got.center, CenteredClipAggregatorState(
             got.center, dict(zip(ids, got.distances[-1].unbind())), dict(zip(ids, got.factors[-1].unbind())))
+
+    return Aggregator(init, apply)
+
+
+@dataclasses.dataclass
+class FLTrustAggregatorState:
+    """What FLTrust needs beside the clients and what it reports: ``server_delta`` — the delta the
+    server computed itself on its trusted dataset for THIS round, a pytree of the clients'
+    structure; the caller sets it before every ``apply`` with ``state.replace(server_delta=...)``
+    (``None``: ``apply`` raises); ``trust`` / ``factors`` — by client id, the last round's trust
+    score ``ts_k`` (float64) and rescale factor ``c_k`` (float32) as 0-d device tensors (0 for a
+    client that was gated out and never loaded by the fold)."""
+    server_delta: Any = None
+    trust: Dict[ClientId, Any] = std_dataclasses.field(default_factory=dict)
+    factors: Dict[ClientId, Any] = std_dataclasses.field(default_factory=dict)
+
+
+def fltrust_aggregator() -> Aggregator:
+    """Builds the FLTrust aggregator of Cao, Fang, Liu and Gong (NDSS 2021; no reference
+    counterpart): every client's params are weighed by the ReLU of their cosine with the server's
+    own delta, rescaled to that delta's norm and averaged by trust
+    (:func:`fedjax_amd.tree_util.tree_fltrust`). The rule judges a client against the server, not
+    against the other clients, so it needs no honest majority — and it needs the server's delta:
+    ``state.server_delta`` must be set for every round (``state.replace(server_delta=g)``);
+    ``apply`` raises ``ValueError`` while it is ``None`` and carries it over unchanged.
+
+    ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
+    client must not be able to scale its own vote in a robust aggregate. A round with no clients
+    returns ``None`` and leaves the state as it was; a round that trusts nobody returns all +0.
+    Float32 params, at most 4096 clients a round; no host synchronisation."""
+
+    def init():
+        return FLTrustAggregatorState()
+
+    def apply(clients_params_and_weights, state):
+        if state is None or state.server_delta is None:
+            raise ValueError("fltrust_aggregator: set state.server_delta (the server's own delta of this round) "
+                             "with state.replace(server_delta=...) before apply")
+        ids, params = [], []
+        for client_id, param, _ in clients_params_and_weights:  # the weights are not used
+            ids.append(client_id)
+            params.append(param)
+        got = tree_util.tree_fltrust(params, state.server_delta)
+        if got is None:
+            return None, state
+        return got.mean, FLTrustAggregatorState(state.server_delta, dict(zip(ids, got.trust.unbind())),
+                                                dict(zip(ids, got.factors.unbind())))
 
     return Aggregator(init, apply)

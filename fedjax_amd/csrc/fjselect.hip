@@ -183,11 +183,8 @@ __global__ __launch_bounds__(kThreads) void k_gather_members(const int64_t* __re
   int count = seg[1] - seg[0];
   if (count > M_max) count = M_max;
   const int64_t n = (int64_t)count * L;
-  for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * kThreads) {
-    const int64_t j = idx / L, l = idx - j * L;
-    const int c = order[j];
-    if ((unsigned)c < (unsigned)K) group[idx] = all[(int64_t)c * L + l];
-  }
+  for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * kThreads)
+    gather_member_word(all, L, K, order, idx, group);
 }
 
 // Bulyan's first launch: row i's K - 1 (key, index) pairs sorted by (key, index) in LDS and written

@@ -151,6 +151,16 @@ FJS_HD int flags_below(const uint8_t* flags, int i) {
   return n;
 }
 
+// One word of a group's plan image (fjagg_gather_member_ptrs; fjtrust.hip's gather): word idx is leaf
+// idx % L of member slot j = idx / L and gets client order[j]'s pointer to that leaf from all[K*L].
+// An order entry outside [0, K) copies nothing, whoever wrote the table.
+FJS_HD void gather_member_word(const int64_t* __restrict__ all, int L, int K, const int32_t* __restrict__ order,
+                               int64_t idx, int64_t* __restrict__ group) {
+  const int64_t j = idx / L, l = idx - j * L;
+  const int c = order[j];
+  if ((unsigned)c < (unsigned)K) group[idx] = all[(int64_t)c * L + l];
+}
+
 // gscale of a group of `count` unit weights: the host's (1. / W if W > 0. else 0.), then float32
 FJS_HD float krum_gscale(int count) { return count > 0 ? (float)div_rn(1.0, (double)count) : 0.0f; }
 

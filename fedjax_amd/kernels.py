@@ -1456,6 +1456,221 @@ def centered_clip_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, max_n
     return distances, factors
 
 
+FLTRUST_MAX_CLIENTS = 4096  # fjagg_fltrust_*: the client limit (fjagg.h)
+_FLTRUST_WS = {}  # (device index, stream handle) -> workspace of an FLTrust round or row pass
+
+
+def _fltrust_workspace(dev: torch.device, need: int) -> torch.Tensor:
+    """The workspace of an FLTrust round on ``dev``'s current stream (the sums, the member tables
+    and the block partials), cached like :func:`_center_workspace`; under stream capture a tensor
+    of the graph's own pool. Never zeroed, nothing carried between calls."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    key = (dev.index, _stream_handle(dev))
+    ws = _FLTRUST_WS.get(key)
+    if ws is None and len(_FLTRUST_WS) >= 16:
+        _FLTRUST_WS.clear()
+    if ws is None or ws.numel() < need:
+        ws = _FLTRUST_WS[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def check_fltrust_clients(K: int) -> int:
+    """``K`` of an FLTrust round, checked: ``1 <= K <= 4096``. Nothing here touches the library."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"fltrust needs at least 1 client, got K = {K}")
+    if K > FLTRUST_MAX_CLIENTS:
+        raise ValueError(f"fltrust supports K <= {FLTRUST_MAX_CLIENTS} clients, got K = {K}")
+    return K
+
+
+def _check_fltrust_slab(x: torch.Tensor) -> Tuple[int, int]:
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"fltrust takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    check_fltrust_clients(K)
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("fltrust takes rows of up to 1 GiB")
+    return K, P
+
+
+def _check_fltrust_vector(name: str, v: torch.Tensor, P: int) -> None:
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 tensor")
+    if v.dim() != 1 or v.numel() != P or not v.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 tensor of {P} elements")
+
+
+def _fltrust_leaf_table(leaf_table: Optional[torch.Tensor], max_n, P: int):
+    """``(L, max_n, table address or None)`` of a dense row's leaf table ``off[L] | n[L]``."""
+    if leaf_table is None:
+        return 1, P, None
+    if not isinstance(leaf_table, torch.Tensor) or leaf_table.dtype != torch.int64 or leaf_table.dim() != 1 \
+            or leaf_table.numel() < 2 or leaf_table.numel() % 2 or not leaf_table.is_contiguous():
+        raise TypeError("leaf_table must be a contiguous int64 device tensor off[L] | n[L]")
+    L = leaf_table.numel() // 2
+    if L > 65535:
+        raise ValueError(f"fltrust takes up to 65535 leaves, got {L}")
+    if max_n is None or isinstance(max_n, (bool, np.bool_)) or not 0 <= int(max_n) <= P:
+        raise ValueError("a leaf table needs max_n, its largest leaf size, in [0, P]")
+    return L, int(max_n), leaf_table.data_ptr()
+
+
+def dotsq_rows(image_dev: torch.Tensor, R: int, max_n: int, *, rows_per_group: int = 1):
+    """FLTrust's row pass on its own (``fjagg_dotsq_rows``): ``image_dev`` is the int64 device
+    image ``ptrs[R] | n[R] | ref_ptrs[R]`` of float32 rows and of the vector each is paired with
+    (4-byte alignment is all a row needs). Returns ``(dot, sq)``, float32 ``[R / rows_per_group]``:
+    ``sum fl(x * ref)`` and ``sum fl(x^2)`` over a group's rows, ONE read of the rows, both in
+    ``fjagg_l2sq_rows``' order (``sq`` has its bits). What a cosine-based rule starts from."""
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    R, max_n, rows_per_group = int(R), int(max_n), int(rows_per_group)
+    if R < 1 or rows_per_group < 1 or R % rows_per_group or max_n < 0 or image_dev.numel() < 3 * R:
+        raise ValueError(f"bad rows: R = {R}, rows_per_group = {rows_per_group}, image of {image_dev.numel()} words")
+    if max_n * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the row pass takes rows of up to 1 GiB")
+    dev = _require_device(image_dev)
+    G = R // rows_per_group
+    both = torch.empty(2, G, dtype=torch.float32, device=dev)
+    ws = _fltrust_workspace(dev, int(_lib.load().fjagg_dotsq_rows_workspace_bytes(R, max_n)))
+    _lib.call("fjagg_dotsq_rows", _lib.F32, image_dev.data_ptr(), R, max_n, rows_per_group, both[0].data_ptr(),
+              both[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle(dev))
+    return both[0], both[1]
+
+
+def dotsq_dense(x: torch.Tensor, ref: torch.Tensor, *, leaf_table: Optional[torch.Tensor] = None,
+                max_n: Optional[int] = None, nontemporal: bool = False):
+    """:func:`dotsq_rows` over a float32 slab ``x[K, P]`` against ONE shared vector ``ref`` (float32
+    ``[P]``, ``fjagg_dotsq_dense``): ``(dot, sq)``, float32 ``[K]``. ``leaf_table`` / ``max_n`` as
+    :func:`centered_clip_dense` takes them: the sums then add up leaf by leaf as the pytree route's
+    do. The table lives on the device and is TRUSTED (checking it would take a host visit): the caller
+    guarantees ``off[l] + n[l] <= P`` and ``n[l] <= max_n``; a wrong entry reads outside the rows.
+    ``nontemporal`` streams the deltas past the cache, which keeps ``ref`` in it."""
+    K, P = _check_fltrust_slab(x)
+    _check_fltrust_vector("ref", ref, P)
+    L, max_n, tab = _fltrust_leaf_table(leaf_table, max_n, P)
+    dev = _require_device(x, ref) if leaf_table is None else _require_device(x, ref, leaf_table)
+    both = torch.empty(2, K, dtype=torch.float32, device=dev)
+    ws = _fltrust_workspace(dev, int(_lib.load().fjagg_dotsq_rows_workspace_bytes(K * L, max_n)))
+    _lib.call("fjagg_dotsq_dense", _lib.F32, x.data_ptr(), x.stride(0) if K > 1 else P, K, P, tab, L, max_n,
+              ref.data_ptr(), both[0].data_ptr(), both[1].data_ptr(), ws.data_ptr(), ws.numel(),
+              _lib.NONTEMPORAL if nontemporal else 0, _stream_handle(dev))
+    return both[0], both[1]
+
+
+class FLTrustDiagnostics(NamedTuple):
+    """What FLTrust's selection reports, all on the device: ``trust`` / ``cosines`` float64 [K];
+    ``factors`` / ``norms`` float32 [K]; ``server_norm`` float32, ``count`` int32 and ``total``
+    float64 scalars (see :class:`fedjax_amd.tree_util.FLTrustResult`)."""
+    trust: torch.Tensor
+    cosines: torch.Tensor
+    factors: torch.Tensor
+    norms: torch.Tensor
+    server_norm: torch.Tensor
+    count: torch.Tensor
+    total: torch.Tensor
+
+
+def _fltrust_diagnostics(K: int, dev: torch.device) -> FLTrustDiagnostics:
+    d = torch.empty(2 * K + 1, dtype=torch.float64, device=dev)  # trust | cosines | total
+    f = torch.empty(2 * K + 1, dtype=torch.float32, device=dev)  # factors | norms | server_norm
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    return FLTrustDiagnostics(d[:K], d[K:2 * K], f[:K], f[K:2 * K], f[2 * K], count, d[2 * K])
+
+
+def _fltrust_diag_args(d: FLTrustDiagnostics):
+    return (d.cosines.data_ptr(), d.trust.data_ptr(), d.factors.data_ptr(), d.norms.data_ptr(),
+            d.server_norm.data_ptr(), d.total.data_ptr(), d.count.data_ptr())
+
+
+def fltrust_select(dot: torch.Tensor, sq: torch.Tensor, server_sq: torch.Tensor):
+    """FLTrust's selection on the device (``fjagg_fltrust_select``; the rule of
+    ``fedjax_amd/csrc/fjtrust_dev.h``): from the float32 sums ``dot[K]``, ``sq[K]`` of
+    :func:`dotsq_dense` and the server delta's squared norm ``server_sq`` (one float32), the
+    cosines, trust scores ``ts = min(max(cos, 0), 1)``, rescale factors ``c = ts |g| / |x_k|`` and
+    the member tables of the fold (the clients with ``c > 0`` ascending, ``wperm = c``, ``gscale =
+    f32(1 / sum ts)``). Returns ``(diagnostics, tables)``: :class:`FLTrustDiagnostics` and the
+    :class:`DeviceGroupTables` of :func:`grouped_sum_dense_device`. One launch of one workgroup, no
+    host synchronisation, nothing uploaded: capturable."""
+    if not isinstance(dot, torch.Tensor) or dot.dim() != 1:
+        raise ValueError("dot must be a float32 [K] device tensor")
+    K = check_fltrust_clients(dot.numel())
+    _f32_vector("dot", dot, K)
+    _f32_vector("sq", sq, K)
+    if not isinstance(server_sq, torch.Tensor) or server_sq.dtype != torch.float32 or server_sq.numel() != 1:
+        raise ValueError("server_sq must be a float32 device tensor of one element")
+    dev = _require_device(dot, sq, server_sq)
+    diag = _fltrust_diagnostics(K, dev)
+    tables = _select_tables(K, dev)
+    _lib.call("fjagg_fltrust_select", dot.data_ptr(), sq.data_ptr(), server_sq.data_ptr(), K, *_fltrust_diag_args(diag),
+              tables.order.data_ptr(), tables.seg.data_ptr(), tables.wperm.data_ptr(), tables.gscale.data_ptr(),
+              _stream_handle(dev))
+    return diag, tables
+
+
+def fltrust_dense(x: torch.Tensor, server: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+                  leaf_table: Optional[torch.Tensor] = None, max_n: Optional[int] = None,
+                  nontemporal: bool = False):
+    """A whole FLTrust round over a float32 slab ``x[K, P]`` against the server delta ``server``
+    (float32 ``[P]``; ``fjagg_fltrust_dense``): the server norm, the row pass, the selection, ``out``
+    zeroed, then the grouped fold over the clients the selection trusted — the others are never
+    loaded by that second read. Returns ``(out, diagnostics)``; ``out`` (float32 ``[P]``, fresh by
+    default) must overlap neither ``x`` nor ``server``. No host synchronisation and nothing uploaded:
+    capturable. ``leaf_table`` / ``max_n`` as :func:`dotsq_dense` takes them: the table's entries are
+    trusted, not checked (:class:`~fedjax_amd.slab.ClientDeltaSlab` builds its own). ``K <= 4096``;
+    every host-side argument is checked before the library is touched."""
+    K, P = _check_fltrust_slab(x)
+    _check_fltrust_vector("server", server, P)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    _check_fltrust_vector("out", out, P)
+    b, x0 = out.data_ptr(), x.data_ptr()
+    if b < server.data_ptr() + 4 * P and server.data_ptr() < b + 4 * P:
+        raise ValueError("out must not overlap the server delta")
+    if b < x0 + 4 * ((K - 1) * (x.stride(0) if K > 1 else P) + P) and x0 < b + 4 * P:
+        raise ValueError("out must not overlap the deltas x: their rows are read while out is written")
+    L, max_n, tab = _fltrust_leaf_table(leaf_table, max_n, P)
+    dev = _require_device(x, server, out) if leaf_table is None else _require_device(x, server, out, leaf_table)
+    diag = _fltrust_diagnostics(K, dev)
+    ws = _fltrust_workspace(dev, int(_lib.load().fjagg_fltrust_workspace_bytes(K, L, max_n)))
+    _lib.call("fjagg_fltrust_dense", _lib.F32, x.data_ptr(), x.stride(0) if K > 1 else P, K, P, tab, L, max_n,
+              server.data_ptr(), out.data_ptr(), *_fltrust_diag_args(diag), ws.data_ptr(), ws.numel(),
+              _lib.NONTEMPORAL if nontemporal else 0, _stream_handle(dev))
+    return out, diag
+
+
+def fltrust_ptrs(image_all: torch.Tensor, image_group: torch.Tensor, L: int, K: int, nblk: int, max_n: int, *,
+                 unaligned: bool = False, nontemporal: bool = False) -> FLTrustDiagnostics:
+    """:func:`fltrust_dense` over pytrees (``fjagg_fltrust_ptrs``): ``image_all`` is ``in_ptrs[K*L] |
+    server_ptrs[L] | leaf_n[L]``, ``image_group`` the grouped fold's plan for ``K`` member slots,
+    ``in_ptrs[K*L] | out_ptrs[L] | leaf_n[L] | blocks[2*nblk]``, whose slots the round fills on the
+    device. ``max_n`` is the largest ``leaf_n``; ``unaligned`` as the plan was made. The result is
+    behind ``out_ptrs``; returns the :class:`FLTrustDiagnostics`."""
+    for name, t in (("image_all", image_all), ("image_group", image_group)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous int64 device tensor")
+    K = check_fltrust_clients(K)
+    L, nblk, max_n = int(L), int(nblk), int(max_n)
+    if L < 1 or L > 65535 or nblk < 1 or image_all.numel() < K * L + 2 * L \
+            or image_group.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, images of {image_all.numel()} and "
+                         f"{image_group.numel()} words")
+    if max_n < 0 or max_n * 4 > _MAX_ROW_BYTES:
+        raise ValueError("fltrust takes leaves of up to 1 GiB")
+    dev = _require_device(image_all, image_group)
+    diag = _fltrust_diagnostics(K, dev)
+    ws = _fltrust_workspace(dev, int(_lib.load().fjagg_fltrust_workspace_bytes(K, L, max_n)))
+    flags = (_lib.UNALIGNED if unaligned else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    _lib.call("fjagg_fltrust_ptrs", _lib.F32, image_all.data_ptr(), image_group.data_ptr(), L, K, nblk, max_n,
+              *_fltrust_diag_args(diag), ws.data_ptr(), ws.numel(), flags, _stream_handle(dev))
+    return diag
+
+
 TOPK_MAX_CLIENTS = _lib.TOPK_MAX_CLIENTS  # fjcomp_topk_*: the clipped fold's client limit (fjcomp.h)
 TOPK_CHUNK = _lib.TOPK_CHUNK  # elements of one row a histogram workgroup counts (FJCOMP_TOPK_CHUNK)
 TOPK_MAX_PARAMS = (1 << 31) - 1  # P < 2^31: the counts and ranks of the select are 32-bit

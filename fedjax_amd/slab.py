@@ -514,7 +514,7 @@ class ClientDeltaSlab:
         median = self.grouped_mean(a32, ids, 1)[0] if (ids >= 0).any() else None
         return tree_util.GeometricMedianResult(median, a32, d, gram)
 
-    def _flat_center(self, center) -> torch.Tensor:
+    def _flat_center(self, center, name: str = "center") -> torch.Tensor:
         """``center`` of :meth:`centered_clip` as a flat float32 [num_params] device tensor: zeros for
         ``None``, the tensor itself when it is flat, a fresh row filled from a pytree's leaves."""
         P = self.num_params
@@ -522,17 +522,17 @@ class ClientDeltaSlab:
             return torch.zeros(P, dtype=torch.float32, device=self.device)
         if isinstance(center, torch.Tensor):
             if center.dtype != torch.float32:
-                raise TypeError(f"center must be float32, not {center.dtype}")
+                raise TypeError(f"{name} must be float32, not {center.dtype}")
             if center.dim() != 1 or center.numel() != P or not center.is_contiguous() or center.device != self.storage.device:
-                raise ValueError(f"a flat center is a contiguous float32 [{P}] tensor on {self.storage.device}")
+                raise ValueError(f"a flat {name} is a contiguous float32 [{P}] tensor on {self.storage.device}")
             return center
         leaves = pytree.flatten_as(self.treedef, center)
         flat = torch.empty(P, dtype=torch.float32, device=self.device)
         for l, (dst, src, shape) in enumerate(zip(pytree.leaves_of(self.unflatten(flat)), leaves, self.shapes)):
             if not isinstance(src, torch.Tensor) or src.dtype != torch.float32:
-                raise TypeError(f"center leaf {l} must be a float32 tensor")
+                raise TypeError(f"{name} leaf {l} must be a float32 tensor")
             if tuple(src.shape) != shape or src.device != self.storage.device:
-                raise ValueError(f"center leaf {l} must have shape {shape} on {self.storage.device}")
+                raise ValueError(f"{name} leaf {l} must have shape {shape} on {self.storage.device}")
             dst.copy_(src)
         return flat
 
@@ -592,6 +592,48 @@ class ClientDeltaSlab:
             rows, tau, self._flat_center(center), iterations=iterations, out=out, leaf_table=tab,
             max_n=max(self.sizes), nontemporal=rows.numel() * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
         return tree_util.CenteredClip(self.unflatten(flat), distances, factors)
+
+    def fltrust(self, server_delta, *, out: Optional[torch.Tensor] = None) -> "tree_util.FLTrustResult":
+        """FLTrust over the K rows (Cao, Fang, Liu and Gong, NDSS 2021): every client is weighed by
+        the ReLU of the cosine between its delta and ``server_delta`` — the delta the server computed
+        itself on a small trusted dataset — rescaled to that delta's norm, and the trust-weighted
+        mean is taken. ``server_delta`` is a flat float32 ``[num_params]`` tensor or a pytree of the
+        template's structure (copied into a flat row on the device). The arithmetic is
+        :func:`fedjax_amd.tree_util.tree_fltrust`'s, and every field of the result is bit for bit
+        that function's over the same deltas (the sums add up leaf by leaf in both). There are no
+        weights.
+
+        ``out``: a flat float32 ``[num_params]`` tensor for the mean; it must overlap neither the
+        slab nor ``server_delta``. Two reads of the slab — the second skips every client that was
+        gated out — and a handful of small launches, no host synchronisation. The only upload is
+        the slab's leaf table, once, on the first call of this or of :meth:`centered_clip`: every
+        later call, one under stream capture included, uploads nothing — after one eager call a
+        round can be captured and replayed over rewritten deltas and a rewritten server delta, and
+        each replay selects afresh. A first call under capture raises. Returns a
+        :class:`~fedjax_amd.tree_util.FLTrustResult` of device tensors whose ``mean`` is the
+        template's pytree of views into ``out``, all +0 when nobody is trusted; a float32 slab of
+        up to 4096 clients."""
+        if self.dtype != torch.float32:
+            raise TypeError(f"fltrust needs a float32 slab, not {self.dtype}")
+        K, P = kernels.check_fltrust_clients(self.num_clients), self.num_params
+        if server_delta is None:
+            raise ValueError("fltrust needs a server_delta (there is no default: the rule has no other anchor)")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
+            raise TypeError("out must be a float32 tensor")
+        if out is not None and (out.dim() != 1 or out.numel() != P or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of {P} elements")
+        if len(self.sizes) > 65535:
+            raise ValueError(f"fltrust takes up to 65535 leaves, got {len(self.sizes)}")
+        server = self._flat_center(server_delta, "server_delta")
+        if P == 0:  # a template of empty leaves: every sum is the empty sum, nobody is trusted
+            flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+            return tree_util.FLTrustResult(self.unflatten(flat), *tree_util._fltrust_nobody(K, self.device))
+        tab = self._center_leaf_table()
+        rows = self.rows
+        flat, d = kernels.fltrust_dense(rows, server, out=out, leaf_table=tab, max_n=max(self.sizes),
+                                        nontemporal=rows.numel() * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
+        return tree_util.FLTrustResult(self.unflatten(flat), d.trust, d.cosines, d.factors, d.norms, d.server_norm,
+                                       d.count, d.total)
 
     def _topk_weight_vector(self, weights: Sequence) -> torch.Tensor:
         """The float32 weights on the device for :meth:`topk_mean`. The vector of the latest call

@@ -2260,6 +2260,104 @@ def tree_centered_clip(pytrees: Iterable[PyTree], tau, center: Optional[PyTree] 
     return CenteredClip(result, distances, factors)
 
 
+class FLTrustResult(NamedTuple):
+    """Result of FLTrust (:func:`tree_fltrust`, :meth:`fedjax_amd.slab.ClientDeltaSlab.fltrust`);
+    nothing of it has visited the host. ``mean`` — the trust-weighted mean of the rescaled client
+    deltas, a pytree of the clients' structure, all +0 when nobody is trusted (never ``None``: the
+    count is not known on the host); per client in input order, device tensors ``[K]``: ``trust`` —
+    float64, ``ts_k = min(max(cos_k, 0), 1)``, 0 for a client that was gated out; ``cosines`` —
+    float64, the cosine between the client's delta and the server's (NaN for a client holding a NaN
+    or all zeros); ``factors`` — float32, ``c_k = ts_k |g| / |x_k|``, what the fold multiplied the
+    client by (0: never loaded); ``norms`` — float32, ``|x_k|``; and the device scalars
+    ``server_norm`` (float32 ``|g|``), ``count`` (int32, the clients with ``c_k > 0``) and ``total``
+    (float64 ``sum_k ts_k``, the divisor). Read ``count`` when you want to: that is the only
+    synchronisation."""
+    mean: Any
+    trust: Any
+    cosines: Any
+    factors: Any
+    norms: Any
+    server_norm: Any
+    count: Any
+    total: Any
+
+
+def _fltrust_nobody(K: int, device: torch.device):
+    """The diagnostics of a round without a single element: every sum is the empty sum, so every
+    cosine is 0/0 and nobody is trusted."""
+    return (torch.zeros(K, dtype=torch.float64, device=device),
+            torch.full((K,), float("nan"), dtype=torch.float64, device=device),
+            torch.zeros(K, dtype=torch.float32, device=device), torch.zeros(K, dtype=torch.float32, device=device),
+            torch.zeros((), dtype=torch.float32, device=device), torch.zeros((), dtype=torch.int32, device=device),
+            torch.zeros((), dtype=torch.float64, device=device))
+
+
+def tree_fltrust(pytrees: Iterable[PyTree], server_delta: PyTree) -> Optional[FLTrustResult]:
+    """FLTrust over client pytrees (Cao, Fang, Liu and Gong, NDSS 2021): the server computes a delta
+    ``g`` of its own on a small trusted dataset, and every client is judged against it, not against
+    the other clients — the rule needs no honest majority::
+
+        cos_k = <x_k, g> / (|x_k| |g|);  ts_k = min(max(cos_k, 0), 1);  c_k = ts_k |g| / |x_k|
+        y = (sum_k c_k x_k) / sum_k ts_k
+
+    a client is weighed by the ReLU of its cosine, rescaled to the server delta's norm, and the
+    trust-weighted mean is taken. The inner products and squared norms are float32 sums in
+    :func:`tree_l2_norms`' order, taken in ONE read of the deltas; the cosines, trust scores and
+    factors are float64 on the device (``include/fjagg.h`` fixes every rounding); the second read is
+    the grouped fold over the clients with ``c_k > 0`` in client order from +0, times
+    ``f32(1 / sum ts)``. A client with ``c_k = 0`` is never loaded by it: one holding a NaN, an inf
+    or 1e30, an all-zero one, one pointing away from ``g`` (``cos <= 0``) and one so small that its
+    squared norm underflows cannot reach the result. A zero or non-finite ``server_delta`` trusts
+    nobody. For finite inputs ``|y| <= |g|`` up to rounding. There are no client weights.
+
+    ``server_delta`` is a pytree of the clients' structure with float32 leaves on their device; it
+    and the inputs are never written. O(K P), two reads, no host synchronisation. The result is a
+    fresh pytree (slices of one allocation), bit for bit
+    :meth:`fedjax_amd.slab.ClientDeltaSlab.fltrust` over the same deltas. Float32 leaves,
+    ``K <= 4096``, at most 65535 leaves. Returns :class:`FLTrustResult`, whose ``mean`` is all +0 when
+    nobody is trusted; no clients: ``None``. Raises under stream capture (the plan image goes
+    through a pinned staging buffer; the slab route is capturable). Out of scope: bfloat16, client
+    weights, a fused server step, several GPUs, and producing ``server_delta`` itself."""
+    trees = pytrees if type(pytrees) is list else list(pytrees)
+    if not trees:
+        return None
+    K = kernels.check_fltrust_clients(len(trees))
+    what = "tree_fltrust"
+    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
+                  if _CANONICAL.get(x.dtype) != torch.float32})
+    if bad:
+        raise TypeError(f"{what} needs float32 leaves (got {bad})")
+    td, rows = _client_table(trees)
+    if not rows[0]:
+        pytree.flatten_as(td, server_delta)
+        return FLTrustResult(pytree.unflatten(td, []), *_fltrust_nobody(K, _default_device()))
+    device = rows[0][0].device
+    leaf_n = np.array([x.numel() for x in rows[0]], dtype=np.int64)
+    L = len(leaf_n)
+    if L > 65535:
+        raise ValueError(f"{what} takes up to 65535 leaves, got {L}")
+    if int(leaf_n.max()) * 4 > kernels._MAX_ROW_BYTES:
+        raise ValueError(f"{what} takes leaves of up to 1 GiB")
+    held = _center_leaves(server_delta, td, rows[0], what)  # (keeps a contiguous copy alive past the launch)
+    # one result row: every leaf at a 16-byte aligned offset
+    offs = np.concatenate([[0], np.cumsum((leaf_n + 3) // 4 * 4)]).astype(np.int64)
+    flat = torch.empty(max(int(offs[-1]), 4), dtype=torch.float32, device=device)
+    result = pytree.unflatten(td, [flat[o:o + n].view(x.shape) for o, n, x in zip(offs[:-1], leaf_n, rows[0])])
+    if not leaf_n.any():  # only empty leaves: nothing to read, nobody to trust
+        return FLTrustResult(result, *_fltrust_nobody(K, device))
+    in_ptrs = _ptr_table(rows)
+    server_ptrs = np.array([v.data_ptr() for v in held], dtype=np.int64)
+    out_ptrs = flat.data_ptr() + 4 * offs[:-1]
+    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)  # any client may become a member
+    all_words = K * L + 2 * L
+    # in_ptrs[K*L] | server_ptrs | leaf_n, then the group image, whose member slots the round fills
+    image = np.concatenate([in_ptrs.ravel(), server_ptrs, leaf_n, np.zeros(K * L, np.int64), out_ptrs, leaf_n, blocks])
+    image_dev = _lib.upload(torch.from_numpy(image), device)
+    d = kernels.fltrust_ptrs(image_dev[:all_words], image_dev[all_words:], L, K, len(blocks) // 2, int(leaf_n.max()),
+                             nontemporal=int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES)
+    return FLTrustResult(result, d.trust, d.cosines, d.factors, d.norms, d.server_norm, d.count, d.total)
+
+
 class BulyanResult(NamedTuple):
     """Result of Bulyan (:func:`tree_bulyan`, :meth:`fedjax_amd.slab.ClientDeltaSlab.bulyan`):
     ``mean`` — the mean around the median over the selected clients (``None`` when fewer than

@@ -25,6 +25,7 @@
  *     (no reference row) mean around the median / Bulyan        fjagg_meamed_* (the keep values nearest the median)
  *     (no reference row) Bulyan on the device                   fjagg_bulyan_select, fjagg_meamed_*_dev
  *     (no reference row) centered clipping (Karimireddy et al. 2021) fjagg_center_* (clipped around the last aggregate)
+ *     (no reference row) FLTrust (Cao et al. 2021)              fjagg_dotsq_*, fjagg_fltrust_* (trust-weighted mean against a server delta)
  *
  * The reference has no native code: each of those rows is a `jax.jit` dispatch
  * into XLA. The Python mirror of the reference's API
@@ -840,6 +841,88 @@ int fjagg_center_clip_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t
 int fjagg_center_clip_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t max_n,
                            float tau, int64_t iterations, float* distances_dev, float* factors_dev, void* ws_dev,
                            int64_t ws_bytes, int flags, void* stream);
+
+/*
+ * FLTrust: the trust-weighted mean of the client deltas against a delta g the server computed itself
+ * on a small trusted dataset (Cao, Fang, Liu and Gong, "FLTrust: Byzantine-robust Federated Learning
+ * via Trust Bootstrapping", NDSS 2021). It needs no honest majority. The reference has no such
+ * aggregator; the semantics are fixed here and in fedjax_amd/csrc/fjtrust_dev.h.
+ * Float32 deltas x_k, server delta and result, 1 <= K <= 4096, no client weights, leaves
+ * l = 0 .. L-1 in flatten order.
+ * Pass 1, float32, no FMA:
+ *     a_k = sum_p fl(x_k[p] * g[p]);  q_k = sum_p fl(x_k[p]^2)
+ *   both in fjagg_l2sq_rows' order exactly: leaf by leaf, in 64 Ki-element blocks; lane t of 256 adds
+ *   elements t, t + 256, ... ascending from +0; the xor shuffle tree 32 .. 1; the four wave sums in
+ *   order; the block partials in leaf / block order from +0. q_k has fjagg_l2sq_rows' bits, and
+ *     q_s = sum_p fl(g[p]^2)     is fjagg_l2sq_rows' own output over the server delta's leaves.
+ * Selection, float64, no FMA, one rounding per operation:
+ *     n_k = sqrt((double)q_k);  n_s = sqrt((double)q_s);  cos_k = (double)a_k / (n_k * n_s)
+ *     ts_k = cos_k > 0 ? min(cos_k, 1) : 0            (a NaN gives 0)
+ *     c_k  = ts_k > 0 ? (float)((ts_k * n_s) / n_k) : 0
+ *     c_k not a finite float32 > 0: c_k = 0 and ts_k = 0
+ *     T = sum_k ts_k in client order from +0.0, sequentially;  r = T > 0 ? (float)(1.0 / T) : 0
+ *     order[K] = the clients with c_k > 0, ascending (0 padded); seg = {0, count};
+ *     wperm[j] = c_order[j] (0 padded); gscale[0] = r
+ *   and the diagnostics cos[K], trust[K] = ts (double), factors[K] = c, norms[K] = (float)n_k,
+ *   server_norm = (float)n_s, total = T, count. A NaN cosine or norm is stored as the quiet NaN
+ *   0x7ff8000000000000 / 0x7fc00000 (the payload of a 0/0 is the processor's).
+ * Pass 2, the grouped fold above with G = 1 (fjagg_wsum_group_*_dev) over those tables:
+ *     s = +0; s = fl(s + fl(x_m[p] * c_m)) in member order;  y[p] = fl(s * r)
+ *   A client that is not in the table is never loaded. A count of 0 writes nothing, so the drivers
+ *   zero y first: a round that trusts nobody gives all +0.
+ * Consequences: a client holding a NaN has a or q NaN, so ts = 0. One holding inf or 1e30 has
+ * q = inf, so cos is 0 or NaN and ts = 0. An all-zero client gives 0/0, so ts = 0. A client so small
+ * that q underflows to 0 gets c = inf, which is zeroed. A zero or non-finite server delta trusts
+ * nobody. For finite inputs |y| <= |g| up to rounding: y is a convex combination of vectors of norm
+ * n_s. The clamp at 1 matters: on clients that are exact multiples of g the float32 sums give cos up
+ * to 1 + 1.5e-7.
+ * No entry visits the host or synchronises; all are capturable. Flags: FJAGG_NONTEMPORAL (the deltas
+ * of both passes) and, on fjagg_fltrust_ptrs, FJAGG_UNALIGNED (the flag the plan was made with).
+ * Refused with nothing launched, all with the one code FJAGG_EUNSUPPORTED: a dtype other than
+ * FJAGG_F32; K < 1 or K > 4096; P < 1 or ld < P; rows over 1 GiB; a null pointer; too small a
+ * workspace (or, for the drivers, one not 16-byte aligned); an out overlapping the dense deltas, the
+ * server delta, the workspace or a diagnostics buffer; a leaf table, row grouping or plan whose
+ * host-side numbers are bad (L > 65535, max_n > P); any other flag. fjagg_last_error names the limit.
+ * What lives in device memory is TRUSTED, because checking it would take a host visit: a leaf table's
+ * entries (the caller guarantees off[l] + n[l] <= P and n[l] <= max_n), the pointers and sizes of an
+ * image, the plan blocks. A wrong entry reads outside the rows. The diagnostics buffers must not
+ * overlap each other, the workspace or the inputs; of these only out is checked.
+ */
+/* The row pass alone over rows at arbitrary 4-byte aligned addresses: image_dev = ptrs[R] | n[R] |
+ * ref_ptrs[R] (fjagg_l2sq_rows_centered's image), dot[g] and sq[g] the sums over the rows_per_group
+ * rows of group g in the order above. R is not limited to 65535. */
+int64_t fjagg_dotsq_rows_workspace_bytes(int64_t R, int64_t max_n);
+int fjagg_dotsq_rows(int in_dtype, const int64_t* image_dev, int64_t R, int64_t max_n, int64_t rows_per_group,
+                     float* dot_dev, float* sq_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+/* The same over a dense slab against one shared vector ref_dev[P]: client k's row at x_dev + k*ld
+ * elements. leaf_tab_dev = off[L] | n[L] (int64 element offsets and sizes of the row's leaves, max_n
+ * the largest) gives the sums their leaf-by-leaf order; NULL with L = 1 takes the row as one leaf.
+ * Workspace: fjagg_dotsq_rows_workspace_bytes(K * L, max_n). */
+int fjagg_dotsq_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const int64_t* leaf_tab_dev,
+                      int64_t L, int64_t max_n, const void* ref_dev, float* dot_dev, float* sq_dev, void* ws_dev,
+                      int64_t ws_bytes, int flags, void* stream);
+/* The selection alone: one launch of one workgroup; T is added by one lane. Every index it writes
+ * lies in [0, K). */
+int fjagg_fltrust_select(const float* dot_dev, const float* sq_dev, const float* server_sq_dev, int64_t K,
+                         double* cos_dev, double* trust_dev, float* factors_dev, float* norms_dev,
+                         float* server_norm_dev, double* total_dev, int32_t* count_dev, int32_t* order_dev,
+                         int32_t* seg_dev, float* wperm_dev, float* gscale_dev, void* stream);
+/* Workspace of the two whole-round entries (the sums, the member tables, the block partials). */
+int64_t fjagg_fltrust_workspace_bytes(int64_t K, int64_t L, int64_t max_n);
+/* The whole round over a dense slab: server norm, row pass, selection, out zeroed, fold. server_dev and
+ * out_dev are float[P]; the leaf table as fjagg_dotsq_dense's. */
+int fjagg_fltrust_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const int64_t* leaf_tab_dev,
+                        int64_t L, int64_t max_n, const void* server_dev, void* out_dev, double* cos_dev,
+                        double* trust_dev, float* factors_dev, float* norms_dev, float* server_norm_dev,
+                        double* total_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes, int flags, void* stream);
+/* The whole round over pytrees: image_all_dev = in_ptrs[K*L] | server_ptrs[L] | leaf_n[L];
+ * image_group_dev = in_ptrs[K*L] (member slots, filled here as fjagg_gather_member_ptrs fills them) | out_ptrs[L] |
+ * leaf_n[L] | blocks[2*nblk], the plan of fjagg_wsum_group_ptrs_dev for M_max = K. Every output leaf
+ * is zeroed before the fold. max_n is the largest leaf_n. */
+int fjagg_fltrust_ptrs(int in_dtype, const int64_t* image_all_dev, int64_t* image_group_dev, int L, int64_t K,
+                       int64_t nblk, int64_t max_n, double* cos_dev, double* trust_dev, float* factors_dev,
+                       float* norms_dev, float* server_norm_dev, double* total_dev, int32_t* count_dev, void* ws_dev,
+                       int64_t ws_bytes, int flags, void* stream);
 
 /*
  * Synthetic client deltas for tests and benchmarks (never on the product path):
