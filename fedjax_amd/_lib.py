@@ -97,6 +97,8 @@ _SIGNATURES = {
                                               _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "fjagg_trim_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i32, _vp]),
     "fjagg_trim_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
+    "fjagg_trim_bucket_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _vp, _i32, _vp]),
+    "fjagg_trim_bucket_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_meamed_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _vp, _i32, _vp]),
     "fjagg_meamed_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_gram_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp]),

@@ -190,7 +190,23 @@ class RobustAggregatorState:
     """The trimmed-mean and median aggregators are stateless."""
 
 
-def trimmed_mean_aggregator(trim) -> Aggregator:
+def _bucket_rng(bucket_size, rng):
+    """The checked ``(bucket_size, rng)`` of a bucketed aggregator: ``rng`` a
+    :class:`fedjax_amd.random.PRNGSequence`, a key (then a sequence over it) or ``None``."""
+    if bucket_size is None:
+        if rng is not None:
+            raise ValueError("rng shuffles the clients of a bucketed aggregator: pass bucket_size too")
+        return None, None
+    if isinstance(bucket_size, (bool, np.bool_)) or not isinstance(bucket_size, (int, np.integer)):
+        raise TypeError(f"bucket_size must be an int >= 1, not {type(bucket_size).__name__}")
+    if bucket_size < 1:
+        raise ValueError(f"bucket_size must be >= 1, got {bucket_size}")
+    if rng is not None and not isinstance(rng, fj_random.PRNGSequence):
+        rng = fj_random.PRNGSequence(fj_random.strict_key(rng))
+    return int(bucket_size), rng
+
+
+def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None) -> Aggregator:
     """Builds the coordinate-wise trimmed-mean aggregator (Yin et al., ICML 2018): per coordinate
     the ``t`` smallest and ``t`` largest client values are dropped and the rest averaged, in one
     launch (:func:`fedjax_amd.tree_util.tree_trimmed_mean`). ``trim`` is the int count ``t`` or a
@@ -198,35 +214,61 @@ def trimmed_mean_aggregator(trim) -> Aggregator:
 
     ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
     client must not be able to scale its own vote in a robust aggregate. Float32 params, at most
-    128 clients a round."""
+    128 clients a round.
+
+    ``bucket_size=s`` is bucketing (Karimireddy, He and Jaggi, ICLR 2022): each round's clients
+    are shuffled, averaged in ``B = ceil(K / s)`` buckets of ``s`` and the rule runs over the
+    bucket means; at most 4096 clients and 128 buckets a round. ``rng`` is a
+    :class:`fedjax_amd.random.PRNGSequence` or a key (then a sequence over it): each ``apply``
+    draws one fresh key and shuffles with :func:`fedjax_amd.random.permutation`, on the device.
+    ``rng=None`` buckets consecutive clients, UNSHUFFLED, which the paper's guarantee does not
+    cover. ``trim`` and the Byzantine budget now count BUCKETS: ``f`` bad clients can spoil ``f``
+    buckets out of ``K / s``, so the fraction of bad clients that a given ``trim`` fraction
+    tolerates shrinks by ``s`` (the paper's ``delta * s`` condition)."""
     if isinstance(trim, (bool, np.bool_)) or not isinstance(trim, (int, float, np.integer, np.floating)):
         raise TypeError("trim must be an int count or a float fraction in [0, 0.5)")
     if isinstance(trim, (float, np.floating)) and not (0.0 <= float(trim) < 0.5):
         raise ValueError(f"a trim fraction must be in [0, 0.5), got {trim}")
     if isinstance(trim, (int, np.integer)) and trim < 0:
         raise ValueError(f"a trim count must be >= 0, got {trim}")
+    bucket_size, rng = _bucket_rng(bucket_size, rng)
 
     def init():
         return RobustAggregatorState()
 
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
-        return tree_util.tree_trimmed_mean(params, trim), state
+        if bucket_size is None or not params:
+            return tree_util.tree_trimmed_mean(params, trim, bucket_size=bucket_size), state
+        kernels.bucket_count(len(params), bucket_size)  # refuse the round before a key is drawn
+        perm = None if rng is None else fj_random.permutation(next(rng), len(params))
+        return tree_util.tree_trimmed_mean(params, trim, bucket_size=bucket_size, perm=perm), state
 
     return Aggregator(init, apply)
 
 
-def median_aggregator() -> Aggregator:
+def median_aggregator(*, bucket_size: Optional[int] = None, rng=None) -> Aggregator:
     """Builds the coordinate-wise median aggregator (Yin et al., ICML 2018):
     :func:`fedjax_amd.tree_util.tree_median` of the round's params. ``apply`` takes the usual
-    triples and IGNORES the weights. Float32 params, at most 128 clients a round."""
+    triples and IGNORES the weights. Float32 params, at most 128 clients a round.
+
+    ``bucket_size`` and ``rng`` as :func:`trimmed_mean_aggregator` takes them: the median of the
+    means of shuffled buckets of ``bucket_size`` clients, for up to 4096 clients a round;
+    ``rng=None`` buckets consecutive clients, UNSHUFFLED. The Byzantine budget counts BUCKETS:
+    the median tolerates fewer than half the buckets spoiled, so fewer than ``K / (2 s)`` bad
+    clients (the paper's ``delta * s`` condition)."""
+    bucket_size, rng = _bucket_rng(bucket_size, rng)
 
     def init():
         return RobustAggregatorState()
 
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
-        return tree_util.tree_median(params), state
+        if bucket_size is None or not params:
+            return tree_util.tree_median(params, bucket_size=bucket_size), state
+        kernels.bucket_count(len(params), bucket_size)  # refuse the round before a key is drawn
+        perm = None if rng is None else fj_random.permutation(next(rng), len(params))
+        return tree_util.tree_median(params, bucket_size=bucket_size, perm=perm), state
 
     return Aggregator(init, apply)
 

@@ -2,7 +2,9 @@
 // (include/fjagg.h: fjagg_trim_dense, fjagg_trim_ptrs; Yin et al., ICML 2018) and the mean
 // around the median (fjagg_meamed_dense, fjagg_meamed_ptrs; Xie et al. 2018), Bulyan's second
 // stage, also with its counts and row table read from device memory (fjagg_meamed_dense_dev,
-// fjagg_meamed_ptrs_dev), where fjagg_bulyan_select wrote them.
+// fjagg_meamed_ptrs_dev), where fjagg_bulyan_select wrote them. The trimmed mean and median also
+// run over the means of buckets of s clients (fjagg_trim_bucket_dense, fjagg_trim_bucket_ptrs;
+// Karimireddy, He and Jaggi, ICLR 2022), which lifts the client limit to 4096.
 //
 // Not a fold: every coordinate needs two order statistics of its K client values. One lane
 // owns one column (fjrobust_dev.h has the per-column routine and the reasons for its shape):
@@ -43,6 +45,7 @@ int check_launch(const char* what) {
 
 constexpr int64_t kTrimMaxRowBytes = 1ll << 30;
 constexpr int kTrimMaxClients = 128;
+constexpr int kBucketMaxClients = 4096;  // fjagg_trim_bucket_*: clients behind at most 128 buckets
 constexpr int kMeamedMaxSlabRows = 1024;  // the Gram pass's client limit: Bulyan selects among so many
 
 // Workgroup size per width: 256 lanes while the tile stays at 32 KiB, one wave above that
@@ -130,6 +133,51 @@ __global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_ptrs(const int64_t* 
                                                                   int t, float scale, int do_scale) {
   ptrs_walk<N, NT>(img, L, K, V, [=](auto load, fjrobust::KeyPair* tile) {
     return fjrobust::trim_column<N, TrimShape<N>::TPB>(load, K, t, do_scale != 0, scale, tile);
+  });
+}
+
+// Bucketing (fjagg_trim_bucket_*): the same column routine over B = ceil(K / s) bucket means, each
+// formed from s client loads where the routine asks for it (fjrobust_dev.h BucketLoad), so the
+// sort reads every delta once and the sum once more, with no B x P temporary. The client table
+// is int32 in device memory (null: the identity, the kernels' HP = false, so that no branch
+// stands between the table reads); its index is uniform over the wave, so an entry is a scalar
+// load, and BucketLoad clamps it into [0, K) before an address is formed.
+struct BucketArgs {
+  const int32_t* perm;
+  int K, s, B;
+  float inv_s, inv_last;
+};
+template <bool HP>
+__device__ __forceinline__ auto bucket_table(const int32_t* __restrict__ perm) {
+  return [=](int m) {
+    if constexpr (HP) return perm[m];
+    else return (int32_t)m;
+  };
+}
+
+template <int N, bool NT, bool HP>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_bucket_dense(const uint32_t* __restrict__ x, int64_t ld,
+                                                                          int64_t P, const BucketArgs b, int t,
+                                                                          float scale, int do_scale,
+                                                                          uint32_t* __restrict__ out) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const int64_t col0 = (int64_t)blockIdx.x * TPB, col = col0 + threadIdx.x;
+  const bool valid = col < P;
+  const uint32_t off = valid ? threadIdx.x : (uint32_t)(P - 1 - col0);
+  const uint32_t* base = x + col0;
+  auto load = [=](int k) { return load_bits<NT>(base + (int64_t)k * ld, off); };
+  auto bucket = fjrobust::bucket_load(load, bucket_table<HP>(b.perm), b.K, b.s, b.inv_s, b.inv_last);
+  const uint32_t y = fjrobust::trim_column<N, TPB>(bucket, b.B, t, do_scale != 0, scale, lane_tile<N, TPB>());
+  if (valid) store_bits(out + col, y);
+}
+
+template <int N, bool NT, bool HP>
+__global__ __launch_bounds__(TrimShape<N>::TPB) void k_trim_bucket_ptrs(const int64_t* __restrict__ img, int L, int V,
+                                                                         const BucketArgs b, int t, float scale,
+                                                                         int do_scale) {
+  ptrs_walk<N, NT>(img, L, b.K, V, [=](auto load, fjrobust::KeyPair* tile) {
+    auto bucket = fjrobust::bucket_load(load, bucket_table<HP>(b.perm), b.K, b.s, b.inv_s, b.inv_last);
+    return fjrobust::trim_column<N, TrimShape<N>::TPB>(bucket, b.B, t, do_scale != 0, scale, tile);
   });
 }
 
@@ -239,8 +287,8 @@ __global__ __launch_bounds__(256) void k_gather_rows(const int64_t* __restrict__
   }
 }
 
-// what both aggregates refuse: the dtype, the flags and the client count
-int column_check(const char* who, int in_dtype, int64_t K, int flags, int allowed) {
+// what every column aggregate refuses for its dtype and flags
+int flags_check(const char* who, int in_dtype, int flags, int allowed) {
   if (in_dtype != FJAGG_F32) return fail(FJAGG_EUNSUPPORTED, "%s: float32 deltas and output only", who);
   if (flags & FJAGG_ACCUMULATE)
     return fail(FJAGG_EUNSUPPORTED, "%s: order statistics do not accumulate (no FJAGG_ACCUMULATE)", who);
@@ -250,9 +298,32 @@ int column_check(const char* who, int in_dtype, int64_t K, int flags, int allowe
   if (flags & FJAGG_ZEROED_WS) return fail(FJAGG_EUNSUPPORTED, "%s: no norms (no FJAGG_ZEROED_WS)", who);
   if (flags & FJAGG_UNBALANCED) return fail(FJAGG_EUNSUPPORTED, "%s: no FJAGG_UNBALANCED", who);
   if (flags & ~allowed) return fail(FJAGG_EUNSUPPORTED, "%s: unsupported flags 0x%x", who, flags & ~allowed);
+  return FJAGG_OK;
+}
+
+// what both aggregates refuse: the dtype, the flags and the client count
+int column_check(const char* who, int in_dtype, int64_t K, int flags, int allowed) {
+  if (int rc = flags_check(who, in_dtype, flags, allowed)) return rc;
   if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
   if (K > kTrimMaxClients)
     return fail(FJAGG_EUNSUPPORTED, "%s: K <= %d clients (got %lld)", who, kTrimMaxClients, (long long)K);
+  return FJAGG_OK;
+}
+
+// fjagg_trim_bucket_*: the dtype and flags of fjagg_trim_*, then s, K, the bucket count B and t
+int bucket_check(int in_dtype, int64_t K, int64_t s, int64_t t, int flags, int allowed) {
+  if (int rc = flags_check("bucketed trimmed mean", in_dtype, flags, allowed)) return rc;
+  if (s < 1) return fail(FJAGG_EINVAL, "bucketed trimmed mean: bucket size s >= 1 (got %lld)", (long long)s);
+  if (K < 1) return fail(FJAGG_EINVAL, "K must be >= 1 (got %lld)", (long long)K);
+  if (K > kBucketMaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "bucketed trimmed mean: K <= %d clients (got %lld)", kBucketMaxClients,
+                (long long)K);
+  const int64_t B = (K + s - 1) / s;
+  if (B > kTrimMaxClients)
+    return fail(FJAGG_EUNSUPPORTED, "bucketed trimmed mean: B = ceil(K / s) <= %d buckets (got %lld of K=%lld, s=%lld)",
+                kTrimMaxClients, (long long)B, (long long)K, (long long)s);
+  if (t < 0 || 2 * t >= B)
+    return fail(FJAGG_EINVAL, "bucketed trimmed mean: need 0 <= 2t < B (t=%lld, B=%lld)", (long long)t, (long long)B);
   return FJAGG_OK;
 }
 
@@ -287,6 +358,34 @@ int launch_trim_ptrs(const int64_t* img, int L, int K, int64_t nblk, int V, int 
   const dim3 grid((unsigned)nblk, 256 / TPB);
   hipLaunchKernelGGL((k_trim_ptrs<N, NT>), grid, dim3(TPB), 0, s, img, L, K, V, t, scale, ds);
   return check_launch("k_trim_ptrs");
+}
+
+template <int N, bool NT>
+int launch_trim_bucket_dense(const uint32_t* x, int64_t ld, int64_t P, const BucketArgs& b, int t, float scale, int ds,
+                             uint32_t* y, hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)((P + TPB - 1) / TPB));
+  if (b.perm) hipLaunchKernelGGL((k_trim_bucket_dense<N, NT, true>), grid, dim3(TPB), 0, s, x, ld, P, b, t, scale, ds, y);
+  else hipLaunchKernelGGL((k_trim_bucket_dense<N, NT, false>), grid, dim3(TPB), 0, s, x, ld, P, b, t, scale, ds, y);
+  return check_launch("k_trim_bucket_dense");
+}
+
+template <int N, bool NT>
+int launch_trim_bucket_ptrs(const int64_t* img, int L, int64_t nblk, int V, const BucketArgs& b, int t, float scale,
+                            int ds, hipStream_t s) {
+  constexpr int TPB = TrimShape<N>::TPB;
+  const dim3 grid((unsigned)nblk, 256 / TPB);
+  if (b.perm) hipLaunchKernelGGL((k_trim_bucket_ptrs<N, NT, true>), grid, dim3(TPB), 0, s, img, L, V, b, t, scale, ds);
+  else hipLaunchKernelGGL((k_trim_bucket_ptrs<N, NT, false>), grid, dim3(TPB), 0, s, img, L, V, b, t, scale, ds);
+  return check_launch("k_trim_bucket_ptrs");
+}
+
+// K clients in buckets of s (checked): the counts and the two inverses, formed as the trimmed
+// mean's scale is (f32 of the double quotient). s > K is one bucket of K.
+BucketArgs bucket_args(const int32_t* perm_dev, int64_t K, int64_t s) {
+  if (s > K) s = K;
+  const int64_t B = (K + s - 1) / s, n_last = K - (B - 1) * s;
+  return BucketArgs{perm_dev, (int)K, (int)s, (int)B, (float)(1.0 / (double)s), (float)(1.0 / (double)n_last)};
 }
 
 template <int N, bool NT>
@@ -380,6 +479,40 @@ int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
   const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
   return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_trim_ptrs, true, image_dev, L, k, nblk, V, tt, scale, ds, s)
                                      : FJ_TRIM_WIDTH(launch_trim_ptrs, false, image_dev, L, k, nblk, V, tt, scale, ds, s);
+}
+
+int fjagg_trim_bucket_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const int32_t* perm_dev,
+                            int64_t s, int64_t t, float scale, void* out_dev, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = bucket_check(in_dtype, K, s, t, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL)) return rc;
+  if (P < 1 || ld < P) return fail(FJAGG_EINVAL, "need 1 <= P <= ld (P=%lld, ld=%lld)", (long long)P, (long long)ld);
+  if (P * 4 > kTrimMaxRowBytes) return fail(FJAGG_EUNSUPPORTED, "bucketed trimmed mean: rows <= 1 GiB");
+  if (!x_dev || !out_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(x_dev);
+  uint32_t* y = reinterpret_cast<uint32_t*>(out_dev);
+  const BucketArgs b = bucket_args(perm_dev, K, s);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, tt = (int)t;
+  K = b.B;  // the width's bound
+  return (flags & FJAGG_NONTEMPORAL) ? FJ_TRIM_WIDTH(launch_trim_bucket_dense, true, x, ld, P, b, tt, scale, ds, y, st)
+                                     : FJ_TRIM_WIDTH(launch_trim_bucket_dense, false, x, ld, P, b, tt, scale, ds, y, st);
+}
+
+int fjagg_trim_bucket_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                           const int32_t* perm_dev, int64_t s, int64_t t, float scale, int flags, void* stream) {
+  g_err[0] = 0;
+  if (int rc = bucket_check(in_dtype, K, s, t, flags, FJAGG_SCALE | FJAGG_NONTEMPORAL | FJAGG_UNALIGNED)) return rc;
+  if (nblk < 1 || nblk > 0x7fffffff || L < 1 || L >= (1 << 22))
+    return fail(FJAGG_EINVAL, "bad plan (nblk=%lld, L=%d)", (long long)nblk, L);
+  if (!image_dev) return fail(FJAGG_EINVAL, "null pointer argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const BucketArgs b = bucket_args(perm_dev, K, s);
+  const int ds = (flags & FJAGG_SCALE) ? 1 : 0, tt = (int)t;
+  const int V = (flags & FJAGG_UNALIGNED) ? 1 : 4;  // the plan's unit (fjagg_ptrs_plan_leaves)
+  K = b.B;  // the width's bound
+  return (flags & FJAGG_NONTEMPORAL)
+             ? FJ_TRIM_WIDTH(launch_trim_bucket_ptrs, true, image_dev, L, nblk, V, b, tt, scale, ds, st)
+             : FJ_TRIM_WIDTH(launch_trim_bucket_ptrs, false, image_dev, L, nblk, V, b, tt, scale, ds, st);
 }
 
 int fjagg_meamed_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P, const int32_t* rows_host,

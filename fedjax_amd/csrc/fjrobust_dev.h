@@ -291,6 +291,71 @@ FJR_HD uint32_t trim_column(Load load, int K, int t, bool do_scale, float scale,
   return kept_sum(load, K, L, U, t - below, cU - (t - above), do_scale, scale);
 }
 
+// A table entry as an index into [0, K): the project's rule for device tables, a stale entry can
+// give a wrong result but never an address outside the slab. K >= 1.
+FJR_HD int clamp_index(int32_t i, int K) { return i < 0 ? 0 : (i >= K ? K - 1 : (int)i); }
+
+// Bucketing (include/fjagg.h, fjagg_trim_bucket_*): a per-bucket load made from a per-client
+// one, so that trim_column and kept_sum run over bucket means with nothing else changed. Bucket
+// j holds the clients table(j*s + i), i = 0 .. n_j - 1, n_j = min(s, K - j*s); its value is the
+// first member verbatim, then a = fl(a + x) in table order, then fl(a * f32(1 / n_j)) unless
+// n_j == 1, and a NaN so computed becomes 0x7FC00000 (a bucket of one keeps its member's bits).
+// Only the last bucket can be short: inv_s is f32(1 / s), inv_last f32(1 / n_last).
+// load(k) as for trim_column; table(m) returns entry m of the client table for 0 <= m < K,
+// uniform over the wave, and is clamped here. The member loop is rolled (s is a run-time value)
+// in steps of 8 whose loads are issued together before the first is added: two groups of 4
+// without a branch inside (a position past the bucket's end loads the last member again and is
+// not added), the second group skipped when the bucket ends before it. The routine is inlined
+// at every load of the column routine, so its code has to stay this small.
+template <class Load, class Table>
+struct BucketLoad {
+  Load load;
+  Table table;
+  int K, s;
+  float inv_s, inv_last;
+  // members i0 .. i0+3 of the bucket at m0: the four table entries first (four scalar loads in
+  // flight on the device), then the four client loads
+  FJR_HD void members4(int m0, int n, int i0, uint32_t* v) const {
+    int r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = clamp_index(table(m0 + (i0 + i < n ? i0 + i : n - 1)), K);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = load(r[i]);
+  }
+  FJR_HD uint32_t operator()(int j) const {
+    const int m0 = j * s;
+    const int n = K - m0 < s ? K - m0 : s;
+    uint32_t first = 0;
+    float a = 0.f;
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += 8) {
+      uint32_t v[8];
+      members4(m0, n, i0, v);
+      if (i0 + 4 < n) {
+        members4(m0, n, i0 + 4, v + 4);
+      } else {
+#pragma unroll
+        for (int i = 4; i < 8; ++i) v[i] = 0u;
+      }
+      if (i0 == 0) first = v[0];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float x = as_float(v[i]);
+        a = i0 + i < n ? (i0 + i == 0 ? x : add_rn(a, x)) : a;
+      }
+    }
+    if (n == 1) return first;
+    // IEEE leaves the sign and payload of a NaN result open, and the sign decides which end of
+    // the order it is trimmed from: a computed NaN is the canonical +NaN on every machine
+    const uint32_t y = as_bits(mul_rn(a, n == s ? inv_s : inv_last));
+    return (y & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FC00000u : y;
+  }
+};
+template <class Load, class Table>
+FJR_HD BucketLoad<Load, Table> bucket_load(Load load, Table table, int K, int s, float inv_s, float inv_last) {
+  return BucketLoad<Load, Table>{load, table, K, s, inv_s, inv_last};
+}
+
 // Distance of a sorted key from the median's, as the bits of a non-negative float32 (which order
 // as the floats do): 0 for the median's own key, else |fl(v - med)| with a NaN (a NaN operand,
 // or inf - inf) replaced by +inf.

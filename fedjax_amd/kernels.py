@@ -779,6 +779,158 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 
+BUCKET_MAX_CLIENTS = 4096  # fjagg_trim_bucket_*: clients behind at most TRIM_MAX_CLIENTS buckets (fjagg.h)
+
+
+def bucket_count(K: int, s) -> int:
+    """The number of buckets ``B = ceil(K / s)`` of ``K`` clients in buckets of ``s``, checked:
+    ``TypeError`` for a bool or a non-int ``s``, ``ValueError`` for ``s < 1``, ``K < 1``, more than
+    4096 clients or more than 128 buckets. Nothing here touches the library."""
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)):
+        raise TypeError(f"bucket_size must be an int >= 1, not {type(s).__name__}")
+    K, s = int(K), int(s)
+    if s < 1:
+        raise ValueError(f"bucket_size must be >= 1, got {s}")
+    if K < 1:
+        raise ValueError(f"bucketing needs at least 1 client, got K = {K}")
+    if K > BUCKET_MAX_CLIENTS:
+        raise ValueError(f"bucketing supports K <= {BUCKET_MAX_CLIENTS} clients, got K = {K}")
+    B = -(-K // s)
+    if B > TRIM_MAX_CLIENTS:
+        raise ValueError(f"bucketing supports B = ceil(K / bucket_size) <= {TRIM_MAX_CLIENTS} buckets, got B = {B} "
+                         f"(K = {K}, bucket_size = {s})")
+    return B
+
+
+def bucket_trim_count(trim, B: int) -> int:
+    """:func:`trim_count` over ``B`` buckets: ``trim`` counts buckets, a fraction gives
+    ``floor(beta * B)``. The same refusals, worded for buckets."""
+    if isinstance(trim, (bool, np.bool_)):
+        raise TypeError("trim must be an int count or a float fraction in [0, 0.5), not a bool")
+    if isinstance(trim, (int, np.integer)):
+        t = int(trim)
+    elif isinstance(trim, (float, np.floating)):
+        beta = float(trim)
+        if not (0.0 <= beta < 0.5):
+            raise ValueError(f"a trim fraction must be in [0, 0.5), got {trim}")
+        t = int(math.floor(beta * B))
+    else:
+        raise TypeError(f"trim must be an int count or a float fraction in [0, 0.5), not {type(trim).__name__}")
+    if t < 0 or 2 * t >= B:
+        raise ValueError(f"a trim count needs 0 <= 2t < B: t = {t} leaves no bucket of B = {B}")
+    return t
+
+
+def bucket_sizes(K: int, s: int) -> np.ndarray:
+    """int64 [B]: the member count of every bucket (only the last may be short)."""
+    B = bucket_count(K, s)
+    s = min(int(s), int(K))
+    n = np.full(B, s, np.int64)
+    n[-1] = K - (B - 1) * s
+    return n
+
+
+def check_bucket_perm(perm, K: int, *, host_only: bool = False):
+    """The client table of a bucketed aggregate, checked without touching the library: ``None``
+    (the identity), an int32 device tensor of ``K`` entries (returned as it is and never read
+    here: the kernel clamps its entries), or a host int sequence or array, which must be a
+    permutation of ``range(K)`` and is returned as an int32 array. ``host_only`` refuses the
+    device tensor (the Gram-matrix rules select on the host)."""
+    if perm is None:
+        return None
+    if isinstance(perm, torch.Tensor) and perm.is_cuda:
+        if host_only:
+            raise TypeError("the bucketed selection runs on the host: perm must be a host sequence or None")
+        if perm.dtype != torch.int32 or perm.dim() != 1 or perm.numel() != K or not perm.is_contiguous():
+            raise ValueError(f"a device perm must be a contiguous int32 tensor of K = {K} entries")
+        return perm
+    a = perm.numpy() if isinstance(perm, torch.Tensor) else np.asarray(perm)
+    if a.dtype == np.bool_ or a.dtype.kind not in "iu":
+        raise TypeError(f"perm must hold ints, got dtype {a.dtype}")
+    if a.ndim != 1 or a.size != K:
+        raise ValueError(f"perm must be a permutation of range({K}), got shape {a.shape}")
+    a = a.astype(np.int64)
+    if not np.array_equal(np.sort(a), np.arange(K)):
+        raise ValueError(f"perm must be a permutation of range({K})")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def bucket_perm_device(perm, device: torch.device) -> Optional[torch.Tensor]:
+    """:func:`check_bucket_perm`'s result on ``device``: a host table is uploaded (which a stream
+    capture refuses), a device tensor must already live there."""
+    if perm is None:
+        return None
+    if isinstance(perm, np.ndarray):
+        return _lib.upload(torch.from_numpy(perm), device)
+    if perm.device != device:
+        raise ValueError(f"perm lives on {perm.device}, the deltas on {device}")
+    return perm
+
+
+def _check_bucket_launch(K: int, s, t, perm) -> Tuple[int, int, int]:
+    B = bucket_count(K, s)
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+        raise TypeError("t must be an int trim count")
+    t = bucket_trim_count(int(t), B)
+    if perm is not None and (not isinstance(perm, torch.Tensor) or not perm.is_cuda or perm.dtype != torch.int32
+                             or perm.dim() != 1 or perm.numel() != K or not perm.is_contiguous()):
+        raise ValueError(f"perm must be None or a contiguous int32 device tensor of K = {K} entries")
+    return B, int(s), t
+
+
+def trim_bucket_dense(x: torch.Tensor, s: int, t: int, *, perm: Optional[torch.Tensor] = None,
+                      scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                      nontemporal: bool = False) -> torch.Tensor:
+    """:func:`trim_dense` over the means of buckets of ``s`` clients (fjagg.h,
+    ``fjagg_trim_bucket_dense``): bucket ``j`` holds the rows ``perm[j*s] .. perm[j*s + n_j - 1]``
+    (``perm``: an int32 device tensor of ``K`` entries, never read by the host; ``None``: the
+    identity), its mean is formed in float32 in table order, and ``t`` trims buckets. ``K <=
+    4096``, ``B = ceil(K / s) <= 128``, ``0 <= 2t < B``; the trimmed mean passes ``scale =
+    f32(1 / (B - 2t))``. One launch, nothing uploaded; everything is checked before the library
+    is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the trimmed mean takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    _, s, t = _check_bucket_launch(K, s, t, perm)
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the trimmed mean takes rows of up to 1 GiB")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.dim() != 1 or out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, out) if perm is None else _require_device(x, out, perm)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_trim_bucket_dense", _lib.F32, x.data_ptr(), ld, K, P, None if perm is None else perm.data_ptr(),
+              s, t, float(scale if scale is not None else 1.0), out.data_ptr(), flags, _stream_handle(dev))
+    return out
+
+
+def trim_bucket_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, s: int, t: int, scale: Optional[float], *,
+                     perm: Optional[torch.Tensor] = None, unaligned: bool = False,
+                     nontemporal: bool = False) -> None:
+    """Launch ``fjagg_trim_bucket_ptrs`` over a device plan image holding all ``K`` clients (as
+    :func:`trim_ptrs` takes it): :func:`trim_bucket_dense`'s arithmetic on every leaf in one
+    launch. Checked before the library is touched."""
+    K = int(K)
+    _, s, t = _check_bucket_launch(K, s, t, perm)
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    dev = _require_device(image_dev) if perm is None else _require_device(image_dev, perm)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    flags |= _lib.UNALIGNED if unaligned else 0
+    _lib.call("fjagg_trim_bucket_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk,
+              None if perm is None else perm.data_ptr(), s, t, float(scale if scale is not None else 1.0), flags,
+              _stream_handle(dev))
+
+
 MEAMED_MAX_SLAB_ROWS = 1024  # fjagg_meamed_dense: the slab a row table selects from (the Gram pass's limit)
 
 

@@ -169,5 +169,19 @@ def rademacher(key, shape: Shape = (), device=None) -> torch.Tensor:
     return torch.where(u < 0.5, 1, -1).to(torch.int32)
 
 
-__all__ = ["PRNGKey", "PRNGSequence", "normal", "normal_from_bits", "rademacher", "random_bits", "split", "split_many",
-           "strict_key", "uniform"]
+def permutation(key, n: int, device=None) -> torch.Tensor:
+    """A permutation of ``range(n)`` as an int32 device tensor: the stable argsort (ties to the
+    lower index) of the ``n`` words ``random_bits(key, (n,))`` compared as unsigned 32-bit
+    integers. This is this project's own rule, fixed here so that a shuffle can be reproduced from
+    its key; it is NOT ``jax.random.permutation``'s bits. The draw and the sort both run on the
+    device, in stream order, with no host step: the table a bucketed aggregate takes as ``perm``."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"n must be an int >= 1, not {type(n).__name__}")
+    if n < 1:
+        raise ValueError(f"a permutation needs n >= 1, got {n}")
+    words = random_bits(key, (int(n),), device).to(torch.int64) & 0xFFFFFFFF
+    return torch.sort(words, stable=True).indices.to(torch.int32)
+
+
+__all__ = ["PRNGKey", "PRNGSequence", "normal", "normal_from_bits", "permutation", "rademacher", "random_bits", "split",
+           "split_many", "strict_key", "uniform"]

@@ -26,7 +26,7 @@ from typing import Tuple
 import numpy as np
 
 __all__ = ["usable", "sq_distances", "krum_scores", "krum_select", "check_krum_args", "bulyan_select",
-           "weiszfeld_weights"]
+           "weiszfeld_weights", "bucket_gram", "bucket_members"]
 
 
 def _gram(G) -> np.ndarray:
@@ -168,6 +168,70 @@ def bulyan_select(G, f) -> np.ndarray:
         selected.append(int(rows[best]))
         alive[rows[best]] = False
     return np.array(selected, dtype=np.int64)
+
+
+def _bucket_table(K: int, bucket_size, perm) -> Tuple[int, int, np.ndarray]:
+    """(s, B, table) of ``K`` clients in buckets of ``bucket_size`` by ``perm`` (None: the identity),
+    checked: an int ``bucket_size >= 1`` (a bool is refused; above ``K`` it is ``K``) and a
+    permutation of ``range(K)``."""
+    s = _int("bucket_size", bucket_size)
+    if s < 1:
+        raise ValueError(f"bucket_size must be >= 1, got {s}")
+    s = min(s, K)
+    if perm is None:
+        table = np.arange(K, dtype=np.int64)
+    else:
+        table = np.asarray(perm)
+        if table.dtype == np.bool_ or table.dtype.kind not in "iu":
+            raise TypeError(f"perm must hold ints, got dtype {table.dtype}")
+        table = table.astype(np.int64)
+        if table.ndim != 1 or table.size != K or not np.array_equal(np.sort(table), np.arange(K)):
+            raise ValueError(f"perm must be a permutation of range({K})")
+    return s, -(-K // s), table
+
+
+def bucket_members(K: int, bucket_size, perm=None) -> list:
+    """The member clients of every bucket, in table order: ``B`` int64 arrays, bucket ``j`` holding
+    ``perm[j*s : min((j+1)*s, K)]``. Only the last can be short. ``np.concatenate`` of the entries
+    a bucketed Krum selected gives the clients whose deltas were averaged."""
+    s, B, table = _bucket_table(int(K), bucket_size, perm)
+    return [table[j * s:min((j + 1) * s, K)] for j in range(B)]
+
+
+def bucket_gram(G, bucket_size, perm=None) -> np.ndarray:
+    """float64 [B, B] Gram matrix of the bucket means of bucketing (Karimireddy, He and Jaggi, ICLR
+    2022) from the clients' ``G`` alone, with no pass over the deltas: with bucket ``a`` holding
+    the ``n_a`` clients ``perm[a*s + i]`` (:func:`bucket_members`),
+
+        Gb[a][b] = (sum_{i in a} sum_{j in b} G[i][j]) / (n_a * n_b)
+
+    The ``n_a * n_b`` terms are added sequentially as ONE chain in table order, rows first: the
+    first term verbatim, then for each member ``i`` of ``a`` in turn every member ``j`` of ``b``;
+    then one division by the float64 ``n_a * n_b``. ``bucket_size = 1`` with the identity table
+    returns ``G`` bit for bit. A client holding a NaN or inf has a non-finite row and column in
+    ``G`` and makes exactly its bucket's row and column of ``Gb`` non-finite; any client with a
+    non-finite ``G[k][k]`` makes its bucket's diagonal entry non-finite, so the bucket is unusable
+    (:func:`usable`) and is never selected."""
+    G = _gram(G)
+    K = G.shape[0]
+    s, B, table = _bucket_table(K, bucket_size, perm)
+    Gp = G[np.ix_(table, table)]
+    full, n_last = (K // s, 0) if K % s == 0 else (K // s, K % s)
+    out = np.empty((B, B), dtype=np.float64)
+
+    def block(r0, cnt_r, nr, c0, cnt_c, nc):  # cnt_r x cnt_c buckets of nr x nc clients: each one chain
+        blk = Gp[r0:r0 + cnt_r * nr, c0:c0 + cnt_c * nc].reshape(cnt_r, nr, cnt_c, nc)
+        chain = np.ascontiguousarray(blk.transpose(0, 2, 1, 3)).reshape(cnt_r, cnt_c, nr * nc)
+        return np.cumsum(chain, axis=-1)[..., -1] / float(nr * nc)  # cumsum adds strictly left to right
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        out[:full, :full] = block(0, full, s, 0, full, s)
+        if n_last:
+            e = full * s
+            out[:full, full:] = block(0, full, s, e, 1, n_last)
+            out[full:, :full] = block(e, 1, n_last, 0, full, s)
+            out[full:, full:] = block(e, 1, n_last, e, 1, n_last)
+    return out
 
 
 def weiszfeld_weights(G, alpha=None, nu: float = 1e-6, iterations: int = 4) -> Tuple[np.ndarray, np.ndarray]:

@@ -290,7 +290,8 @@ class ClientDeltaSlab:
                                       nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return [self.unflatten(out[g]) if alive[g] else None for g in range(G)]
 
-    def trimmed_mean(self, trim, *, out: Optional[torch.Tensor] = None) -> PyTree:
+    def trimmed_mean(self, trim, *, bucket_size: Optional[int] = None, perm=None,
+                     out: Optional[torch.Tensor] = None) -> PyTree:
         """Coordinate-wise trimmed mean of the K rows (Yin et al., ICML 2018): in every coordinate
         the ``t`` smallest and the ``t`` largest client values are dropped and the rest averaged,
         so up to ``t`` clients that upload ``inf``, ``NaN`` or huge values in a coordinate do not
@@ -303,29 +304,66 @@ class ClientDeltaSlab:
         :meth:`mean` adds and multiplied by f32(1 / (K - 2t)), so ``trim=0`` is bit for bit
         ``mean([1] * K)``. There are no weights: a robust aggregate that let a client scale its
         own vote would not be robust. A float32 slab of up to 128 clients. Returns the
-        template's pytree (views into ``out`` if given: float32, ``num_params`` elements)."""
+        template's pytree (views into ``out`` if given: float32, ``num_params`` elements).
+
+        ``bucket_size=s`` is bucketing (Karimireddy, He and Jaggi, ICLR 2022): the
+        clients are averaged in ``B = ceil(K / s)`` buckets of ``s`` and the rule runs over the
+        bucket means, which helps on heterogeneous clients and lifts the limit to 4096 clients
+        (``B <= 128``). Bucket ``j`` holds the clients ``perm[j*s + i]``; its mean is the first
+        member verbatim, the others added in table order, times f32(1 / n_j) — a short last
+        bucket is divided by its own size. ``trim`` then counts BUCKETS (a fraction gives
+        ``floor(beta * B)``), ties go by bucket index and the scale is f32(1 / (B - 2t)); ``f``
+        bad clients can spoil ``f`` buckets out of ``B``, so the tolerable fraction of bad
+        clients shrinks by ``s``. ``perm`` is ``None`` (consecutive clients, unshuffled), a host
+        int sequence (checked to be a permutation of ``range(K)`` and uploaded, which a stream
+        capture refuses), or an int32 device tensor of ``K`` entries such as
+        :func:`fedjax_amd.random.permutation` returns (used as it is, never read by the host:
+        nothing is uploaded, the call can be captured and each replay reads the table afresh;
+        the kernel clamps its entries into ``[0, K)``). Still one launch and no temporary; the
+        bucket means are formed inside the column kernel, which reads every delta twice.
+        ``bucket_size=1`` without ``perm`` is bit for bit the unbucketed result. ``perm`` without
+        ``bucket_size`` is a ``ValueError``."""
         if self.dtype != torch.float32:
             raise TypeError(f"trimmed_mean needs a float32 slab, not {self.dtype}")
         K = self.num_clients
-        t = kernels.trim_count(trim, K)
+        if bucket_size is None:
+            if perm is not None:
+                raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+            t = kernels.trim_count(trim, K)
+        else:
+            B = kernels.bucket_count(K, bucket_size)
+            t = kernels.bucket_trim_count(trim, B)
+            perm = kernels.check_bucket_perm(perm, K)
         if self.num_params == 0:  # a template of empty leaves: nothing to launch
             flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
             return self.unflatten(flat)
         rows = self.rows
         nbytes = rows.numel() * rows.element_size()
-        flat = kernels.trim_dense(rows, t, scale=float(np.float32(tree_util._inverse(K - 2 * t))), out=out,
-                                  nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        if bucket_size is None:
+            flat = kernels.trim_dense(rows, t, scale=float(np.float32(tree_util._inverse(K - 2 * t))), out=out,
+                                      nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+        else:
+            flat = kernels.trim_bucket_dense(rows, int(bucket_size), t, perm=kernels.bucket_perm_device(perm, self.device),
+                                             scale=float(np.float32(tree_util._inverse(B - 2 * t))), out=out,
+                                             nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return self.unflatten(flat)
 
-    def median(self, *, out: Optional[torch.Tensor] = None) -> PyTree:
+    def median(self, *, bucket_size: Optional[int] = None, perm=None, out: Optional[torch.Tensor] = None) -> PyTree:
         """Coordinate-wise median of the K rows: :meth:`trimmed_mean` at ``t = (K-1) // 2``. Odd
         K gives the middle value verbatim, even K ``fl(fl(a + b) * 0.5)`` of the two middle
         values (a before b in client order); ``np.median``'s bits on finite data. Weights play
-        no part. A float32 slab of up to 128 clients."""
+        no part. A float32 slab of up to 128 clients. With ``bucket_size`` (and ``perm``) as
+        :meth:`trimmed_mean` takes them: the median of the ``B`` bucket means, ``t = (B-1) // 2``,
+        for up to 4096 clients."""
         if self.dtype != torch.float32:
             raise TypeError(f"median needs a float32 slab, not {self.dtype}")
-        kernels.trim_count(0, self.num_clients)
-        return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
+        if bucket_size is None:
+            if perm is not None:
+                raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+            kernels.trim_count(0, self.num_clients)
+            return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
+        B = kernels.bucket_count(self.num_clients, bucket_size)
+        return self.trimmed_mean((B - 1) // 2, bucket_size=bucket_size, perm=perm, out=out)
 
     def mean_around_median(self, keep, *, rows: Optional[Sequence[int]] = None,
                            out: Optional[torch.Tensor] = None) -> PyTree:
@@ -436,7 +474,8 @@ class ClientDeltaSlab:
                                              nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return self.unflatten(out)
 
-    def krum(self, num_byzantine, num_selected=1, *, select: str = "host"):
+    def krum(self, num_byzantine, num_selected=1, *, select: str = "host", bucket_size: Optional[int] = None,
+             perm=None):
         """Krum (``num_selected = 1``) and multi-Krum (Blanchard et al., NeurIPS 2017) over the
         rows: client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
         other clients, ``f = num_byzantine``, and the ``num_selected`` clients of smallest
@@ -456,7 +495,37 @@ class ClientDeltaSlab:
         uploaded: the round can be captured into a graph and replayed over rewritten deltas, and
         each replay selects afresh. The argument checks and their exceptions are the same.
         Returns a :class:`~fedjax_amd.tree_util.DeviceKrumResult` of device tensors; ``mean`` is
-        all +0 when no client has a finite score (never ``None``)."""
+        all +0 when no client has a finite score (never ``None``).
+
+        ``bucket_size=s`` is bucketing (Karimireddy, He and Jaggi, ICLR 2022): Krum
+        over the means of ``B = ceil(K / s)`` buckets of the rows ``perm[j*s + i]`` (``perm``: a
+        host int sequence, a permutation of ``range(K)``, or ``None`` for consecutive rows). No
+        third pass: the bucket means' Gram is :func:`fedjax_amd.robust.bucket_gram` of
+        :meth:`gram`, the argument checks run on ``B`` and ``f`` counts buckets. The mean is
+        ``grouped_mean(w, ids, 1)[0]`` with id 0 for the members of the selected buckets, -1 for
+        everyone else, and integer weights that make it the mean of the selected bucket means
+        (all 1 unless the short last bucket is selected beside full ones). Returns a
+        :class:`~fedjax_amd.tree_util.BucketedKrumResult`: ``selected`` and ``scores`` are per
+        bucket, ``members`` names the clients. Host selection only: ``select="device"`` with
+        ``bucket_size`` is a ``ValueError`` before any pass over the deltas."""
+        if bucket_size is None and perm is not None:
+            raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+        if bucket_size is not None:
+            from fedjax_amd import robust
+
+            kernels.check_select(select)
+            if select != "host":
+                raise ValueError('the bucketed selection is host-only: bucket_size needs select="host"')
+            kernels.refuse_capture("krum", kernels._TWO_PASS)
+            if self.dtype != torch.float32:
+                raise TypeError(f"krum needs a float32 slab, not {self.dtype}")
+            B, perm = tree_util._bucket_args(self.num_clients, bucket_size, perm)
+            robust.check_krum_args(B, num_byzantine, num_selected)
+            gram = self.gram()
+            selected, scores, w, ids, members = tree_util._bucket_krum_plan(gram.cpu().numpy(), bucket_size, perm,
+                                                                            num_byzantine, num_selected)
+            mean = self.grouped_mean(w, ids, 1)[0] if len(selected) else None
+            return tree_util.BucketedKrumResult(mean, selected, scores, gram, members)
         if kernels.check_select(select):
             if self.dtype != torch.float32:
                 raise TypeError(f"krum needs a float32 slab, not {self.dtype}")
@@ -474,7 +543,7 @@ class ClientDeltaSlab:
         return tree_util.KrumResult(mean, selected, scores, gram)
 
     def geometric_median(self, weights: Optional[Sequence] = None, *, iterations=4,
-                         nu=1e-6, select: str = "host"):
+                         nu=1e-6, select: str = "host", bucket_size: Optional[int] = None, perm=None):
         """The geometric median of the rows by the smoothed Weiszfeld algorithm ("RFA", Pillutla
         et al., IEEE TSP 2022), ``weights`` the clients' positive weights alpha (default all 1).
         All ``iterations`` run on the host over the Gram matrix
@@ -493,7 +562,32 @@ class ClientDeltaSlab:
         copy and no synchronisation; ``weights`` are uploaded once (which a capture refuses),
         ``None`` uploads nothing and can be captured. The argument checks and their exceptions
         are the same. Returns a :class:`~fedjax_amd.tree_util.DeviceGeometricMedianResult`;
-        ``median`` is all +0 when no client is usable (never ``None``)."""
+        ``median`` is all +0 when no client is usable (never ``None``).
+
+        ``bucket_size=s`` is bucketing (as :meth:`krum` takes it, with ``perm``): the geometric
+        median of the ``B`` bucket means. ``weiszfeld_weights`` over the bucket Gram gives ``a_b``
+        and every member of bucket ``b`` folds with ``f32(a_b / n_b)``; in the result ``weights``
+        are those per-CLIENT fold weights and ``distances`` are per BUCKET. Client ``weights``
+        together with ``bucket_size``, and ``select="device"`` with ``bucket_size``, are
+        ``ValueError`` before any pass over the deltas."""
+        if bucket_size is None and perm is not None:
+            raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+        if bucket_size is not None:
+            kernels.check_select(select)
+            if select != "host":
+                raise ValueError('the bucketed selection is host-only: bucket_size needs select="host"')
+            if weights is not None:
+                raise ValueError("client weights and bucket_size cannot be combined: a bucket mean has no client "
+                                 "weights")
+            kernels.refuse_capture("geometric_median", kernels._TWO_PASS)
+            if self.dtype != torch.float32:
+                raise TypeError(f"geometric_median needs a float32 slab, not {self.dtype}")
+            _, perm = tree_util._bucket_args(self.num_clients, bucket_size, perm)
+            tree_util._check_median_iterations(iterations, nu)
+            gram = self.gram()
+            w32, d, ids = tree_util._bucket_median_plan(gram.cpu().numpy(), bucket_size, perm, iterations, nu)
+            median = self.grouped_mean(w32, ids, 1)[0] if (ids >= 0).any() else None
+            return tree_util.GeometricMedianResult(median, w32, d, gram)
         if kernels.check_select(select):
             if self.dtype != torch.float32:
                 raise TypeError(f"geometric_median needs a float32 slab, not {self.dtype}")

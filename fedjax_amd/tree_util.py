@@ -46,7 +46,7 @@ __all__ = [
     "set_lazy_norms", "set_bf16_semantics", "bf16_semantics", "tree_clipped_mean", "ClippedMean",
     "tree_dp_clipped_mean",
     "tree_grouped_mean", "tree_trimmed_mean", "tree_median",
-    "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult",
+    "tree_gram", "tree_krum", "tree_geometric_median", "KrumResult", "GeometricMedianResult", "BucketedKrumResult",
     "DeviceKrumResult", "DeviceGeometricMedianResult",
     "tree_mean_around_median", "tree_bulyan", "BulyanResult", "DeviceBulyanResult",
     "tree_centered_clip", "CenteredClip",
@@ -2005,7 +2005,8 @@ def tree_grouped_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], group
     return result
 
 
-def tree_trimmed_mean(pytrees: Iterable[PyTree], trim) -> Optional[PyTree]:
+def tree_trimmed_mean(pytrees: Iterable[PyTree], trim, *, bucket_size: Optional[int] = None,
+                      perm=None) -> Optional[PyTree]:
     """Coordinate-wise trimmed mean of client pytrees (Yin et al., ICML 2018): in every coordinate
     of every leaf the ``t`` smallest and ``t`` largest client values are dropped and the rest
     averaged — up to ``t`` clients that send ``inf``, ``NaN`` or huge values in a coordinate do not
@@ -2020,11 +2021,27 @@ def tree_trimmed_mean(pytrees: Iterable[PyTree], trim) -> Optional[PyTree]:
     plan image is uploaded and ONE launch covers every leaf, reading each delta once, with
     float32 alignment as the only requirement on a leaf. Float32 leaves, ``K <= 128``. The
     inputs are never written; a one-shot iterable is consumed once; no clients: ``None``.
-    Raises under stream capture (the plan image goes through a pinned staging buffer)."""
+    Raises under stream capture (the plan image goes through a pinned staging buffer).
+
+    ``bucket_size=s`` is bucketing (Karimireddy, He and Jaggi, ICLR 2022), with
+    ``perm`` as :meth:`fedjax_amd.slab.ClientDeltaSlab.trimmed_mean` takes both and bit for bit
+    its result over the same deltas: the rule runs over the means of ``B = ceil(K / s)`` buckets
+    of ``s`` clients, ``trim`` counts buckets, ``K <= 4096`` and ``B <= 128``. Still one launch.
+    ``perm`` without ``bucket_size`` is a ``ValueError``."""
     trees = pytrees if type(pytrees) is list else list(pytrees)
+    if bucket_size is None and perm is not None:
+        raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
     if not trees:
         return None
     K = len(trees)
+    if bucket_size is not None:
+        B = kernels.bucket_count(K, bucket_size)
+        t = kernels.bucket_trim_count(trim, B)
+        table = kernels.check_bucket_perm(perm, K)
+        scale = float(np.float32(_inverse(B - 2 * t)))
+        return _tree_columns(trees, "tree_trimmed_mean", lambda image_dev, L, nblk, nt: kernels.trim_bucket_ptrs(
+            image_dev, L, K, nblk, int(bucket_size), t, scale, perm=kernels.bucket_perm_device(table, image_dev.device),
+            nontemporal=nt))
     t = kernels.trim_count(trim, K)
     scale = float(np.float32(_inverse(K - 2 * t)))
     return _tree_columns(trees, "tree_trimmed_mean",
@@ -2121,13 +2138,20 @@ def tree_topk_mean(pytrees_and_weights: Iterable[Tuple[PyTree, float]], k) -> To
     return TopKMean(result, thr, sent)
 
 
-def tree_median(pytrees: Iterable[PyTree]) -> Optional[PyTree]:
+def tree_median(pytrees: Iterable[PyTree], *, bucket_size: Optional[int] = None, perm=None) -> Optional[PyTree]:
     """Coordinate-wise median of client pytrees: :func:`tree_trimmed_mean` at ``t = (K-1) // 2``.
     Odd K: the middle value verbatim; even K: ``fl(fl(a + b) * 0.5)`` of the two middle values —
-    ``np.median``'s bits on finite data. Float32 leaves, ``K <= 128``; no clients: ``None``."""
+    ``np.median``'s bits on finite data. Float32 leaves, ``K <= 128``; no clients: ``None``.
+    With ``bucket_size`` (and ``perm``) as :func:`tree_trimmed_mean` takes them: the median of the
+    ``B`` bucket means, ``t = (B-1) // 2``, for up to 4096 clients."""
     trees = pytrees if type(pytrees) is list else list(pytrees)
+    if bucket_size is None and perm is not None:
+        raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
     if not trees:
         return None
+    if bucket_size is not None:
+        B = kernels.bucket_count(len(trees), bucket_size)
+        return tree_trimmed_mean(trees, (B - 1) // 2, bucket_size=bucket_size, perm=perm)
     kernels.trim_count(0, len(trees))
     return tree_trimmed_mean(trees, (len(trees) - 1) // 2)
 
@@ -2527,6 +2551,77 @@ def _median_plan(G: np.ndarray, weights, iterations, nu):
     return a32, d, ids
 
 
+class BucketedKrumResult(NamedTuple):
+    """Result of Krum / multi-Krum over bucket means (``bucket_size`` given): ``mean`` — the mean of
+    the selected buckets' means (``None`` when no bucket could be selected); ``selected`` — the
+    selected BUCKETS' indices, best first (int64 numpy); ``scores`` — every bucket's Krum score
+    (float64 numpy [B], ``inf`` for a bucket with an unusable member); ``gram`` — the clients'
+    float64 ``[K, K]`` Gram matrix on the device; ``members`` — the member clients of the selected
+    buckets, one int64 array per entry of ``selected`` in table order
+    (:func:`fedjax_amd.robust.bucket_members`): ``np.concatenate(members)`` are the clients whose
+    deltas were loaded."""
+    mean: Any
+    selected: Any
+    scores: Any
+    gram: Any
+    members: Any
+
+
+def _bucket_args(K: int, bucket_size, perm):
+    """The checks of a bucketed Gram-matrix rule, before any pass over the deltas; returns ``B`` and
+    the table as a numpy array (``None``: the identity)."""
+    from fedjax_amd import robust
+
+    if isinstance(perm, torch.Tensor) and perm.is_cuda:
+        raise TypeError("the bucketed selection runs on the host: perm must be a host sequence or None")
+    kernels._check_gram_clients(K)
+    perm = None if perm is None else np.asarray(perm.numpy() if isinstance(perm, torch.Tensor) else perm)
+    return robust._bucket_table(K, bucket_size, perm)[1], perm
+
+
+def _bucket_krum_plan(G: np.ndarray, bucket_size, perm, num_byzantine, num_selected):
+    """(selected buckets, bucket scores, fold weights, fold ids, members) of a bucketed Krum round.
+    The weights are exact integers that make the grouped fold the mean of the selected bucket
+    means: all 1 when the selected buckets have one size, else the short bucket's size for the
+    members of full buckets and the full size for the short bucket's."""
+    from fedjax_amd import robust
+
+    K = G.shape[0]
+    Gb = robust.bucket_gram(G, bucket_size, perm)
+    scores = robust.krum_scores(Gb, num_byzantine)
+    selected = robust.krum_select(Gb, num_byzantine, num_selected)
+    buckets = robust.bucket_members(K, bucket_size, perm)
+    members = [buckets[j] for j in selected]
+    ids = np.full(K, -1, dtype=np.int64)
+    w = [1] * K
+    sizes = {len(m) for m in members}
+    for m in members:
+        ids[m] = 0
+        if len(sizes) > 1:
+            for k in m:
+                w[int(k)] = min(sizes) if len(m) == max(sizes) else max(sizes)
+    return selected, scores, w, ids, members
+
+
+def _bucket_median_plan(G: np.ndarray, bucket_size, perm, iterations, nu):
+    """(float32 fold weights per client, bucket distances, fold ids) of a bucketed geometric-median
+    round: ``weiszfeld_weights`` over the bucket Gram gives ``a_b``; a member's fold weight is
+    ``f32(a_b / n_b)``."""
+    from fedjax_amd import robust
+
+    K = G.shape[0]
+    Gb = robust.bucket_gram(G, bucket_size, perm)
+    a, d = robust.weiszfeld_weights(Gb, None, nu, iterations)
+    ok = robust.usable(Gb)
+    w32 = np.zeros(K, dtype=np.float32)
+    ids = np.full(K, -1, dtype=np.int64)
+    for j, m in enumerate(robust.bucket_members(K, bucket_size, perm)):
+        w32[m] = np.float32(a[j] / len(m))
+        if ok[j] and w32[m[0]] > 0:
+            ids[m] = 0
+    return w32, d, ids
+
+
 def _check_krum_args(K: int, num_byzantine, num_selected) -> None:
     """Krum's argument checks on K alone, before any pass over the deltas."""
     from fedjax_amd import robust
@@ -2645,7 +2740,8 @@ def _tree_fold_selected(trees: list, M_max: int, select, fold=None):
     return gram, result, got
 
 
-def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1, *, select: str = "host"):
+def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1, *, select: str = "host",
+              bucket_size: Optional[int] = None, perm=None):
     """Krum (``num_selected = 1``) and multi-Krum over client pytrees (Blanchard et al., NeurIPS
     2017): client i's score is the sum of its ``K - f - 2`` smallest squared distances to the
     other clients, ``f = num_byzantine``; the ``num_selected`` clients of smallest score are
@@ -2664,7 +2760,39 @@ def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1, *, selec
     member tables the kernel wrote — no device-to-host copy, no synchronisation. The argument
     checks and their exceptions are the same. Returns a :class:`DeviceKrumResult` whose ``mean``
     is all +0 when no client could be selected (never ``None``); still raises under stream
-    capture, because the plan image goes through a pinned staging buffer."""
+    capture, because the plan image goes through a pinned staging buffer.
+
+    ``bucket_size=s`` is bucketing (Karimireddy, He and Jaggi, ICLR 2022): Krum over
+    the means of ``B = ceil(K / s)`` buckets of the clients ``perm[j*s + i]`` (``perm``: a host int
+    sequence, a permutation of ``range(K)``, or ``None`` for consecutive clients). No third pass:
+    the bucket means' Gram matrix is :func:`fedjax_amd.robust.bucket_gram` of the clients' and the
+    argument checks run on ``B`` (``B >= 2f + 3``, ``num_selected <= B - f``; ``f`` counts
+    buckets). The result is ``tree_grouped_mean`` with id 0 for the members of the selected
+    buckets and -1 for everyone else, with integer weights that make it the mean of the selected
+    bucket means (all 1 unless the short last bucket is selected beside full ones). Returns a
+    :class:`BucketedKrumResult`, whose ``selected`` and ``scores`` are per bucket and whose
+    ``members`` names the clients. Host selection only: ``select="device"`` with ``bucket_size``
+    is a ``ValueError`` before any pass over the deltas, and so is ``perm`` without
+    ``bucket_size``."""
+    if bucket_size is None and perm is not None:
+        raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+    if bucket_size is not None:
+        from fedjax_amd import robust
+
+        kernels.check_select(select)
+        if select != "host":
+            raise ValueError('the bucketed selection is host-only: bucket_size needs select="host"')
+        kernels.refuse_capture("tree_krum", kernels._TWO_PASS)
+        trees = pytrees if type(pytrees) is list else list(pytrees)
+        if not trees:
+            return None
+        B, perm = _bucket_args(len(trees), bucket_size, perm)
+        robust.check_krum_args(B, num_byzantine, num_selected)
+        gram = _tree_gram(trees)[0]
+        selected, scores, w, ids, members = _bucket_krum_plan(gram.cpu().numpy(), bucket_size, perm, num_byzantine,
+                                                              num_selected)
+        mean = tree_grouped_mean(list(zip(trees, w)), ids, 1)[0] if len(selected) else None
+        return BucketedKrumResult(mean, selected, scores, gram, members)
     if kernels.check_select(select):
         trees = pytrees if type(pytrees) is list else list(pytrees)
         if not trees:
@@ -2685,7 +2813,7 @@ def tree_krum(pytrees: Iterable[PyTree], num_byzantine, num_selected=1, *, selec
 
 
 def tree_geometric_median(pytrees: Iterable[PyTree], weights=None, *, iterations=4,
-                          nu=1e-6, select: str = "host"):
+                          nu=1e-6, select: str = "host", bucket_size: Optional[int] = None, perm=None):
     """The geometric median of client pytrees by the smoothed Weiszfeld algorithm ("RFA",
     Pillutla et al., IEEE TSP 2022): from ``a = alpha / sum(alpha)`` (``weights``, default all 1),
     ``iterations`` times ``beta_k = alpha_k / max(nu, |v - x_k|)``, ``a = beta / sum(beta)`` with
@@ -2704,7 +2832,33 @@ def tree_geometric_median(pytrees: Iterable[PyTree], weights=None, *, iterations
     tables the kernel wrote. ``weights`` are uploaded once; ``None`` uploads nothing. The
     argument checks and their exceptions are the same. Returns a
     :class:`DeviceGeometricMedianResult` whose ``median`` is all +0 when no client is usable;
-    still raises under stream capture (the plan image goes through a pinned staging buffer)."""
+    still raises under stream capture (the plan image goes through a pinned staging buffer).
+
+    ``bucket_size=s`` is bucketing (as :func:`tree_krum` takes it, with ``perm``): the geometric
+    median of the ``B`` bucket means. ``weiszfeld_weights`` over
+    :func:`fedjax_amd.robust.bucket_gram` gives a weight ``a_b`` per bucket and every member of
+    bucket ``b`` folds with ``f32(a_b / n_b)``; a bucket with an unusable member has weight 0 and
+    its members are never loaded. In the result ``weights`` are those per-CLIENT fold weights and
+    ``distances`` are per BUCKET. Client ``weights`` together with ``bucket_size`` and
+    ``select="device"`` with ``bucket_size`` are ``ValueError`` before any pass over the deltas."""
+    if bucket_size is None and perm is not None:
+        raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
+    if bucket_size is not None:
+        kernels.check_select(select)
+        if select != "host":
+            raise ValueError('the bucketed selection is host-only: bucket_size needs select="host"')
+        if weights is not None:
+            raise ValueError("client weights and bucket_size cannot be combined: a bucket mean has no client weights")
+        kernels.refuse_capture("tree_geometric_median", kernels._TWO_PASS)
+        trees = pytrees if type(pytrees) is list else list(pytrees)
+        if not trees:
+            return None
+        _, perm = _bucket_args(len(trees), bucket_size, perm)
+        _check_median_iterations(iterations, nu)
+        gram = _tree_gram(trees)[0]
+        w32, d, ids = _bucket_median_plan(gram.cpu().numpy(), bucket_size, perm, iterations, nu)
+        median = tree_grouped_mean(list(zip(trees, w32)), ids, 1)[0] if (ids >= 0).any() else None
+        return GeometricMedianResult(median, w32, d, gram)
     if kernels.check_select(select):
         trees = pytrees if type(pytrees) is list else list(pytrees)
         if not trees:

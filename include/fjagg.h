@@ -582,6 +582,44 @@ int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
                     int flags, void* stream);
 
 /*
+ * Bucketing for the two aggregates above: Karimireddy, He and Jaggi, "Byzantine-Robust Learning on
+ * Heterogeneous Datasets via Bucketing", ICLR 2022, Algorithm 1 — shuffle the clients, average them in
+ * buckets of s, give the B = ceil(K / s) bucket means to the robust rule. The reference has no such
+ * aggregator; the semantics are fixed here. The bucket means are formed inside the column
+ * routine, where it asks for a value: one launch, no B x P temporary, every delta read twice (once for
+ * the sort, once for the sum). Float32, 1 <= K <= 4096 clients, s >= 1, B <= 128, 0 <= 2t < B.
+ *     perm = a table of K client indices in device memory, int32 (perm_dev; null: the identity)
+ *     bucket j, 0 <= j < B, has the members perm[j*s + i], i = 0 .. n_j - 1, n_j = min(s, K - j*s):
+ *              only the last bucket may be short (s > K is s = K: one bucket)
+ *     for every element p: a = the first member's x[p] verbatim; a = fl(a + x[p]) over the other
+ *              members in table order (no FMA); y_j = a when n_j == 1 (no multiply), else
+ *              y_j = fl(a * f32(1 / n_j)), the inverse the float32 of the double quotient; a y_j so
+ *              computed that is a NaN becomes +NaN 0x7FC00000 (IEEE leaves a result NaN's sign and
+ *              payload open, and the sign decides which end of the order the bucket is trimmed from)
+ *     out[p] = fjagg_trim_*'s rule over y_0 .. y_{B-1} in bucket order: the same total order, ties by
+ *              bucket index, the kept values added in bucket order, fl(sum * scale) with FJAGG_SCALE
+ *              (the caller passes f32(1 / (B - 2t))); t counts buckets, the median is t = (B-1)/2
+ * A short last bucket is divided by its own size n_j, not by s: this project's decision (the paper
+ * leaves K not divisible by s open); its mean then has the weight of a full bucket in the rule.
+ * s = 1 with the identity table is bit for bit fjagg_trim_*; s = 1 with a table is the trimmed mean of
+ * the permuted rows; s >= K is the mean in table order. A client holding a NaN poisons only its own
+ * bucket, which is then trimmed like any NaN. The host never reads the table, so nothing is uploaded
+ * and a graph replay reads it afresh; the kernel clamps every entry into [0, K) before it forms an
+ * address, so a stale table can give a wrong result but never an access outside the deltas. A table
+ * that is not a permutation counts a client twice or not at all; checking that is the caller's.
+ * Flags as fjagg_trim_*. Refused on the host with nothing launched: everything fjagg_trim_* refuses
+ * for its dtype and flags (FJAGG_EUNSUPPORTED); s < 1, K < 1, t < 0 or 2t >= B, null pointers other
+ * than perm_dev, P < 1, ld < P, a bad plan (FJAGG_EINVAL); B > 128, K > 4096 and rows over 1 GiB
+ * (FJAGG_EUNSUPPORTED, fjagg_last_error naming the limit).
+ */
+/* Dense slab: client k's row at x_dev + k*ld elements, P elements each; out_dev is float[P]. */
+int fjagg_trim_bucket_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, const int32_t* perm_dev,
+                            int64_t s, int64_t t, float scale, void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image as fjagg_trim_ptrs takes it, holding all K clients. */
+int fjagg_trim_bucket_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                           const int32_t* perm_dev, int64_t s, int64_t t, float scale, int flags, void* stream);
+
+/*
  * The mean around the median over the client axis ("MeaMed": Xie, Koyejo and Gupta, "Generalized
  * Byzantine-tolerant SGD", 2018), which is also the coordinate-wise second stage of Bulyan (El Mhamdi,
  * Guerraoui and Rouault, "The Hidden Vulnerability of Distributed Learning in Byzantium", ICML 2018):
