@@ -206,7 +206,7 @@ def _bucket_rng(bucket_size, rng):
     return int(bucket_size), rng
 
 
-def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None) -> Aggregator:
+def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None, method: str = "sort") -> Aggregator:
     """Builds the coordinate-wise trimmed-mean aggregator (Yin et al., ICML 2018): per coordinate
     the ``t`` smallest and ``t`` largest client values are dropped and the rest averaged, in one
     launch (:func:`fedjax_amd.tree_util.tree_trimmed_mean`). ``trim`` is the int count ``t`` or a
@@ -224,7 +224,12 @@ def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None
     ``rng=None`` buckets consecutive clients, UNSHUFFLED, which the paper's guarantee does not
     cover. ``trim`` and the Byzantine budget now count BUCKETS: ``f`` bad clients can spoil ``f``
     buckets out of ``K / s``, so the fraction of bad clients that a given ``trim`` fraction
-    tolerates shrinks by ``s`` (the paper's ``delta * s`` condition)."""
+    tolerates shrinks by ``s`` (the paper's ``delta * s`` condition).
+
+    ``method="select"``: the selection kernel of :func:`fedjax_amd.tree_util.tree_trimmed_mean`,
+    at most 1024 clients a round, the same bits; it takes no ``bucket_size`` or ``rng``."""
+    if kernels.trim_method(method):
+        kernels.refuse_bucketed_select(bucket_size, rng, "rng")
     if isinstance(trim, (bool, np.bool_)) or not isinstance(trim, (int, float, np.integer, np.floating)):
         raise TypeError("trim must be an int count or a float fraction in [0, 0.5)")
     if isinstance(trim, (float, np.floating)) and not (0.0 <= float(trim) < 0.5):
@@ -239,7 +244,7 @@ def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
         if bucket_size is None or not params:
-            return tree_util.tree_trimmed_mean(params, trim, bucket_size=bucket_size), state
+            return tree_util.tree_trimmed_mean(params, trim, bucket_size=bucket_size, method=method), state
         kernels.bucket_count(len(params), bucket_size)  # refuse the round before a key is drawn
         perm = None if rng is None else fj_random.permutation(next(rng), len(params))
         return tree_util.tree_trimmed_mean(params, trim, bucket_size=bucket_size, perm=perm), state
@@ -247,7 +252,7 @@ def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None
     return Aggregator(init, apply)
 
 
-def median_aggregator(*, bucket_size: Optional[int] = None, rng=None) -> Aggregator:
+def median_aggregator(*, bucket_size: Optional[int] = None, rng=None, method: str = "sort") -> Aggregator:
     """Builds the coordinate-wise median aggregator (Yin et al., ICML 2018):
     :func:`fedjax_amd.tree_util.tree_median` of the round's params. ``apply`` takes the usual
     triples and IGNORES the weights. Float32 params, at most 128 clients a round.
@@ -256,7 +261,10 @@ def median_aggregator(*, bucket_size: Optional[int] = None, rng=None) -> Aggrega
     means of shuffled buckets of ``bucket_size`` clients, for up to 4096 clients a round;
     ``rng=None`` buckets consecutive clients, UNSHUFFLED. The Byzantine budget counts BUCKETS:
     the median tolerates fewer than half the buckets spoiled, so fewer than ``K / (2 s)`` bad
-    clients (the paper's ``delta * s`` condition)."""
+    clients (the paper's ``delta * s`` condition). ``method="select"`` as
+    :func:`trimmed_mean_aggregator` takes it: at most 1024 clients a round, no buckets."""
+    if kernels.trim_method(method):
+        kernels.refuse_bucketed_select(bucket_size, rng, "rng")
     bucket_size, rng = _bucket_rng(bucket_size, rng)
 
     def init():
@@ -265,7 +273,7 @@ def median_aggregator(*, bucket_size: Optional[int] = None, rng=None) -> Aggrega
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
         if bucket_size is None or not params:
-            return tree_util.tree_median(params, bucket_size=bucket_size), state
+            return tree_util.tree_median(params, bucket_size=bucket_size, method=method), state
         kernels.bucket_count(len(params), bucket_size)  # refuse the round before a key is drawn
         perm = None if rng is None else fj_random.permutation(next(rng), len(params))
         return tree_util.tree_median(params, bucket_size=bucket_size, perm=perm), state

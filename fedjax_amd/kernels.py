@@ -697,21 +697,43 @@ def grouped_dense_shape(x: torch.Tensor, out: torch.Tensor, tables: GroupTables)
 
 
 TRIM_MAX_CLIENTS = 128  # fjagg_trim_*: a column's K values live in one lane (fjagg.h)
+TRIM_SELECT_MAX_CLIENTS = 1024  # fjagg_trim_select_*: a column's K keys live in a workgroup's LDS tile (fjagg.h)
 _MAX_ROW_BYTES = 1 << 30
 
 
-def trim_count(trim, K: int) -> int:
+def trim_method(method) -> bool:
+    """``method="sort" | "select"`` of the trimmed-mean and median surfaces: True for the selection
+    kernels (``fjagg_trim_select_*``, up to 1024 clients), False for the default sorting ones
+    (``fjagg_trim_*``, up to 128). Anything else is a ``ValueError``."""
+    if not isinstance(method, str) or method not in ("sort", "select"):
+        raise ValueError(f'method must be "sort" or "select", got {method!r}')
+    return method == "select"
+
+
+def refuse_bucketed_select(bucket_size, order, order_name: str = "perm") -> None:
+    """``method="select"`` takes no buckets: the bucketed rule runs in the sorting kernels only.
+    ``order`` is the surface's bucket-order argument, ``perm`` or the aggregators' ``rng``."""
+    if bucket_size is not None or order is not None:
+        raise ValueError(f'method="select" does not take bucket_size or {order_name}: bucketing runs with '
+                         'method="sort"')
+
+
+def trim_count(trim, K: int, *, select: bool = False) -> int:
     """The trim count ``t`` of a trimmed mean over ``K`` clients, checked: ``trim`` is an int count
     ``t``, or a float fraction ``0 <= beta < 0.5`` giving ``t = floor(beta * K)`` (in double
     precision: 0.29 of 100 is 28, since 0.29 * 100 < 29). Raises ``TypeError`` for a bool or a
     non-number, ``ValueError`` for more than 128 clients, a fraction outside [0, 0.5), or a count
-    with ``t < 0`` or ``2t >= K``. Nothing here touches the library."""
+    with ``t < 0`` or ``2t >= K``. ``select``: the limit of the selection kernels, 1024 clients,
+    in place of 128. Nothing here touches the library."""
     K = int(K)
     if isinstance(trim, (bool, np.bool_)):
         raise TypeError("trim must be an int count or a float fraction in [0, 0.5), not a bool")
     if K < 1:
         raise ValueError(f"a trimmed mean needs at least 1 client, got K = {K}")
-    if K > TRIM_MAX_CLIENTS:
+    if select and K > TRIM_SELECT_MAX_CLIENTS:
+        raise ValueError(f'the trimmed mean and median with method="select" support K <= {TRIM_SELECT_MAX_CLIENTS} '
+                         f"clients, got K = {K}")
+    if not select and K > TRIM_MAX_CLIENTS:
         raise ValueError(f"the trimmed mean and median support K <= {TRIM_MAX_CLIENTS} clients, got K = {K}")
     if isinstance(trim, (int, np.integer)):
         t = int(trim)
@@ -734,6 +756,12 @@ def trim_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None, out: O
     total order of fjagg.h are added in client order, then multiplied by ``scale`` (the trimmed
     mean passes f32(1 / (K - 2t))). One launch of ``fjagg_trim_dense``; there are no weights.
     ``K <= 128``, ``0 <= 2t < K``; everything is checked before the library is touched."""
+    return _trim_dense(False, x, t, scale, out, nontemporal)
+
+
+def _trim_dense(select: bool, x, t, scale, out, nontemporal) -> torch.Tensor:
+    """The checks and the launch of :func:`trim_dense` (``fjagg_trim_dense``) or, with ``select``, of
+    :func:`trim_select_dense` (``fjagg_trim_select_dense``): they differ in the client limit only."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("x must be a [K, P] tensor with unit column stride")
     if x.dtype != torch.float32:
@@ -741,7 +769,7 @@ def trim_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None, out: O
     K, P = x.shape
     if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
         raise TypeError("t must be an int trim count")
-    t = trim_count(int(t), K)
+    t = trim_count(int(t), K, select=select)
     if P < 1:
         raise ValueError("x must have at least one column")
     if P * 4 > _MAX_ROW_BYTES:
@@ -753,9 +781,24 @@ def trim_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None, out: O
     dev = _require_device(x, out)
     flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
     ld = x.stride(0) if K > 1 else P
-    _lib.call("fjagg_trim_dense", _lib.F32, x.data_ptr(), ld, K, P, t, float(scale if scale is not None else 1.0),
-              out.data_ptr(), flags, _stream_handle(dev))
+    _lib.call("fjagg_trim_select_dense" if select else "fjagg_trim_dense", _lib.F32, x.data_ptr(), ld, K, P, t,
+              float(scale if scale is not None else 1.0), out.data_ptr(), flags, _stream_handle(dev))
     return out
+
+
+def trim_select_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                      nontemporal: bool = False) -> torch.Tensor:
+    """:func:`trim_dense` by rank selection (fjagg.h, ``fjagg_trim_select_dense``): the same
+    arguments, checks and arithmetic, bit for bit its result for ``K <= 128``, for ``K <= 1024``
+    clients. One launch, nothing uploaded, no workspace."""
+    return _trim_dense(True, x, t, scale, out, nontemporal)
+
+
+def trim_select_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale: Optional[float], *,
+                     unaligned: bool = False, nontemporal: bool = False) -> None:
+    """:func:`trim_ptrs` by rank selection (``fjagg_trim_select_ptrs``): the same plan image,
+    checks and arithmetic, for ``K <= 1024`` clients."""
+    _trim_ptrs(True, image_dev, L, K, nblk, t, scale, unaligned, nontemporal)
 
 
 def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale: Optional[float], *,
@@ -764,9 +807,14 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
     leaf_n[L] | blocks[2*nblk]``, the blocks of :func:`ptrs_plan` for float32 leaves):
     :func:`trim_dense`'s arithmetic on every leaf in one launch. ``unaligned`` as the plan was
     made. Checked before the library is touched."""
+    _trim_ptrs(False, image_dev, L, K, nblk, t, scale, unaligned, nontemporal)
+
+
+def _trim_ptrs(select: bool, image_dev, L, K, nblk, t, scale, unaligned, nontemporal) -> None:
+    """The checks and the launch of :func:`trim_ptrs` or, with ``select``, of :func:`trim_select_ptrs`."""
     if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
         raise TypeError("t must be an int trim count")
-    t = trim_count(int(t), K)
+    t = trim_count(int(t), K, select=select)
     if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
         raise TypeError("image_dev must be a contiguous int64 device tensor")
     L, nblk = int(L), int(nblk)
@@ -775,7 +823,7 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
     dev = _require_device(image_dev)
     flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
     flags |= _lib.UNALIGNED if unaligned else 0
-    _lib.call("fjagg_trim_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
+    _lib.call("fjagg_trim_select_ptrs" if select else "fjagg_trim_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 

@@ -291,7 +291,7 @@ class ClientDeltaSlab:
         return [self.unflatten(out[g]) if alive[g] else None for g in range(G)]
 
     def trimmed_mean(self, trim, *, bucket_size: Optional[int] = None, perm=None,
-                     out: Optional[torch.Tensor] = None) -> PyTree:
+                     out: Optional[torch.Tensor] = None, method: str = "sort") -> PyTree:
         """Coordinate-wise trimmed mean of the K rows (Yin et al., ICML 2018): in every coordinate
         the ``t`` smallest and the ``t`` largest client values are dropped and the rest averaged,
         so up to ``t`` clients that upload ``inf``, ``NaN`` or huge values in a coordinate do not
@@ -322,14 +322,23 @@ class ClientDeltaSlab:
         the kernel clamps its entries into ``[0, K)``). Still one launch and no temporary; the
         bucket means are formed inside the column kernel, which reads every delta twice.
         ``bucket_size=1`` without ``perm`` is bit for bit the unbucketed result. ``perm`` without
-        ``bucket_size`` is a ``ValueError``."""
+        ``bucket_size`` is a ``ValueError``.
+
+        ``method="select"`` lifts the unbucketed limit to 1024 clients: the same
+        rule and the same bits (bit for bit ``method="sort"`` up to 128 clients), from a kernel
+        that selects the two ranks in an LDS tile instead of sorting a column in a lane. Still
+        one launch that reads every delta once, nothing uploaded, graph-capturable. It takes no
+        ``bucket_size`` or ``perm`` (``ValueError``); any other ``method`` is a ``ValueError``."""
+        select = kernels.trim_method(method)
+        if select:
+            kernels.refuse_bucketed_select(bucket_size, perm)
         if self.dtype != torch.float32:
             raise TypeError(f"trimmed_mean needs a float32 slab, not {self.dtype}")
         K = self.num_clients
         if bucket_size is None:
             if perm is not None:
                 raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
-            t = kernels.trim_count(trim, K)
+            t = kernels.trim_count(trim, K, select=select)
         else:
             B = kernels.bucket_count(K, bucket_size)
             t = kernels.bucket_trim_count(trim, B)
@@ -340,28 +349,34 @@ class ClientDeltaSlab:
         rows = self.rows
         nbytes = rows.numel() * rows.element_size()
         if bucket_size is None:
-            flat = kernels.trim_dense(rows, t, scale=float(np.float32(tree_util._inverse(K - 2 * t))), out=out,
-                                      nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
+            launch = kernels.trim_select_dense if select else kernels.trim_dense
+            flat = launch(rows, t, scale=float(np.float32(tree_util._inverse(K - 2 * t))), out=out,
+                          nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         else:
             flat = kernels.trim_bucket_dense(rows, int(bucket_size), t, perm=kernels.bucket_perm_device(perm, self.device),
                                              scale=float(np.float32(tree_util._inverse(B - 2 * t))), out=out,
                                              nontemporal=nbytes >= tree_util.NONTEMPORAL_MIN_BYTES)
         return self.unflatten(flat)
 
-    def median(self, *, bucket_size: Optional[int] = None, perm=None, out: Optional[torch.Tensor] = None) -> PyTree:
+    def median(self, *, bucket_size: Optional[int] = None, perm=None, out: Optional[torch.Tensor] = None,
+               method: str = "sort") -> PyTree:
         """Coordinate-wise median of the K rows: :meth:`trimmed_mean` at ``t = (K-1) // 2``. Odd
         K gives the middle value verbatim, even K ``fl(fl(a + b) * 0.5)`` of the two middle
         values (a before b in client order); ``np.median``'s bits on finite data. Weights play
         no part. A float32 slab of up to 128 clients. With ``bucket_size`` (and ``perm``) as
         :meth:`trimmed_mean` takes them: the median of the ``B`` bucket means, ``t = (B-1) // 2``,
-        for up to 4096 clients."""
+        for up to 4096 clients. ``method="select"`` as :meth:`trimmed_mean` takes it: up to 1024
+        clients, no buckets."""
+        select = kernels.trim_method(method)
+        if select:
+            kernels.refuse_bucketed_select(bucket_size, perm)
         if self.dtype != torch.float32:
             raise TypeError(f"median needs a float32 slab, not {self.dtype}")
         if bucket_size is None:
             if perm is not None:
                 raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")
-            kernels.trim_count(0, self.num_clients)
-            return self.trimmed_mean((self.num_clients - 1) // 2, out=out)
+            kernels.trim_count(0, self.num_clients, select=select)
+            return self.trimmed_mean((self.num_clients - 1) // 2, out=out, method=method)
         B = kernels.bucket_count(self.num_clients, bucket_size)
         return self.trimmed_mean((B - 1) // 2, bucket_size=bucket_size, perm=perm, out=out)
 

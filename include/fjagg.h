@@ -582,6 +582,29 @@ int fjagg_trim_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, in
                     int flags, void* stream);
 
 /*
+ * The same two aggregates for up to 1024 clients, by rank SELECTION instead of a sort.
+ * The arithmetic is fjagg_trim_*'s, word for word: the key order, the ranking by (key(v_k), k), the
+ * kept ranks t .. K-1-t, the first kept value verbatim and then fl(s + v_k) in CLIENT order with no
+ * FMA, fl(s * scale) with FJAGG_SCALE. 1 <= K <= 1024, 0 <= 2t < K. For K <= 128 the result is bit
+ * for bit fjagg_trim_*'s, NaN payloads included: the same adds in the same order.
+ * A 256-lane workgroup holds 32 columns of all K clients as keys in LDS, in client order; a wave
+ * finds a column's keys of rank t and K-1-t bit by bit from counts of the keys below a candidate
+ * (32 steps whatever the data), compacts the kept values in client order and adds them. One launch,
+ * every delta read once, no workspace, no atomics, nothing uploaded; the order of every operation is
+ * a function of (K, t) alone. 0xFFFFFFFF is a client's key like any other (the +NaN 0x7FFFFFFF):
+ * slots past K are excluded by client index, never by a sentinel. Columns past P or past a plan
+ * range's end store nothing. Float32 only; rows and leaves need float32's alignment only.
+ * Flags and refusals as fjagg_trim_* (on the host, nothing launched), with K > 1024 in place of
+ * K > 128 (FJAGG_EUNSUPPORTED, fjagg_last_error naming the limit). Opt-in: fjagg_trim_* is unchanged.
+ */
+/* Dense slab: client k's row at x_dev + k*ld elements, P elements each; out_dev is float[P]. */
+int fjagg_trim_select_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t t, float scale,
+                            void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image and blocks as fjagg_trim_ptrs takes them, decoded the same way. */
+int fjagg_trim_select_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t,
+                           float scale, int flags, void* stream);
+
+/*
  * Bucketing for the two aggregates above: Karimireddy, He and Jaggi, "Byzantine-Robust Learning on
  * Heterogeneous Datasets via Bucketing", ICLR 2022, Algorithm 1 — shuffle the clients, average them in
  * buckets of s, give the B = ceil(K / s) bucket means to the robust rule. The reference has no such
