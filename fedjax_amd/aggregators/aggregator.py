@@ -346,14 +346,15 @@ def krum_aggregator(num_byzantine: int, num_selected: int = 1, *, select: str = 
     return Aggregator(init, apply)
 
 
-def mean_around_median_aggregator(keep: int) -> Aggregator:
+def mean_around_median_aggregator(keep: int, *, method: str = "sort") -> Aggregator:
     """Builds the mean-around-the-median aggregator ("MeaMed", Xie et al. 2018): per coordinate
     the mean of the ``keep`` client values closest to the coordinate's median, in one launch
     (:func:`fedjax_amd.tree_util.tree_mean_around_median`). A round needs ``K >= keep`` clients.
 
     ``apply`` takes the usual ``(client_id, params, weight)`` triples and IGNORES the weights: a
     client must not be able to scale its own vote in a robust aggregate. Float32 params, at most
-    128 clients a round."""
+    128 clients a round; ``method="select"`` (the selection kernel, the same bits): at most 1024."""
+    kernels.meamed_method(method)
     if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)):
         raise TypeError("keep must be an int count")
     if keep < 1:
@@ -364,7 +365,7 @@ def mean_around_median_aggregator(keep: int) -> Aggregator:
 
     def apply(clients_params_and_weights, state):
         params = [param for _, param, _ in clients_params_and_weights]  # the weights are not used
-        return tree_util.tree_mean_around_median(params, keep), state
+        return tree_util.tree_mean_around_median(params, keep, method=method), state
 
     return Aggregator(init, apply)
 
@@ -391,7 +392,7 @@ class DeviceBulyanAggregatorState:
     keep: Any = None
 
 
-def bulyan_aggregator(num_byzantine: int, *, select: str = "host") -> Aggregator:
+def bulyan_aggregator(num_byzantine: int, *, select: str = "host", method: str = "sort") -> Aggregator:
     """Builds the Bulyan aggregator of El Mhamdi, Guerraoui and Rouault (ICML 2018):
     :func:`fedjax_amd.tree_util.tree_bulyan` of the round's params — ``K - 2f`` clients chosen by
     iterated Krum, ``f = num_byzantine``, then per coordinate the mean of the ``K - 4f`` chosen
@@ -405,8 +406,13 @@ def bulyan_aggregator(num_byzantine: int, *, select: str = "host") -> Aggregator
     ``select="device"`` runs the selection on the device (``tree_bulyan(..., select="device")``): no
     host step between the two passes. The mean of a round with too few selectable clients is then
     all +0 instead of ``None``, and the state is a :class:`DeviceBulyanAggregatorState` of device
-    tensors."""
+    tensors.
+
+    ``method="select"`` runs the second stage by rank selection (``tree_bulyan(..., method="select")``):
+    any ``K - 2f`` of up to 1024 clients. Host selection only: with ``select="device"`` it is a
+    ``ValueError`` here."""
     device = kernels.check_select(select)
+    kernels.refuse_device_bulyan_select(device, kernels.meamed_method(method))
     if isinstance(num_byzantine, (bool, np.bool_)) or not isinstance(num_byzantine, (int, np.integer)):
         raise TypeError("num_byzantine must be an int")
     if num_byzantine < 0:
@@ -423,7 +429,7 @@ def bulyan_aggregator(num_byzantine: int, *, select: str = "host") -> Aggregator
                 return None, DeviceBulyanAggregatorState()
             return got.mean, DeviceBulyanAggregatorState(tuple(cid for cid, _, _ in triples), got.selected,
                                                          got.count, got.keep)
-        got = tree_util.tree_bulyan([param for _, param, _ in triples], num_byzantine)
+        got = tree_util.tree_bulyan([param for _, param, _ in triples], num_byzantine, method=method)
         if got is None:
             return None, BulyanAggregatorState()
         ids = [cid for cid, _, _ in triples]

@@ -980,18 +980,30 @@ def trim_bucket_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, s: int,
 
 
 MEAMED_MAX_SLAB_ROWS = 1024  # fjagg_meamed_dense: the slab a row table selects from (the Gram pass's limit)
+MEAMED_SELECT_MAX_CLIENTS = 1024  # fjagg_meamed_select_*: a column's keys live in a workgroup's LDS tile (fjagg.h)
 
 
-def keep_count(keep, K: int) -> int:
+def meamed_method(method) -> bool:
+    """``method="sort" | "select"`` of the mean-around-median and Bulyan surfaces: True for the
+    selection kernels (``fjagg_meamed_select_*``, up to 1024 participating clients), False for the
+    default sorting ones (``fjagg_meamed_*``, up to 128). Anything else is a ``ValueError``."""
+    return trim_method(method)
+
+
+def keep_count(keep, K: int, *, select: bool = False) -> int:
     """The keep count ``beta`` of a mean around the median over ``K`` participating clients,
     checked: an int in ``[1, K]``. Raises ``TypeError`` for a bool or a non-int, ``ValueError``
-    for ``K`` outside ``[1, 128]`` or a count out of range. Nothing here touches the library."""
+    for ``K`` outside ``[1, 128]`` or a count out of range. ``select``: the limit of the selection
+    kernels, 1024 clients, in place of 128. Nothing here touches the library."""
     K = int(K)
     if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)):
         raise TypeError(f"keep must be an int count, not {type(keep).__name__}")
     if K < 1:
         raise ValueError(f"a mean around the median needs at least 1 client, got K = {K}")
-    if K > TRIM_MAX_CLIENTS:
+    if select and K > MEAMED_SELECT_MAX_CLIENTS:
+        raise ValueError(f'the mean around the median with method="select" supports K <= {MEAMED_SELECT_MAX_CLIENTS} '
+                         f"participating clients, got K = {K}")
+    if not select and K > TRIM_MAX_CLIENTS:
         raise ValueError(f"the mean around the median supports K <= {TRIM_MAX_CLIENTS} participating clients, "
                          f"got K = {K}")
     if not (1 <= int(keep) <= K):
@@ -999,14 +1011,14 @@ def keep_count(keep, K: int) -> int:
     return int(keep)
 
 
-def _row_table(rows, K_rows: int) -> np.ndarray:
+def _row_table(rows, K_rows: int, limit: int = TRIM_MAX_CLIENTS) -> np.ndarray:
     """``rows`` as the int32 table ``fjagg_meamed_dense`` takes: strictly ascending indices into
-    a slab of ``K_rows`` rows, at most 128 of them."""
+    a slab of ``K_rows`` rows, at most ``limit`` (128) of them."""
     if isinstance(rows, torch.Tensor):
         rows = rows.cpu().numpy()
     table = np.asarray(rows)
-    if table.ndim != 1 or not (1 <= table.size <= TRIM_MAX_CLIENTS):
-        raise ValueError(f"rows must name between 1 and {TRIM_MAX_CLIENTS} slab rows, got shape {table.shape}")
+    if table.ndim != 1 or not (1 <= table.size <= limit):
+        raise ValueError(f"rows must name between 1 and {limit} slab rows, got shape {table.shape}")
     if table.dtype == np.bool_ or not np.issubdtype(table.dtype, np.integer):
         raise TypeError("rows must be a sequence of int row indices")
     table = table.astype(np.int64)
@@ -1070,6 +1082,94 @@ def meamed_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, keep: int, s
     flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
     flags |= _lib.UNALIGNED if unaligned else 0
     _lib.call("fjagg_meamed_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, keep,
+              float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
+
+
+def select_row_table(rows, K_rows: int):
+    """The row table of :func:`meamed_select_dense`, checked without touching the library: ``None``
+    (every row), an int32 device tensor of 1 to ``min(1024, K_rows)`` entries (returned as it is
+    and never read here: the kernel clamps its entries into the slab), or a host sequence,
+    checked by :func:`_row_table` and returned as an int32 array."""
+    if rows is None:
+        return None
+    if not (1 <= K_rows <= MEAMED_MAX_SLAB_ROWS):
+        raise ValueError(f"a row table selects from a slab of 1 <= K <= {MEAMED_MAX_SLAB_ROWS} rows, got K = {K_rows}")
+    if isinstance(rows, torch.Tensor) and rows.is_cuda:
+        if (rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous()
+                or not (1 <= rows.numel() <= min(MEAMED_SELECT_MAX_CLIENTS, K_rows))):
+            raise ValueError(f"device rows must be a contiguous int32 tensor of 1 to "
+                             f"{min(MEAMED_SELECT_MAX_CLIENTS, K_rows)} entries")
+        return rows
+    return _row_table(rows, K_rows, MEAMED_SELECT_MAX_CLIENTS)
+
+
+def meamed_select_args(keep, rows, K_rows: int):
+    """``(table, M, keep)`` of a mean around the median by selection over a slab of ``K_rows`` rows:
+    :func:`select_row_table`'s table, the participant count and the checked keep count. Nothing
+    here touches the library."""
+    table = select_row_table(rows, K_rows)
+    M = K_rows if table is None else int(table.numel() if isinstance(table, torch.Tensor) else table.size)
+    return table, M, keep_count(keep, M, select=True)
+
+
+def meamed_select_dense(x: torch.Tensor, keep: int, rows=None, *, scale: Optional[float] = None,
+                        out: Optional[torch.Tensor] = None, nontemporal: bool = False) -> torch.Tensor:
+    """:func:`meamed_dense` by rank selection (fjagg.h, ``fjagg_meamed_select_dense``): the same
+    arithmetic, bit for bit its result up to 128 participating clients, for up to 1024 of a slab
+    of up to 1024 rows. ``rows``: ``None`` (all ``K`` rows); a host sequence, strictly ascending,
+    checked here and uploaded (which a stream capture refuses); or an int32 device tensor, used
+    as it is and never read by the host (capturable; the kernel clamps its entries into the
+    slab, so a stale table can give a wrong result but no fault). One launch, no workspace.
+    Everything is checked before the library is touched."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    return _meamed_select_launch(x, *meamed_select_args(keep, rows, x.shape[0]), scale=scale, out=out,
+                                nontemporal=nontemporal)
+
+
+def _meamed_select_launch(x: torch.Tensor, table, M: int, keep: int, *, scale: Optional[float] = None,
+                         out: Optional[torch.Tensor] = None, nontemporal: bool = False) -> torch.Tensor:
+    """:func:`meamed_select_dense` with the row table, the participant count and the keep count as
+    :func:`meamed_select_args` returned them for ``x.shape[0]`` rows: they are not checked again."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x must be a [K, P] tensor with unit column stride")
+    if x.dtype != torch.float32:
+        raise TypeError(f"the mean around the median takes float32 deltas, not {x.dtype}")
+    K, P = x.shape
+    if P < 1:
+        raise ValueError("x must have at least one column")
+    if P * 4 > _MAX_ROW_BYTES:
+        raise ValueError("the mean around the median takes rows of up to 1 GiB")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=x.device)
+    if out.dim() != 1 or out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of P elements")
+    dev = _require_device(x, out)
+    if isinstance(table, np.ndarray):
+        table = _lib.upload(torch.from_numpy(table), dev)
+    elif table is not None and table.device != dev:
+        raise ValueError(f"rows live on {table.device}, the deltas on {dev}")
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjagg_meamed_select_dense", _lib.F32, x.data_ptr(), ld, K, P, None if table is None else table.data_ptr(),
+              M, keep, float(scale if scale is not None else 1.0), out.data_ptr(), flags, _stream_handle(dev))
+    return out
+
+
+def meamed_select_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, keep: int, scale: Optional[float], *,
+                       unaligned: bool = False, nontemporal: bool = False) -> None:
+    """:func:`meamed_ptrs` by rank selection (``fjagg_meamed_select_ptrs``): the same plan image,
+    checks and arithmetic, for ``K <= 1024`` participating clients."""
+    keep = keep_count(keep, K, select=True)
+    if not isinstance(image_dev, torch.Tensor) or image_dev.dtype != torch.int64 or not image_dev.is_contiguous():
+        raise TypeError("image_dev must be a contiguous int64 device tensor")
+    L, nblk = int(L), int(nblk)
+    if L < 1 or nblk < 1 or image_dev.numel() < K * L + 2 * L + 2 * nblk:
+        raise ValueError(f"bad plan: L = {L}, nblk = {nblk}, image of {image_dev.numel()} words")
+    dev = _require_device(image_dev)
+    flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
+    flags |= _lib.UNALIGNED if unaligned else 0
+    _lib.call("fjagg_meamed_select_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, keep,
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 
@@ -1444,6 +1544,15 @@ def check_select(select) -> bool:
     if select == "device":
         return True
     raise ValueError(f'select must be "host" or "device", got {select!r}')
+
+
+def refuse_device_bulyan_select(device: bool, by_rank: bool) -> None:
+    """Bulyan with ``method="select"`` selects on the host: ``fjagg_bulyan_select``'s byte indices
+    and LDS arrays stop at K = 252, below the cohorts the selection kernels are for."""
+    if device and by_rank:
+        raise ValueError('method="select" runs with select="host": the device selection of Bulyan stops at '
+                         "K <= 252 clients (its byte indices and LDS arrays), below the cohorts "
+                         'method="select" is for')
 
 
 CENTER_MAX_CLIENTS = 4096  # fjagg_center_*: the clipped fold's client limit (fjagg.h)

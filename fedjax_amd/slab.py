@@ -381,7 +381,7 @@ class ClientDeltaSlab:
         return self.trimmed_mean((B - 1) // 2, bucket_size=bucket_size, perm=perm, out=out)
 
     def mean_around_median(self, keep, *, rows: Optional[Sequence[int]] = None,
-                           out: Optional[torch.Tensor] = None) -> PyTree:
+                           out: Optional[torch.Tensor] = None, method: str = "sort") -> PyTree:
         """The mean around the median of the rows ("MeaMed", Xie et al. 2018; the coordinate-wise
         stage of Bulyan): in every coordinate, the mean of the ``keep`` client values closest to
         the coordinate's lower median ``s_mid``, ``mid = (K-1) // 2``. ``keep`` is an int in
@@ -397,9 +397,27 @@ class ClientDeltaSlab:
         towards the strictly closer side, the lower side on a tie. The result is multiplied by
         f32(1 / keep): ``keep = K`` is bit for bit ``mean([1] * K)``, ``keep = 1`` the lower
         median verbatim. There are no weights. A float32 slab. Returns the template's pytree
-        (views into ``out`` if given: float32, ``num_params`` elements)."""
+        (views into ``out`` if given: float32, ``num_params`` elements).
+
+        ``method="select"`` lifts the limit to 1024 participating rows of a slab of up
+        to 1024: the same rule and the same bits (bit for bit ``method="sort"`` up to 128), from
+        a kernel that finds the window by rank selection in an LDS tile instead of sorting a
+        column in a lane. ``rows`` is then a host sequence, checked and uploaded (which a stream
+        capture refuses), or an int32 device tensor, used as it is and never read by the host:
+        the call can be captured, each replay reads the table afresh, and the kernel clamps its
+        entries into the slab. Any other ``method`` is a ``ValueError``."""
+        select = kernels.meamed_method(method)
         if self.dtype != torch.float32:
             raise TypeError(f"mean_around_median needs a float32 slab, not {self.dtype}")
+        if select:
+            table, M, keep = kernels.meamed_select_args(keep, rows, self.num_clients)
+            if self.num_params == 0:  # a template of empty leaves: nothing to launch
+                flat = out if out is not None else torch.empty(0, dtype=torch.float32, device=self.device)
+                return self.unflatten(flat)
+            flat = kernels._meamed_select_launch(
+                self.rows, table, M, keep, scale=float(np.float32(tree_util._inverse(keep))), out=out,
+                nontemporal=M * self.num_params * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
+            return self.unflatten(flat)
         if rows is not None:
             if self.num_clients > kernels.MEAMED_MAX_SLAB_ROWS:
                 raise ValueError(f"a row table selects from a slab of up to {kernels.MEAMED_MAX_SLAB_ROWS} "
@@ -414,7 +432,7 @@ class ClientDeltaSlab:
                                     nontemporal=M * self.num_params * 4 >= tree_util.NONTEMPORAL_MIN_BYTES)
         return self.unflatten(flat)
 
-    def bulyan(self, num_byzantine, *, select: str = "host"):
+    def bulyan(self, num_byzantine, *, select: str = "host", method: str = "sort"):
         """Bulyan (El Mhamdi, Guerraoui and Rouault, ICML 2018) over the rows: Krum iterated
         ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
         (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then
@@ -438,8 +456,16 @@ class ClientDeltaSlab:
         over rewritten deltas, and each replay selects afresh. The argument checks and their
         exceptions are the same. Returns a :class:`~fedjax_amd.tree_util.DeviceBulyanResult` of
         device tensors; ``mean`` is all +0 when fewer than ``2f + 1`` clients could be selected
-        (never ``None``)."""
-        if kernels.check_select(select):
+        (never ``None``).
+
+        ``method="select"`` runs the second stage by rank selection
+        (``mean_around_median(..., method="select")``): any ``K - 2f`` of ``K <= 1024`` clients, the
+        same bits where both methods apply. Host selection only: with ``select="device"`` it is a
+        ``ValueError`` before any pass over the deltas (the device selection stops at K = 252)."""
+        by_rank = kernels.meamed_method(method)
+        device = kernels.check_select(select)
+        kernels.refuse_device_bulyan_select(device, by_rank)
+        if device:
             if self.dtype != torch.float32:
                 raise TypeError(f"bulyan needs a float32 slab, not {self.dtype}")
             f = tree_util._check_bulyan_args(self.num_clients, num_byzantine)
@@ -455,10 +481,10 @@ class ClientDeltaSlab:
         kernels.refuse_capture("bulyan", kernels._TWO_PASS)
         if self.dtype != torch.float32:
             raise TypeError(f"bulyan needs a float32 slab, not {self.dtype}")
-        f = tree_util._check_bulyan_args(self.num_clients, num_byzantine)
+        f = tree_util._check_bulyan_args(self.num_clients, num_byzantine, select=by_rank)
         gram = self.gram()
         selected, members, keep = tree_util._bulyan_plan(gram.cpu().numpy(), f)
-        mean = self.mean_around_median(keep, rows=members) if keep else None
+        mean = self.mean_around_median(keep, rows=members, method=method) if keep else None
         return tree_util.BulyanResult(mean, selected, keep, gram)
 
     def gram(self, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:

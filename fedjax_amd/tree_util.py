@@ -2169,7 +2169,7 @@ def tree_median(pytrees: Iterable[PyTree], *, bucket_size: Optional[int] = None,
     return tree_trimmed_mean(trees, (len(trees) - 1) // 2, method=method)
 
 
-def tree_mean_around_median(pytrees: Iterable[PyTree], keep) -> Optional[PyTree]:
+def tree_mean_around_median(pytrees: Iterable[PyTree], keep, *, method: str = "sort") -> Optional[PyTree]:
     """The mean around the median of client pytrees ("MeaMed", Xie et al. 2018; the coordinate-wise
     stage of Bulyan): in every coordinate of every leaf, the mean of the ``keep`` client values
     closest to the coordinate's lower median ``s_mid``, ``mid = (K-1) // 2``. ``keep`` is an int
@@ -2184,16 +2184,22 @@ def tree_mean_around_median(pytrees: Iterable[PyTree], keep) -> Optional[PyTree]
     bit :meth:`fedjax_amd.slab.ClientDeltaSlab.mean_around_median` over the same deltas. There
     are no weights. The walk, checks, plan image and ONE launch are :func:`tree_trimmed_mean`'s.
     Float32 leaves, ``K <= 128``; no clients: ``None``. Raises under stream capture (the plan
-    image goes through a pinned staging buffer)."""
+    image goes through a pinned staging buffer).
+
+    ``method="select"``: the same rule and bits from the selection kernel, for
+    ``K <= 1024`` (bit for bit ``method="sort"`` up to 128 clients, and bit for bit the slab's
+    ``method="select"``). The plan image, its upload and the capture refusal are unchanged. Any
+    other ``method`` is a ``ValueError``."""
+    select = kernels.meamed_method(method)
     trees = pytrees if type(pytrees) is list else list(pytrees)
     if not trees:
         return None
     K = len(trees)
-    keep = kernels.keep_count(keep, K)
+    keep = kernels.keep_count(keep, K, select=select)
     scale = float(np.float32(_inverse(keep)))
+    launch = kernels.meamed_select_ptrs if select else kernels.meamed_ptrs
     return _tree_columns(trees, "tree_mean_around_median",
-                         lambda image_dev, L, nblk, nt: kernels.meamed_ptrs(image_dev, L, K, nblk, keep, scale,
-                                                                            nontemporal=nt))
+                         lambda image_dev, L, nblk, nt: launch(image_dev, L, K, nblk, keep, scale, nontemporal=nt))
 
 
 class CenteredClip(NamedTuple):
@@ -2410,13 +2416,14 @@ class BulyanResult(NamedTuple):
 BULYAN_MAX_SELECTED = kernels.TRIM_MAX_CLIENTS  # theta = K - 2f clients reach the column routine
 
 
-def _check_bulyan_args(K: int, num_byzantine) -> int:
-    """Bulyan's argument checks on K and f alone, before any pass over the deltas."""
+def _check_bulyan_args(K: int, num_byzantine, *, select: bool = False) -> int:
+    """Bulyan's argument checks on K and f alone, before any pass over the deltas. ``select``: the
+    second stage runs by rank selection, which takes every ``K - 2f`` the Gram pass's K allows."""
     from fedjax_amd import robust
 
     kernels._check_gram_clients(K)
     f = robust.check_bulyan(K, num_byzantine)
-    if K - 2 * f > BULYAN_MAX_SELECTED:
+    if not select and K - 2 * f > BULYAN_MAX_SELECTED:
         raise ValueError(f"Bulyan's second stage takes K - 2f <= {BULYAN_MAX_SELECTED} selected clients, "
                          f"got K = {K}, f = {f}")
     return f
@@ -2447,7 +2454,7 @@ class DeviceBulyanResult(NamedTuple):
     gram: Any
 
 
-def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine, *, select: str = "host"):
+def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine, *, select: str = "host", method: str = "sort"):
     """Bulyan over client pytrees (El Mhamdi, Guerraoui and Rouault, ICML 2018): Krum iterated
     ``theta = K - 2f`` times on the shrinking set of clients not yet chosen
     (:func:`fedjax_amd.robust.bulyan_select`, ``f = num_byzantine``), then, per coordinate, the
@@ -2469,8 +2476,16 @@ def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine, *, select: str = "host
     so the same bits) — no device-to-host copy, no synchronisation. The argument checks and
     their exceptions are the same. Returns a :class:`DeviceBulyanResult` whose ``mean`` is all +0
     when too few clients could be selected (never ``None``); still raises under stream capture,
-    because the plan images go through a pinned staging buffer."""
-    if kernels.check_select(select):
+    because the plan images go through a pinned staging buffer.
+
+    ``method="select"`` runs the second stage by rank selection
+    (``tree_mean_around_median(..., method="select")``): any ``K - 2f`` of ``K <= 1024`` clients, the
+    same bits where both methods apply, and bit for bit the slab's. Host selection only: with
+    ``select="device"`` it is a ``ValueError`` before any pass over the deltas."""
+    by_rank = kernels.meamed_method(method)
+    device = kernels.check_select(select)
+    kernels.refuse_device_bulyan_select(device, by_rank)
+    if device:
         trees = pytrees if type(pytrees) is list else list(pytrees)
         if not trees:
             return None
@@ -2484,10 +2499,10 @@ def tree_bulyan(pytrees: Iterable[PyTree], num_byzantine, *, select: str = "host
     trees = pytrees if type(pytrees) is list else list(pytrees)
     if not trees:
         return None
-    f = _check_bulyan_args(len(trees), num_byzantine)
+    f = _check_bulyan_args(len(trees), num_byzantine, select=by_rank)
     gram = _tree_gram(trees)[0]
     selected, members, keep = _bulyan_plan(gram.cpu().numpy(), f)
-    mean = tree_mean_around_median([trees[k] for k in members], keep) if keep else None
+    mean = tree_mean_around_median([trees[k] for k in members], keep, method=method) if keep else None
     return BulyanResult(mean, selected, keep, gram)
 
 

@@ -676,6 +676,35 @@ int fjagg_meamed_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, 
                       int flags, void* stream);
 
 /*
+ * The same aggregate for up to 1024 participating clients, by rank SELECTION instead of a sort
+ * (DESIGN §3w). The arithmetic is fjagg_meamed_*'s, word for word: the order, the lower median, the
+ * distances, the window and its ties, the kept values added in CLIENT order with no FMA, fl(s * scale)
+ * with FJAGG_SCALE. 1 <= M <= 1024, 1 <= keep <= M. For M <= 128 the result is bit for bit
+ * fjagg_meamed_*'s, NaN payloads included. The tile is fjagg_trim_select_*'s: a 256-lane workgroup
+ * holds 32 columns of all M clients as keys in LDS, and a wave finds a column's window from three bit
+ * descents over counts: the median, then the distance of rank keep-2 among the other M-1 sorted
+ * positions (lower side before upper side at equal distance), then the keys at the window's two ends.
+ * One launch, every participating delta read once, no workspace, no atomics; the order of every
+ * operation is a function of (M, keep) alone.
+ * The dense entry's row table lives in DEVICE memory (int32[M]; 1024 entries do not fit the kernel
+ * arguments): it is never read by the host, so it is not checked for order here, and the kernel
+ * clamps every entry into [0, K_rows) before it forms an address; a row it does not name is never
+ * read. Null: the rows 0 .. M-1 of a slab of exactly M rows.
+ * Flags: FJAGG_SCALE, FJAGG_NONTEMPORAL and, on the pytree entry, FJAGG_UNALIGNED. Refused on the
+ * host with nothing launched, with fjagg_trim_select_*'s codes: a dtype other than float32, every
+ * other flag, M > 1024 and K_rows > 1024 (FJAGG_EUNSUPPORTED); M < 1, K_rows < 1, M > K_rows (or
+ * M != K_rows without a table), keep < 1 or keep > M, null pointers, P < 1, ld < P, a bad plan
+ * (FJAGG_EINVAL); rows over 1 GiB (FJAGG_EUNSUPPORTED). Opt-in: fjagg_meamed_* is unchanged.
+ */
+/* Dense slab: row r at x_dev + r*ld elements, P elements each; out_dev is float[P]. */
+int fjagg_meamed_select_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K_rows, int64_t P,
+                              const int32_t* rows_dev /* NULL: rows 0..M-1, M == K_rows */, int64_t M,
+                              int64_t keep, float scale, void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image as fjagg_meamed_ptrs takes it, decoded as fjagg_trim_select_ptrs decodes it. */
+int fjagg_meamed_select_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk,
+                             int64_t keep, float scale, int flags, void* stream);
+
+/*
  * The K x K Gram matrix of the client deltas, G[i][j] = sum_p x_i[p] * x_j[p], in float64: the one
  * pass over the deltas that the two whole-vector Byzantine-robust aggregates need. Krum and
  * multi-Krum (Blanchard, El Mhamdi, Guerraoui and Stainer, "Machine Learning with Adversaries:
