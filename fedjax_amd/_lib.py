@@ -99,6 +99,8 @@ _SIGNATURES = {
     "fjagg_trim_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_trim_select_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i32, _vp]),
     "fjagg_trim_select_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
+    "fjagg_trim_select16_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i32, _vp]),
+    "fjagg_trim_select16_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_trim_bucket_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _vp, _i32, _vp]),
     "fjagg_trim_bucket_ptrs": (_i32, [_i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp]),
     "fjagg_meamed_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _vp, _i32, _vp]),

@@ -227,7 +227,8 @@ def trimmed_mean_aggregator(trim, *, bucket_size: Optional[int] = None, rng=None
     tolerates shrinks by ``s`` (the paper's ``delta * s`` condition).
 
     ``method="select"``: the selection kernel of :func:`fedjax_amd.tree_util.tree_trimmed_mean`,
-    at most 1024 clients a round, the same bits; it takes no ``bucket_size`` or ``rng``."""
+    at most 1024 clients a round, the same bits; it takes no ``bucket_size`` or ``rng``. It also
+    takes params that are all bfloat16 and returns their float32 trimmed mean."""
     if kernels.trim_method(method):
         kernels.refuse_bucketed_select(bucket_size, rng, "rng")
     if isinstance(trim, (bool, np.bool_)) or not isinstance(trim, (int, float, np.integer, np.floating)):

@@ -8,7 +8,8 @@
 // K-1-t, and the counts of keys below L, above U and equal to U. The key of rank r is the
 // largest v with |{key < v}| <= r, so it is built from its most significant bit down: bit b is
 // set iff the count of keys below (v | 1 << b) is still <= r. Both ranks descend together, one
-// bit a step, 32 steps whatever the data. A step asks only "how many client keys are below
+// bit a step, 32 steps whatever the data (BITS = 16 steps over the 16-bit keys of bfloat16
+// values, key16_of below: fjtrimsel16.hip). A step asks only "how many client keys are below
 // these two candidates": how the keys are held and counted is the caller's (a wave's registers
 // and ballots on the device, a loop on the host). The count that admitted a bit is the count
 // below the prefix so far, so the descent ends with |{key < L}| and |{key < U}| in hand; one
@@ -31,14 +32,14 @@ struct Cuts {
 };
 
 // count2(a, b, na, nb): na = clients with key < a, nb = clients with key < b.
-// count_eq(u): clients with key == u. 1 <= K, 0 <= 2t < K.
-template <class Count2, class CountEq>
+// count_eq(u): clients with key == u. 1 <= K, 0 <= 2t < K. Every key is below 2^BITS.
+template <int BITS = 32, class Count2, class CountEq>
 FJR_HD Cuts select_cuts(Count2 count2, CountEq count_eq, int K, int t) {
   const int rl = t, ru = K - 1 - t;
   uint32_t L = 0, U = 0;
   int belowL = 0, belowU = 0;
 #pragma unroll 1
-  for (int b = 31; b >= 0; --b) {
+  for (int b = BITS - 1; b >= 0; --b) {
     const uint32_t cl = L | (1u << b), cu = U | (1u << b);
     int nl, nu;
     count2(cl, cu, nl, nu);
@@ -61,6 +62,13 @@ FJR_HD bool kept(uint32_t key, const Cuts& c, int iL, int iU) {
   const bool isL = key == c.L, isU = key == c.U;
   return key >= c.L && key <= c.U && (!isL || iL >= c.nL) && (!isU || iU < c.keepU);
 }
+
+// The 16-bit key of a bfloat16 value's bits b: the top half of fjrobust::key_of(b << 16), whose low
+// half (0xFFFF or 0x0000) depends on the sign alone, so keys of bfloat16 values compare as their
+// top halves do and tie exactly when the values' bits are equal. Zero-extended in a uint32.
+FJR_HD uint32_t key16_of(uint32_t b) { return b ^ ((b >> 15) ? 0xFFFFu : 0x8000u); }
+// its inverse, shifted into place: the float32 bits of the bfloat16 value whose key is k
+FJR_HD uint32_t float_bits_of_key16(uint32_t k) { return (k ^ ((k >> 15) ? 0x8000u : 0xFFFFu)) << 16; }
 
 // fl(s + x) with the running sum as the instruction's FIRST operand. IEEE leaves open which
 // payload a sum of two NaNs carries; the hardware takes the first operand's, and the compiler is

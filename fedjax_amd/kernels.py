@@ -764,7 +764,8 @@ def _trim_dense(select: bool, x, t, scale, out, nontemporal) -> torch.Tensor:
     :func:`trim_select_dense` (``fjagg_trim_select_dense``): they differ in the client limit only."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("x must be a [K, P] tensor with unit column stride")
-    if x.dtype != torch.float32:
+    bf16 = select and x.dtype == torch.bfloat16  # fjagg_trim_select16_dense: 16-bit keys, float32 out
+    if x.dtype != torch.float32 and not bf16:
         raise TypeError(f"the trimmed mean takes float32 deltas, not {x.dtype}")
     K, P = x.shape
     if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
@@ -772,7 +773,7 @@ def _trim_dense(select: bool, x, t, scale, out, nontemporal) -> torch.Tensor:
     t = trim_count(int(t), K, select=select)
     if P < 1:
         raise ValueError("x must have at least one column")
-    if P * 4 > _MAX_ROW_BYTES:
+    if P * x.element_size() > _MAX_ROW_BYTES:
         raise ValueError("the trimmed mean takes rows of up to 1 GiB")
     if out is None:
         out = torch.empty(P, dtype=torch.float32, device=x.device)
@@ -781,7 +782,8 @@ def _trim_dense(select: bool, x, t, scale, out, nontemporal) -> torch.Tensor:
     dev = _require_device(x, out)
     flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
     ld = x.stride(0) if K > 1 else P
-    _lib.call("fjagg_trim_select_dense" if select else "fjagg_trim_dense", _lib.F32, x.data_ptr(), ld, K, P, t,
+    entry = "fjagg_trim_select16_dense" if bf16 else "fjagg_trim_select_dense" if select else "fjagg_trim_dense"
+    _lib.call(entry, _lib.BF16 if bf16 else _lib.F32, x.data_ptr(), ld, K, P, t,
               float(scale if scale is not None else 1.0), out.data_ptr(), flags, _stream_handle(dev))
     return out
 
@@ -790,15 +792,23 @@ def trim_select_dense(x: torch.Tensor, t: int, *, scale: Optional[float] = None,
                       nontemporal: bool = False) -> torch.Tensor:
     """:func:`trim_dense` by rank selection (fjagg.h, ``fjagg_trim_select_dense``): the same
     arguments, checks and arithmetic, bit for bit its result for ``K <= 128``, for ``K <= 1024``
-    clients. One launch, nothing uploaded, no workspace."""
+    clients. One launch, nothing uploaded, no workspace.
+
+    A bfloat16 ``x`` goes to ``fjagg_trim_select16_dense``: the selection runs over
+    16-bit keys, and the float32 ``out`` holds bit for bit the result of the same values upcast to
+    float32, with no float32 copy of ``x`` made. Rows then need bfloat16's alignment only."""
     return _trim_dense(True, x, t, scale, out, nontemporal)
 
 
 def trim_select_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale: Optional[float], *,
-                     unaligned: bool = False, nontemporal: bool = False) -> None:
+                     unaligned: bool = False, nontemporal: bool = False, dtype: torch.dtype = torch.float32) -> None:
     """:func:`trim_ptrs` by rank selection (``fjagg_trim_select_ptrs``): the same plan image,
-    checks and arithmetic, for ``K <= 1024`` clients."""
-    _trim_ptrs(True, image_dev, L, K, nblk, t, scale, unaligned, nontemporal)
+    checks and arithmetic, for ``K <= 1024`` clients. ``dtype``: the input leaves' type, the one
+    :func:`ptrs_plan` was given: float32, or bfloat16 for ``fjagg_trim_select16_ptrs``. The output
+    leaves are float32 either way."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"the trimmed mean by selection takes float32 or bfloat16 leaves, not {dtype}")
+    _trim_ptrs(True, image_dev, L, K, nblk, t, scale, unaligned, nontemporal, bf16=dtype == torch.bfloat16)
 
 
 def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale: Optional[float], *,
@@ -810,7 +820,7 @@ def trim_ptrs(image_dev: torch.Tensor, L: int, K: int, nblk: int, t: int, scale:
     _trim_ptrs(False, image_dev, L, K, nblk, t, scale, unaligned, nontemporal)
 
 
-def _trim_ptrs(select: bool, image_dev, L, K, nblk, t, scale, unaligned, nontemporal) -> None:
+def _trim_ptrs(select: bool, image_dev, L, K, nblk, t, scale, unaligned, nontemporal, bf16: bool = False) -> None:
     """The checks and the launch of :func:`trim_ptrs` or, with ``select``, of :func:`trim_select_ptrs`."""
     if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
         raise TypeError("t must be an int trim count")
@@ -823,7 +833,8 @@ def _trim_ptrs(select: bool, image_dev, L, K, nblk, t, scale, unaligned, nontemp
     dev = _require_device(image_dev)
     flags = (_lib.SCALE if scale is not None else 0) | (_lib.NONTEMPORAL if nontemporal else 0)
     flags |= _lib.UNALIGNED if unaligned else 0
-    _lib.call("fjagg_trim_select_ptrs" if select else "fjagg_trim_ptrs", _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
+    entry = "fjagg_trim_select16_ptrs" if bf16 else "fjagg_trim_select_ptrs" if select else "fjagg_trim_ptrs"
+    _lib.call(entry, _lib.BF16 if bf16 else _lib.F32, image_dev.data_ptr(), L, K, nblk, t,
               float(scale if scale is not None else 1.0), flags, _stream_handle(dev))
 
 

@@ -328,12 +328,17 @@ class ClientDeltaSlab:
         rule and the same bits (bit for bit ``method="sort"`` up to 128 clients), from a kernel
         that selects the two ranks in an LDS tile instead of sorting a column in a lane. Still
         one launch that reads every delta once, nothing uploaded, graph-capturable. It takes no
-        ``bucket_size`` or ``perm`` (``ValueError``); any other ``method`` is a ``ValueError``."""
+        ``bucket_size`` or ``perm`` (``ValueError``); any other ``method`` is a ``ValueError``.
+
+        ``method="select"`` also takes a bfloat16 slab: the selection runs over
+        bfloat16's 16-bit keys and the float32 result is bit for bit that of a float32 slab
+        holding the same values, without the K x P float32 copy. ``method="sort"`` and
+        ``bucket_size`` stay float32 only (``TypeError``)."""
         select = kernels.trim_method(method)
         if select:
             kernels.refuse_bucketed_select(bucket_size, perm)
-        if self.dtype != torch.float32:
-            raise TypeError(f"trimmed_mean needs a float32 slab, not {self.dtype}")
+        if self.dtype != torch.float32 and not select:
+            raise TypeError(f'trimmed_mean needs a float32 slab, not {self.dtype} (bfloat16: method="select")')
         K = self.num_clients
         if bucket_size is None:
             if perm is not None:
@@ -366,12 +371,12 @@ class ClientDeltaSlab:
         no part. A float32 slab of up to 128 clients. With ``bucket_size`` (and ``perm``) as
         :meth:`trimmed_mean` takes them: the median of the ``B`` bucket means, ``t = (B-1) // 2``,
         for up to 4096 clients. ``method="select"`` as :meth:`trimmed_mean` takes it: up to 1024
-        clients, no buckets."""
+        clients, no buckets, a float32 or bfloat16 slab."""
         select = kernels.trim_method(method)
         if select:
             kernels.refuse_bucketed_select(bucket_size, perm)
-        if self.dtype != torch.float32:
-            raise TypeError(f"median needs a float32 slab, not {self.dtype}")
+        if self.dtype != torch.float32 and not select:
+            raise TypeError(f'median needs a float32 slab, not {self.dtype} (bfloat16: method="select")')
         if bucket_size is None:
             if perm is not None:
                 raise ValueError("perm orders the clients of a bucketed aggregate: pass bucket_size too")

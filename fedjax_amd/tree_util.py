@@ -2032,7 +2032,10 @@ def tree_trimmed_mean(pytrees: Iterable[PyTree], trim, *, bucket_size: Optional[
     ``method="select"``: the same rule and bits from the selection kernel, for
     ``K <= 1024`` (bit for bit ``method="sort"`` up to 128 clients, and bit for bit the slab's
     ``method="select"``). The plan image, its upload and the capture refusal are unchanged. It
-    takes no ``bucket_size`` or ``perm``; any other ``method`` is a ``ValueError``."""
+    takes no ``bucket_size`` or ``perm``; any other ``method`` is a ``ValueError``. It also takes
+    leaves that are ALL bfloat16: the result leaves are float32, bit for bit those of
+    the same values as float32 leaves, and no float32 copy is made. A mix of float32 and bfloat16
+    leaves is a ``TypeError``."""
     select = kernels.trim_method(method)
     if select:
         kernels.refuse_bucketed_select(bucket_size, perm)
@@ -2052,20 +2055,26 @@ def tree_trimmed_mean(pytrees: Iterable[PyTree], trim, *, bucket_size: Optional[
             nontemporal=nt))
     t = kernels.trim_count(trim, K, select=select)
     scale = float(np.float32(_inverse(K - 2 * t)))
-    launch = kernels.trim_select_ptrs if select else kernels.trim_ptrs
-    return _tree_columns(trees, "tree_trimmed_mean",
-                         lambda image_dev, L, nblk, nt: launch(image_dev, L, K, nblk, t, scale, nontemporal=nt))
+    if not select:
+        return _tree_columns(trees, "tree_trimmed_mean", lambda image_dev, L, nblk, nt: kernels.trim_ptrs(
+            image_dev, L, K, nblk, t, scale, nontemporal=nt))
+    return _tree_columns(trees, "tree_trimmed_mean", lambda image_dev, L, nblk, nt, dtype: kernels.trim_select_ptrs(
+        image_dev, L, K, nblk, t, scale, nontemporal=nt, dtype=dtype), bf16=True)
 
 
-def _tree_columns(trees: list, what: str, launch) -> PyTree:
+def _tree_columns(trees: list, what: str, launch, bf16: bool = False) -> PyTree:
     """The pytree route of the per-column aggregates (trimmed mean, mean around the median) over
     a non-empty list of client trees: ``tree_mean``'s structure walk and checks, one result row,
-    one plan image, and ``launch(image_dev, L, nblk, nontemporal)`` once over every leaf."""
+    one plan image, and ``launch(image_dev, L, nblk, nontemporal)`` once over every leaf.
+    ``bf16``: leaves that are all bfloat16 are taken too (a mix is not), the plan is bfloat16's,
+    and ``launch`` gets the leaves' dtype as a fifth argument; the result row is float32."""
     K = len(trees)
-    bad = sorted({str(x.dtype) for x in map(_to_tensor, pytree.leaves_of(trees[0]))
-                  if _CANONICAL.get(x.dtype) != torch.float32})
+    kinds = [(_CANONICAL.get(x.dtype), str(x.dtype)) for x in map(_to_tensor, pytree.leaves_of(trees[0]))]
+    in_dtype = torch.bfloat16 if bf16 and {c for c, _ in kinds} == {torch.bfloat16} else torch.float32
+    bad = sorted({name for c, name in kinds if c != in_dtype})
     if bad:
-        raise TypeError(f"{what} needs float32 leaves (got {bad})")
+        takes = "float32 leaves, or bfloat16 leaves throughout" if bf16 else "float32 leaves"
+        raise TypeError(f"{what} needs {takes} (got {bad})")
     td, rows = _client_table(trees)
     if not rows[0]:
         return pytree.unflatten(td, [])
@@ -2080,10 +2089,12 @@ def _tree_columns(trees: list, what: str, launch) -> PyTree:
         return result
     in_ptrs = _ptr_table(rows)
     out_ptrs = flat.data_ptr() + 4 * offs[:-1].astype(np.int64)
-    blocks, _ = _leaf_plan(_lib.F32, leaf_n, in_ptrs, out_ptrs, device)
+    esize = 2 if in_dtype == torch.bfloat16 else 4
+    blocks, _ = _leaf_plan(_lib.BF16 if esize == 2 else _lib.F32, leaf_n, in_ptrs, out_ptrs, device)
     image = np.concatenate([in_ptrs.ravel(), out_ptrs, leaf_n, blocks])
     image_dev = _lib.upload(torch.from_numpy(image), device)
-    launch(image_dev, L, len(blocks) // 2, int(leaf_n.sum()) * K * 4 >= NONTEMPORAL_MIN_BYTES)
+    nt = int(leaf_n.sum()) * K * esize >= NONTEMPORAL_MIN_BYTES
+    launch(image_dev, L, len(blocks) // 2, nt, *([in_dtype] if bf16 else []))
     return result
 
 

@@ -605,6 +605,33 @@ int fjagg_trim_select_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_
                            float scale, int flags, void* stream);
 
 /*
+ * The same two aggregates of BFLOAT16 deltas, by rank selection over 16-bit keys. The
+ * result is float32 and is, bit for bit, what fjagg_trim_select_* gives on the same values upcast to
+ * float32 (bits << 16, exact): the ranking by (key(v_k), k), the kept ranks t .. K-1-t, the first kept
+ * value verbatim as float32 and then fl(s + v_k) in CLIENT order with the running sum as the first
+ * operand and no FMA, fl(s * scale) with FJAGG_SCALE. 1 <= K <= 1024, 0 <= 2t < K. No float32 copy of
+ * the deltas is made: every bfloat16 delta is read once, two bytes a value.
+ *     key16(b) = b ^ ((b >> 15) ? 0xFFFF : 0x8000), compared as uint16: the top half of key(b << 16),
+ *                whose low half depends on the sign alone, so the order and the ties are key()'s
+ * A workgroup of 8 waves holds 64 columns of all K clients as 16-bit keys in LDS, in client order; a
+ * wave finds a column's keys of rank t and K-1-t in 16 steps (half of fjagg_trim_select_*'s 32),
+ * compacts the kept keys in client order, and the sum turns each back into float32 bits as it adds.
+ * One launch, no workspace, no atomics, nothing uploaded; the order of every operation is a function
+ * of (K, t) alone. 0xFFFF is a client's key like any other (the +NaN 0x7FFF): slots past K are
+ * excluded by client index. Rows and leaves need bfloat16's alignment only; out and the plan's output
+ * leaves are float32. The plan is fjagg_ptrs_plan_leaves' for FJAGG_BF16 (units of 8 elements, of 1
+ * with FJAGG_UNALIGNED or on a leaf marked for element units).
+ * in_dtype must be FJAGG_BF16 (anything else: FJAGG_EUNSUPPORTED). Flags, limits and refusals are
+ * fjagg_trim_select_*'s, on the host with nothing launched; rows over 1 GiB are P * 2 bytes.
+ */
+/* Dense slab: client k's row at x_dev + k*ld bfloat16 elements, P elements each; out_dev is float[P]. */
+int fjagg_trim_select16_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P, int64_t t,
+                              float scale, void* out_dev, int flags, void* stream);
+/* Pytree path: the plan image and blocks as fjagg_trim_select_ptrs takes them, for bfloat16 leaves. */
+int fjagg_trim_select16_ptrs(int in_dtype, const int64_t* image_dev, int L, int64_t K, int64_t nblk, int64_t t,
+                             float scale, int flags, void* stream);
+
+/*
  * Bucketing for the two aggregates above: Karimireddy, He and Jaggi, "Byzantine-Robust Learning on
  * Heterogeneous Datasets via Bucketing", ICLR 2022, Algorithm 1 — shuffle the clients, average them in
  * buckets of s, give the B = ceil(K / s) bucket means to the robust rule. The reference has no such
