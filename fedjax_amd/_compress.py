@@ -208,6 +208,94 @@ def quant_fold(method: int, in_ptrs: np.ndarray, keys: np.ndarray, qparams_ptr: 
     return up
 
 
+# ----------------------------------------------------------------------------- 8-bit level codes
+def check_num_levels(num_levels) -> int:
+    """The level counts whose index fits a byte: an int in [2, 256] (a bool is refused)."""
+    if isinstance(num_levels, (bool, np.bool_)) or not isinstance(num_levels, (int, np.integer)):
+        raise TypeError(f"num_levels must be an int in [2, 256], not {type(num_levels).__name__}")
+    if not 2 <= int(num_levels) <= 256:
+        raise ValueError(f"8-bit level codes need 2 <= num_levels <= 256, got {int(num_levels)}")
+    return int(num_levels)
+
+
+CODES_MIN_BLOCKS = 1024  # k_codes_fold workgroups wanted before the share grows (4 per CU: one resident set)
+
+
+def _block_prefix(counts: np.ndarray, block: int = _lib.CODES_BLOCK) -> np.ndarray:
+    blocks = (np.asarray(counts, dtype=np.int64) + block - 1) // block
+    return np.concatenate([[0], np.cumsum(blocks)]).astype(np.int64)
+
+
+def encode_uniform_table(in_ptrs: np.ndarray, leaf_n: np.ndarray, keys: np.ndarray, num_levels: int,
+                         code_ptrs: np.ndarray, minmax: torch.Tensor, device: torch.device) -> None:
+    """k_encode_uniform over float32 rows in_ptrs [K, L] with keys [K, L, 2]: the statistics pass of
+    the fused round, then one launch writing the codes at code_ptrs [K, L] and minmax [K, L, 2]."""
+    K, L = in_ptrs.shape
+    ns = np.tile(np.asarray(leaf_n, dtype=np.int64), K)
+    _, qp = row_stats_table(in_ptrs.reshape(-1), ns, _lib.COMP_UNIFORM, device)
+    prefix = _block_prefix((ns + 1) // 2)
+    up = Upload()
+    o_in = up.add(np.ascontiguousarray(in_ptrs, dtype=np.uint64))
+    o_keys = up.add(np.ascontiguousarray(keys, dtype=np.uint32))
+    o_n, o_pre = up.add(ns), up.add(prefix)
+    o_codes = up.add(np.ascontiguousarray(code_ptrs, dtype=np.uint64))
+    base = up.commit(device)
+    _lib.call("fjcomp_encode_uniform", base + o_in, base + o_keys, qp.data_ptr(), K * L, base + o_n, base + o_pre,
+              int(prefix[-1]), int(num_levels), base + o_codes, minmax.data_ptr(), _stream(device))
+
+
+def encode_uniform(rows: List[List[torch.Tensor]], keys: np.ndarray, num_levels: int):
+    """Level codes of float32 rows [K][L] under keys [K, L, 2]: (codes [K][L] uint8 tensors shaped
+    like the leaves, minmax float32 [K, L, 2]); what quantized_mean(COMP_UNIFORM) decides."""
+    device = rows[0][0].device
+    in_ptrs = tree_util._ptr_table(rows, np.uint64)  # (rows may hold client 0's leaves only)
+    K, L = in_ptrs.shape
+    codes = [[torch.empty(x.shape, dtype=torch.uint8, device=device) for x in rows[0]] for _ in range(K)]
+    minmax = torch.empty(K, L, 2, dtype=torch.float32, device=device)
+    encode_uniform_table(in_ptrs, np.array([x.numel() for x in rows[0]], dtype=np.int64),
+                         keys, num_levels, np.array([[c.data_ptr() for c in r] for r in codes], dtype=np.uint64),
+                         minmax, device)
+    return codes, minmax
+
+
+class CodesFold:
+    """The device tables of one k_codes_fold launch shape (code pointers [K, L], leaf sizes, block
+    prefix, output pointers), uploaded once: :meth:`launch` uploads nothing, so it can be captured
+    into a graph, and every replay reads codes, minmax and weights afresh."""
+
+    def __init__(self, code_ptrs: np.ndarray, leaf_n: np.ndarray, out_ptrs: np.ndarray, device: torch.device):
+        self.K, self.L = code_ptrs.shape
+        self.device = device
+        leaf_n = np.ascontiguousarray(leaf_n, dtype=np.int64)
+        prefix, self.block = _block_prefix(leaf_n), _lib.CODES_BLOCK
+        if int(prefix[-1]) < CODES_MIN_BLOCKS:  # few codes in total: the small share fills the chip
+            prefix, self.block = _block_prefix(leaf_n, _lib.CODES_BLOCK_SMALL), _lib.CODES_BLOCK_SMALL
+        self.nblocks = int(prefix[-1])
+        self._up = Upload()
+        o = [self._up.add(np.ascontiguousarray(code_ptrs, dtype=np.uint64)), self._up.add(leaf_n),
+             self._up.add(prefix), self._up.add(np.ascontiguousarray(out_ptrs, dtype=np.uint64))]
+        base = self._up.commit(device)
+        self._codes, self._n, self._prefix, self._outs = (base + x for x in o)
+
+    def launch(self, minmax_ptr: int, w_ptr: int, scale: Optional[float], num_levels: int) -> None:
+        flags = _lib.SCALE if scale is not None else 0
+        _lib.call("fjcomp_codes_fold", self._codes, minmax_ptr, w_ptr, self.K, self.L, self._n, self._prefix,
+                  self.nblocks, self.block, int(num_levels), float(np.float32(scale if scale is not None else 1.0)), flags,
+                  self._outs, _stream(self.device))
+
+
+def codes_mean(codes: List[List[torch.Tensor]], minmax: torch.Tensor, w: np.ndarray, scale: Optional[float],
+               outs: List[torch.Tensor], num_levels: int) -> None:
+    """outs[l] = [scale *] sum_k fl(decode(codes[k][l], minmax[k, l]) * w_k): tree_mean over the
+    decoded deltas straight from the codes (minmax: float32 [K, L, 2] on the device)."""
+    device = outs[0].device
+    tables = CodesFold(np.array([[c.data_ptr() for c in r] for r in codes], dtype=np.uint64),
+                       np.array([c.numel() for c in codes[0]], dtype=np.int64),
+                       np.array([o.data_ptr() for o in outs], dtype=np.uint64), device)
+    w_dev = _lib.upload(torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)), device)
+    tables.launch(minmax.data_ptr(), w_dev.data_ptr(), scale, num_levels)
+
+
 def rademacher_words(keys: np.ndarray, ds: Sequence[int], device: torch.device,
                      block_pairs: int = 0) -> Tuple[torch.Tensor, np.ndarray]:
     """Sign bits for jobs (keys [J, 2], lengths ds): one word buffer, per-job word offsets.

@@ -48,6 +48,7 @@ TREE_ORDERED = 1 << 10  # FJTREE_ORDERED: norm combine by release/acquire atomic
 COMP_UNIFORM, COMP_TERNGRAD, COMP_BINARY = 1, 2, 3
 WHT_PLAIN, WHT_ROTATE, WHT_UNROTATE, WHT_UNROTATE_DRIVE = 0, 1, 2, 3
 STATS_CHUNK = 16384
+CODES_BLOCK, CODES_BLOCK_SMALL = 4096, 1024  # FJCOMP_CODES_BLOCK, FJCOMP_CODES_BLOCK_SMALL
 TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
@@ -153,6 +154,8 @@ _SIGNATURES = {
     "fjcomp_stats_combine": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "fjcomp_quant_fold": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _f32, _i32, _vp,
                                  _vp, _vp]),
+    "fjcomp_codes_fold": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "fjcomp_encode_uniform": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "fjcomp_wht_tiles": (_i64, [_i32, _i32]),
     "fjcomp_wht": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fjcomp_topk_workspace_bytes": (_i64, [_i64]),

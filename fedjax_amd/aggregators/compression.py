@@ -28,6 +28,7 @@ from __future__ import annotations
 
 import itertools
 import math
+from dataclasses import field as _field
 from typing import Any, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -313,6 +314,102 @@ def terngrad_quantizer(rng) -> aggregator.Aggregator:
     return aggregator.Aggregator(init, apply)
 
 
+# ----------------------------------------------------------------------------- transmitted form
+@dataclasses.dataclass
+class EncodedDelta:
+    """A uniformly quantized delta as a client transmits it: ``codes``, a pytree of uint8 device
+    tensors shaped like the delta's leaves (the level index of every element), ``minmax``, a
+    float32 ``[L, 2]`` tensor of every leaf's (amin, amax), and ``num_levels`` (2 .. 256). A code
+    ``c`` of leaf ``l`` stands for ``vmin + lev[c] * (vmax - vmin)``, ``lev[c] = f32(c) / f32(num_levels - 1)``,
+    in float32: the value ``uniform_stochastic_quantize`` returns (compression.py:84-97)."""
+    codes: Any
+    minmax: Any
+    num_levels: int = _field(metadata={"pytree_node": False})
+
+
+def _encoded_rows(deltas: Sequence[Any], num_levels: int, shapes=None):
+    """(treedef, codes [K][L], minmax [K]) of EncodedDelta clients after every check the kernels
+    rely on: uint8 codes, one structure and leaf shapes (``shapes``, default client 0's), float32
+    ``[L, 2]`` minmax, and ``num_levels`` everywhere."""
+    td, rows, mms = None, [], []
+    for k, d in enumerate(deltas):
+        if not isinstance(d, EncodedDelta):
+            raise TypeError(f"client {k}: expected an EncodedDelta, got {type(d).__name__}")
+        if C.check_num_levels(d.num_levels) != num_levels:
+            raise ValueError(f"client {k} was encoded with num_levels={d.num_levels}, expected {num_levels}")
+        if td is None:
+            leaves, td = pytree.flatten(d.codes)
+        else:
+            leaves = pytree.flatten_as(td, d.codes)
+        if shapes is None:
+            shapes = [tuple(x.shape) if isinstance(x, torch.Tensor) else None for x in leaves]
+        if len(leaves) != len(shapes):
+            raise ValueError(f"client {k} has {len(leaves)} leaves, expected {len(shapes)}")
+        for l, (x, s) in enumerate(zip(leaves, shapes)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+                raise TypeError(f"client {k} leaf {l}: codes must be uint8 tensors, got "
+                                f"{x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
+            if tuple(x.shape) != s:
+                raise ValueError(f"client {k} leaf {l} has shape {tuple(x.shape)}, expected {s}")
+        mm = d.minmax
+        if not isinstance(mm, torch.Tensor) or mm.dtype != torch.float32:
+            raise TypeError(f"client {k}: minmax must be a float32 tensor")
+        if tuple(mm.shape) != (len(shapes), 2):
+            raise ValueError(f"client {k}: minmax has shape {tuple(mm.shape)}, expected {(len(shapes), 2)}")
+        rows.append(leaves)
+        mms.append(mm)
+    return td, rows, mms
+
+
+def uniform_stochastic_encode_pytree(params: PyTree, num_levels: int, rng) -> EncodedDelta:
+    """The client side of :func:`encoded_mean_aggregator`: ``uniform_stochastic_quantize_pytree``'s
+    draws and decisions (leaf keys = split(rng, num_leaves)) kept as level indices, one byte per
+    element, instead of decoded float32 values."""
+    num_levels = C.check_num_levels(num_levels)
+    td, rows = _rows([params])
+    L = len(rows[0])
+    if not L:
+        return EncodedDelta(pytree.unflatten(td, []), torch.empty(0, 2, dtype=torch.float32), num_levels)
+    codes, minmax = C.encode_uniform(rows, random.split(rng, L).reshape(1, L, 2), num_levels)
+    return EncodedDelta(pytree.unflatten(td, codes[0]), minmax[0], num_levels)
+
+
+def encoded_mean_aggregator(num_levels: int) -> aggregator.Aggregator:
+    """The server side of a round whose clients transmit :class:`EncodedDelta`: ``apply`` takes
+    ``(client_id, EncodedDelta, weight)`` triples and returns ``tree_mean`` over the decoded deltas,
+    folded straight from the codes in one launch (a quarter of the float32 fold's bytes, no
+    decoded copy), and a :class:`CompressionState` whose ``num_bits`` grows as the reference's
+    ``uniform_stochastic_quantizer`` counts them. With clients encoded by
+    :func:`uniform_stochastic_encode_pytree` under that aggregator's keys the mean is bit for bit
+    its mean."""
+    num_levels = C.check_num_levels(num_levels)
+
+    def init():
+        return CompressionState(0.0, None)
+
+    def apply(clients_params_and_weights, aggregator_state):
+        deltas, weights = _consume(clients_params_and_weights)
+        agg, P, L = None, 0, 0
+        if deltas:
+            td, rows, mms = _encoded_rows(deltas, num_levels)
+            L = len(rows[0])
+            if L:
+                device = tree_util._find_device(rows[0])
+                rows = [[x.to(device).contiguous() for x in r] for r in rows]
+                P = sum(x.numel() for x in rows[0])
+                w, scale = _weights(weights)
+                outs = [torch.empty(x.shape, dtype=torch.float32, device=device) for x in rows[0]]
+                minmax = torch.stack([m.to(device) for m in mms])
+                C.codes_mean(rows, minmax, w, scale, outs, num_levels)
+                agg = pytree.unflatten(td, outs)
+            else:
+                agg = pytree.unflatten(td, [])
+        new_bits = _bits_per_param(math.log2(num_levels), P, L)
+        return agg, CompressionState(F32(aggregator_state.num_bits + new_bits), aggregator_state.rng)
+
+    return aggregator.Aggregator(init, apply)
+
+
 @dataclasses.dataclass
 class SparsifierState:
     """State of :func:`top_k_sparsifier`: the bits transmitted so far, ``0.0`` at first and a 0-d
@@ -352,7 +449,8 @@ def top_k_sparsifier(k) -> aggregator.Aggregator:
     return aggregator.Aggregator(init, apply)
 
 
-__all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier",
+__all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier", "EncodedDelta", "encoded_mean_aggregator",
+           "uniform_stochastic_encode_pytree",
            "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",
            "num_leaves", "rotated_uniform_stochastic_quantizer", "structured_drive_quantizer", "terngrad_quantize",
            "terngrad_quantize_pytree", "terngrad_quantizer", "uniform_stochastic_quantize",

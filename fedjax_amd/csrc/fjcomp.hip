@@ -1001,6 +1001,252 @@ __global__ __launch_bounds__(kWhtThreads) void k_wht(const fjcomp_wht_job* __res
   if (tile_stats) mm.store(reinterpret_cast<Partial*>(const_cast<fjcomp_stats*>(jb.stats)) + tix, tile_sums);
 }
 
+// ------------------------------------------------------------------ 8-bit level codes
+// A client that really transmits its uniformly quantized delta sends, per leaf, one byte per
+// element (the level index c < num_levels <= 256) and the pair (vmin, vmax). k_encode_uniform
+// produces that form with k_quant_fold's operator and draws; k_codes_fold is tree_mean over it.
+// 
+constexpr int kCThreads = 256;
+constexpr int kCPerLane = 16;  // consecutive codes a lane owns: one 16-byte load per client
+constexpr int kCPerLaneSmall = 4;  // ... of the small workgroup share: one 4-byte load
+constexpr int kCGroup = 4;     // clients whose codes and value tables are prepared one group ahead
+static_assert(kCThreads * kCPerLane == FJCOMP_CODES_BLOCK, "codes per workgroup");
+static_assert(kCThreads * kCPerLaneSmall == FJCOMP_CODES_BLOCK_SMALL, "codes per small workgroup");
+static_assert(kCThreads == 256, "a lane builds one entry of a 256-entry value table");
+
+// A lane's PER codes of one client, four to a word.
+template <int PER>
+struct CodeRun {
+  uint32_t v[PER / 4];
+};
+
+// The PER codes at p, of which `left` lie inside the leaf (the rest read as 0; left <= 0: none).
+// One PER-byte load when the lane's run is whole and aligned, else a byte at a time; no address
+// past the leaf's end is formed into a load either way.
+template <int PER>
+__device__ inline CodeRun<PER> load_codes(const uint8_t* __restrict__ p, int64_t left, bool aligned) {
+  CodeRun<PER> r;
+  if (aligned && left >= PER) {
+    if constexpr (PER == 16) {
+      const uint4 x = *reinterpret_cast<const uint4*>(p);
+      r.v[0] = x.x, r.v[1] = x.y, r.v[2] = x.z, r.v[3] = x.w;
+    } else {
+      static_assert(PER == 4, "a 16-byte or a 4-byte run");
+      r.v[0] = *reinterpret_cast<const uint32_t*>(p);
+    }
+    return r;
+  }
+#pragma unroll
+  for (int q = 0; q < PER / 4; ++q) r.v[q] = 0u;
+#pragma unroll
+  for (int j = 0; j < PER; ++j)
+    if (j < left) r.v[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+  return r;
+}
+
+__device__ inline void store_codes(uint8_t* __restrict__ p, int64_t left, const uint32_t (&v)[4]) {
+  if (left >= kCPerLane && ((uintptr_t)p & 15) == 0) {
+    *reinterpret_cast<uint4*>(p) = uint4{v[0], v[1], v[2], v[3]};
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kCPerLane; ++j)
+    if (j < left) p[j] = (uint8_t)(v[j >> 2] >> (8 * (j & 3)));
+}
+
+// One client's PER codes through its value table T (LDS, 256 entries: T[c] = fl(decode(c) * w_k),
+// the entries past the top level repeating it, so a byte is its own clamped address): the fold
+// is a table read and an add per code, pairs of elements as packed adds.
+template <bool FIRST, int PER>
+__device__ inline void fold_codes(const float* T, const CodeRun<PER>& x, f2 (&s)[PER / 2]) {
+#pragma unroll
+  for (int q = 0; q < PER / 4; ++q) {
+    const uint32_t wd = x.v[q];
+    const f2 t0 = {T[wd & 0xffu], T[(wd >> 8) & 0xffu]};
+    const f2 t1 = {T[(wd >> 16) & 0xffu], T[wd >> 24]};
+    s[2 * q] = FIRST ? t0 : s[2 * q] + t0;
+    s[2 * q + 1] = FIRST ? t1 : s[2 * q + 1] + t1;
+  }
+}
+
+// Workgroup b folds 256 * PER consecutive codes of one leaf over all K clients; lane t owns PER
+// of them and keeps their PER running sums in registers (PER = 16; 4 when the larger share
+// would leave most of the chip without a workgroup: every workgroup walks all K clients, a
+// chain of K dependent steps that only more workgroups can overlap). Per client the decode and the weight are
+// not done per code: the workgroup builds the client's table of all 256 possible values
+//   T_k[c] = fl(fl(vmin_k + fl(lev[min(c, top)] * range_k)) * w_k),   lev[j] = RN_f32(j / top)
+// one entry a lane (lane t holds lev[min(t, top)] in a register: div_by's correctly rounded
+// quotient, the v_floor / v_ceil of UniformQ), so every product and sum of the reference's
+// sequence is formed once per (client, workgroup, level) with the same roundings, and a code
+// costs its byte extract, one LDS read and one add. Tables and codes of the next kCGroup
+// clients are prepared while this group folds (two LDS table sets, two register sets, one
+// barrier per group).
+template <int PER>
+__global__ __launch_bounds__(kCThreads) void k_codes_fold(const uint8_t* const* __restrict__ code_ptrs,
+                                                           const float* __restrict__ minmax,
+                                                           const float* __restrict__ w, int64_t K, int64_t L,
+                                                           const int64_t* __restrict__ leaf_n,
+                                                           const int64_t* __restrict__ prefix, int top,
+                                                           double rcp_top, float scale, int flags,
+                                                           float* const* __restrict__ out_ptrs) {
+  const int64_t b = blockIdx.x;
+  const int64_t l = find_segment(prefix, L, b);
+  const int tid = threadIdx.x;
+  const int64_t n = leaf_n[l];
+  const int64_t e0 = ((b - prefix[l]) * kCThreads + tid) * PER;
+  const int64_t left = n - e0;  // this lane's codes inside the leaf (<= 0: none)
+  const float lev = div_by((float)(tid < top ? tid : top), rcp_top);
+  struct CClient {
+    uint64_t ptr;
+    float vmin, range, w;
+    uint32_t aligned;
+  };
+  __shared__ CClient qc[kCThreads];
+  __shared__ float tab[2][kCGroup][256];
+  constexpr int G = kCGroup;
+  f2 s[PER / 2];
+#pragma unroll
+  for (int q = 0; q < PER / 2; ++q) s[q] = f2{0.0f, 0.0f};
+  // clients j .. j+G-1 of the staged chunk (those < jn; the rest repeat the last one)
+  auto fetch = [&](int64_t j, int64_t jn, CodeRun<PER> (&x)[G]) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const CClient& e = qc[j + u < jn ? j + u : jn - 1];
+      x[u] = load_codes<PER>(reinterpret_cast<const uint8_t*>(e.ptr) + e0, left, e.aligned != 0);
+    }
+  };
+  auto build = [&](int64_t j, int64_t jn, float (&T)[G][256]) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (j + u >= jn) break;  // workgroup-uniform
+      const CClient& e = qc[j + u];
+      T[u][tid] = (e.vmin + lev * e.range) * e.w;
+    }
+  };
+  auto fold = [&](int64_t kc, int64_t j, int64_t jn, const CodeRun<PER> (&x)[G], const float (&T)[G][256]) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (j + u >= jn) break;  // workgroup-uniform
+      if (kc + j + u == 0)
+        fold_codes<true>(T[u], x[u], s);
+      else
+        fold_codes<false>(T[u], x[u], s);
+    }
+  };
+  for (int64_t kc = 0; kc < K; kc += kCThreads) {
+    const int64_t jn = K - kc < kCThreads ? K - kc : kCThreads;
+    // (every wave left the previous chunk's last group at that group's barrier)
+    if (tid < jn) {
+      const int64_t k = kc + tid, row = k * L + l;
+      CClient e;
+      e.ptr = (uint64_t)code_ptrs[row];
+      e.vmin = minmax[2 * row];
+      e.range = minmax[2 * row + 1] - e.vmin;
+      e.w = w[k];
+      e.aligned = (e.ptr & (PER - 1)) == 0;
+      qc[tid] = e;
+    }
+    __syncthreads();
+    CodeRun<PER> xa[G], xb[G];
+    fetch(0, jn, xa);
+    build(0, jn, tab[0]);
+    __syncthreads();
+    for (int64_t j = 0; j < jn; j += 2 * G) {
+      if (j + G < jn) {
+        fetch(j + G, jn, xb);
+        build(j + G, jn, tab[1]);
+      }
+      fold(kc, j, jn, xa, tab[0]);
+      __syncthreads();
+      if (j + G >= jn) break;
+      if (j + 2 * G < jn) {
+        fetch(j + 2 * G, jn, xa);
+        build(j + 2 * G, jn, tab[0]);
+      }
+      fold(kc, j + G, jn, xb, tab[1]);
+      __syncthreads();
+    }
+  }
+  if (left <= 0) return;
+  if (flags & FJAGG_SCALE) {
+#pragma unroll
+    for (int q = 0; q < PER / 2; ++q) s[q] = s[q] * scale;
+  }
+  float* __restrict__ o = out_ptrs[l] + e0;
+  if (left >= PER && ((uintptr_t)o & 15) == 0) {
+#pragma unroll
+    for (int q = 0; q < PER / 4; ++q)
+      reinterpret_cast<float4*>(o)[q] = float4{s[2 * q].x, s[2 * q].y, s[2 * q + 1].x, s[2 * q + 1].y};
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < PER / 2; ++q) {
+    if (2 * q < left) o[2 * q] = s[q].x;
+    if (2 * q + 1 < left) o[2 * q + 1] = s[q].y;
+  }
+}
+
+// 16 floats at p, of which `left` are inside the row (the rest read as 0).
+__device__ inline void load_floats(const float* __restrict__ p, int64_t left, float (&v)[kCPerLane]) {
+  if (left >= kCPerLane && ((uintptr_t)p & 15) == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 t = reinterpret_cast<const float4*>(p)[q];
+      v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kCPerLane; ++j) v[j] = j < left ? p[j] : 0.0f;
+}
+
+// The client side of k_codes_fold: row r = (client, leaf) of n floats becomes n level codes and
+// (vmin, vmax). The element pair (i, i + h), h = ceil(n / 2), is one threefry2x32 call, as in
+// k_quant_fold (same counters, same bits -> uniform map, the same operator object, whose
+// *level outputs are the codes), so a lane owns 16 consecutive pairs: elements [i0, i0 + 16)
+// of the first half and [h + i0, h + i0 + 16) of the second, each run loaded as four float4
+// and stored as one 16-byte word where its address allows, element by element where not.
+__global__ __launch_bounds__(kCThreads) void k_encode_uniform(UniformTQ quant, const float* const* __restrict__ in_ptrs,
+                                                               const uint32_t* __restrict__ keys,
+                                                               const fjcomp_qparams* __restrict__ qps, int64_t R,
+                                                               const int64_t* __restrict__ row_n,
+                                                               const int64_t* __restrict__ prefix,
+                                                               uint8_t* const* __restrict__ code_ptrs,
+                                                               float* __restrict__ minmax) {
+  const int64_t b = blockIdx.x;
+  const int64_t r = find_segment(prefix, R, b);
+  extern __shared__ __attribute__((aligned(16))) unsigned char qtab[];
+  quant.build(qtab);
+  const int64_t n = row_n[r], h = (n + 1) >> 1;
+  const int64_t i0 = (b - prefix[r]) * FJCOMP_CODES_BLOCK + (int64_t)threadIdx.x * kCPerLane;
+  const fjcomp_qparams p = qps[r];
+  if (b == prefix[r] && threadIdx.x == 0) {
+    minmax[2 * r] = p.vmin;
+    minmax[2 * r + 1] = p.vmax;
+  }
+  const int64_t na = h - i0, nb = n - h - i0;  // this lane's elements inside each half
+  if (na <= 0) return;
+  const uint32_t k0 = keys[2 * r], k1 = keys[2 * r + 1], k2 = k0 ^ k1 ^ 0x1BD11BDAu;
+  float va[kCPerLane], vb[kCPerLane];
+  load_floats(in_ptrs[r] + i0, na, va);
+  load_floats(in_ptrs[r] + h + i0, nb, vb);
+  uint32_t ca[4] = {0u, 0u, 0u, 0u}, cb[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < kCPerLane; ++j) {
+    const int64_t i = i0 + j;
+    uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(j < nb ? i + h : 0);
+    threefry_k(k0, k1, k2, c0, c1);
+    const f2 uu = {__uint_as_float(__builtin_amdgcn_alignbit(0x7fu, c0, 9u)),
+                   __uint_as_float(__builtin_amdgcn_alignbit(0x7fu, c1, 9u))};
+    float l0, l1;
+    quant.pair(f2{va[j], vb[j]}, uu - 1.0f, p, &l0, &l1);  // levels are integers in [0, top]
+    ca[j >> 2] |= (uint32_t)l0 << (8 * (j & 3));
+    cb[j >> 2] |= (uint32_t)l1 << (8 * (j & 3));
+  }
+  store_codes(code_ptrs[r] + i0, na, ca);
+  store_codes(code_ptrs[r] + h + i0, nb, cb);
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 void host_split(const uint32_t key[2], int64_t num, uint32_t* out) {
@@ -1210,6 +1456,53 @@ int fjcomp_quant_fold(int method, const float* const* in_ptrs, const uint32_t* k
     return fail(FJAGG_EINVAL, "quant_fold: unknown method %d", method);
   }
   return check_launch("k_quant_fold");
+}
+
+int fjcomp_codes_fold(const uint8_t* const* code_ptrs, const float* minmax, const float* w, int64_t K, int64_t L,
+                      const int64_t* leaf_n, const int64_t* block_prefix, int64_t nblocks, int block_codes,
+                      int num_levels, float scale, int flags, float* const* out_ptrs, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (K < 1 || L < 0 || nblocks < 0 || nblocks > INT32_MAX)
+    return fail(FJAGG_EINVAL, "codes_fold: bad sizes (K=%lld L=%lld nblocks=%lld)", (long long)K, (long long)L,
+                (long long)nblocks);
+  if (num_levels < 2 || num_levels > 256)
+    return fail(FJAGG_EINVAL, "codes_fold: num_levels=%d outside [2, 256]", num_levels);
+  if (block_codes != FJCOMP_CODES_BLOCK && block_codes != FJCOMP_CODES_BLOCK_SMALL)
+    return fail(FJAGG_EINVAL, "codes_fold: block_codes=%d (%d or %d)", block_codes, FJCOMP_CODES_BLOCK,
+                FJCOMP_CODES_BLOCK_SMALL);
+  if (flags & ~FJAGG_SCALE) return fail(FJAGG_EINVAL, "codes_fold: unsupported flags %#x", flags);
+  if (L && (!code_ptrs || !minmax || !w || !leaf_n || !block_prefix || !out_ptrs))
+    return fail(FJAGG_EINVAL, "codes_fold: null table");
+  if (!L || !nblocks) return FJAGG_OK;
+  const int top = num_levels - 1;
+  const double rcp_top = 1.0 / (double)(float)top;
+  if (block_codes == FJCOMP_CODES_BLOCK)
+    hipLaunchKernelGGL(k_codes_fold<kCPerLane>, dim3((unsigned)nblocks), dim3(kCThreads), 0, as_stream(stream),
+                       code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top, rcp_top, scale, flags, out_ptrs);
+  else
+    hipLaunchKernelGGL(k_codes_fold<kCPerLaneSmall>, dim3((unsigned)nblocks), dim3(kCThreads), 0, as_stream(stream),
+                       code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top, rcp_top, scale, flags, out_ptrs);
+  return check_launch("k_codes_fold");
+}
+
+int fjcomp_encode_uniform(const float* const* in_ptrs, const uint32_t* keys, const fjcomp_qparams* qparams, int64_t R,
+                          const int64_t* row_n, const int64_t* block_prefix, int64_t nblocks, int num_levels,
+                          uint8_t* const* code_ptrs, float* minmax, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (R < 0 || nblocks < 0 || nblocks > INT32_MAX)
+    return fail(FJAGG_EINVAL, "encode_uniform: bad sizes (R=%lld nblocks=%lld)", (long long)R, (long long)nblocks);
+  if (num_levels < 2 || num_levels > 256)
+    return fail(FJAGG_EINVAL, "encode_uniform: num_levels=%d outside [2, 256]", num_levels);
+  if (R && (!in_ptrs || !keys || !qparams || !row_n || !block_prefix || !code_ptrs || !minmax))
+    return fail(FJAGG_EINVAL, "encode_uniform: null table");
+  if (!R || !nblocks) return FJAGG_OK;
+  UniformTQ q{};  // k_quant_fold's operator for these level counts, built the same way
+  q.lm1 = (float)(num_levels - 1);
+  q.num_levels = num_levels;
+  q.rcp_lm1 = 1.0 / (double)q.lm1;
+  hipLaunchKernelGGL(k_encode_uniform, dim3((unsigned)nblocks), dim3(kCThreads), UniformTQ::lds_bytes(num_levels),
+                     as_stream(stream), q, in_ptrs, keys, qparams, R, row_n, block_prefix, code_ptrs, minmax);
+  return check_launch("k_encode_uniform");
 }
 
 int64_t fjcomp_wht_tiles(int log2d, int pass) {

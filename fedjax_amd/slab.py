@@ -859,4 +859,131 @@ class ClientDeltaSlab:
         return torch.sqrt(kernels.l2_squared_dense(self.rows))
 
 
-__all__ = ["ClientDeltaSlab"]
+class CodeSlab:
+    """K uniformly quantized client deltas in their transmitted form: one byte per
+    element, the level index of ``uniform_stochastic_quantize``, as one uint8 ``[K, row_stride]``
+    device tensor — row k is client k's leaves in jax flatten order, every leaf starting on a
+    16-byte boundary — and ``minmax``, float32 ``[K, L, 2]``, every (client, leaf)'s (amin, amax).
+    :meth:`mean` is ``tree_mean`` over the decoded deltas folded straight from the codes: a quarter
+    of the bytes :meth:`ClientDeltaSlab.mean` reads, and no decoded copy."""
+
+    def __init__(self, template: PyTree, num_clients: int, num_levels: int, *,
+                 device: Optional[torch.device] = None):
+        from fedjax_amd import _compress
+
+        self.num_levels = _compress.check_num_levels(num_levels)
+        leaves, self.treedef = pytree.flatten(template)
+        self.shapes = [tuple(tree_util._to_tensor(x).shape) for x in leaves]
+        self.sizes = [int(np.prod(s, dtype=np.int64)) for s in self.shapes]
+        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)  # of the float32 mean
+        self.num_params = int(self.offsets[-1])
+        padded = (np.array(self.sizes, dtype=np.int64) + 15) // 16 * 16
+        self.code_offsets = np.concatenate([[0], np.cumsum(padded)]).astype(np.int64)
+        self.row_stride = max(16, int(self.code_offsets[-1]))
+        self.num_clients = int(num_clients)
+        self.device = device if device is not None else tree_util._default_device()
+        self.storage = torch.zeros(self.num_clients, self.row_stride, dtype=torch.uint8, device=self.device)
+        self.minmax = torch.zeros(self.num_clients, len(self.sizes), 2, dtype=torch.float32, device=self.device)
+        self._tables = self._weights = None
+
+    def _code_ptrs(self) -> np.ndarray:
+        rows = np.arange(self.num_clients, dtype=np.int64)[:, None] * self.row_stride
+        return (self.storage.data_ptr() + rows + self.code_offsets[None, :-1]).astype(np.uint64)
+
+    def client(self, k: int):
+        """Client k as an :class:`~fedjax_amd.aggregators.EncodedDelta` of views into the slab."""
+        from fedjax_amd.aggregators.compression import EncodedDelta
+
+        row = self.storage[k]
+        views = [row[o:o + n].view(s) for o, n, s in zip(self.code_offsets[:-1], self.sizes, self.shapes)]
+        return EncodedDelta(pytree.unflatten(self.treedef, views), self.minmax[k], self.num_levels)
+
+    def set_client(self, k: int, encoded) -> None:
+        """Copy one client's :class:`~fedjax_amd.aggregators.EncodedDelta` (device or host tensors)
+        into row k, after checking its dtype, structure, shapes and ``num_levels``."""
+        from fedjax_amd.aggregators.compression import _encoded_rows
+
+        _, rows, mms = _encoded_rows([encoded], self.num_levels, self.shapes)
+        dst = self.client(k)
+        for d, src in zip(pytree.leaves_of(dst.codes), pytree.flatten_as(self.treedef, encoded.codes)):
+            d.copy_(src, non_blocking=True)
+        dst.minmax.copy_(mms[0], non_blocking=True)
+
+    def encode_from(self, delta_slab: ClientDeltaSlab, rng) -> "CodeSlab":
+        """Fill all K rows from a float32 :class:`ClientDeltaSlab` of the same template in one encoder
+        launch (after the statistics pass). ``rng`` is the round's key as
+        ``uniform_stochastic_quantizer`` uses it after its split: client keys are
+        ``PRNGSequence(rng).take(K)``, leaf keys ``split_many(client_keys, L)``, so :meth:`mean` then
+        equals that aggregator's mean of the same deltas bit for bit."""
+        from fedjax_amd import _compress, random
+
+        if not isinstance(delta_slab, ClientDeltaSlab) or delta_slab.dtype != torch.float32:
+            raise TypeError("encode_from needs a float32 ClientDeltaSlab")
+        if delta_slab.shapes != self.shapes or delta_slab.num_clients != self.num_clients:
+            raise ValueError("encode_from needs a slab of the same template and number of clients")
+        K, L = self.num_clients, len(self.sizes)
+        if not K or not L:
+            return self
+        keys = random.split_many(random.PRNGSequence(rng).take(K), L)
+        rows = np.arange(K, dtype=np.int64)[:, None] * delta_slab.row_stride
+        in_ptrs = (delta_slab.storage.data_ptr() + 4 * (rows + delta_slab.offsets[None, :-1])).astype(np.uint64)
+        _compress.encode_uniform_table(in_ptrs, np.array(self.sizes, dtype=np.int64), keys, self.num_levels,
+                                       self._code_ptrs(), self.minmax, self.device)
+        return self
+
+    def _kept(self, name: str, key, make):
+        """A device table that stays with the slab (``make()`` uploads it, which a capture refuses):
+        reused while ``key`` is the same, so after one eager call :meth:`mean` uploads nothing. A
+        call on another stream waits for the upload through an event, as in
+        :meth:`ClientDeltaSlab.grouped_mean` (whose notes on capture apply)."""
+        cached = getattr(self, name)
+        stream = torch.cuda.current_stream(self.device)
+        if cached is not None and cached[0] == key:
+            if torch.cuda.is_current_stream_capturing():  # the graph reads it on every replay
+                self._captured = getattr(self, "_captured", []) + [cached[1]]
+            elif stream != cached[2]:
+                stream.wait_event(cached[3])
+            return cached[1]
+        value = make()
+        uploaded = torch.cuda.Event()
+        uploaded.record(stream)
+        setattr(self, name, (key, value, stream, uploaded))
+        return value
+
+    def mean(self, weights: Sequence, *, out: Optional[torch.Tensor] = None) -> PyTree:
+        """Weighted mean of the K decoded rows — ``tree_mean`` with the reference's W and f32(1/W)
+        over the values the codes stand for, bit for bit ``uniform_stochastic_quantizer``'s mean
+        when the rows come from :meth:`encode_from` — in one launch that reads every code once.
+        Returns the template's pytree of float32 views into ``out`` (flat float32,
+        ``num_params`` elements; allocated when ``None``). The pointer tables and the weight
+        vector are uploaded on the first call and kept: a later call with the same ``out`` and
+        the same weights uploads nothing, so it can be captured into a graph, and each replay
+        reads codes and ``minmax`` afresh."""
+        from fedjax_amd import _compress
+
+        if len(weights) != self.num_clients:
+            raise ValueError(f"need {self.num_clients} weights, got {len(weights)}")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
+            raise TypeError("out must be a float32 tensor")
+        if out is not None and (out.dim() != 1 or out.numel() != self.num_params or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of {self.num_params} elements")
+        W, hw = 0.0, []
+        for x in weights:
+            x = tree_util._host_weight(x)
+            hw.append(np.float32(x))
+            W += x
+        scale = float(np.float32(tree_util._inverse(W)))
+        if out is None:
+            out = torch.empty(self.num_params, dtype=torch.float32, device=self.device)
+        views = [out[o:o + n].view(s) for o, n, s in zip(self.offsets[:-1], self.sizes, self.shapes)]
+        if self.num_params and self.num_clients:
+            w = np.array(hw, dtype=np.float32)
+            w_dev = self._kept("_weights", w.tobytes(), lambda: _lib.upload(torch.from_numpy(w), self.device))
+            tables = self._kept("_tables", out.data_ptr(), lambda: _compress.CodesFold(
+                self._code_ptrs(), np.array(self.sizes, dtype=np.int64),
+                (out.data_ptr() + 4 * self.offsets[:-1]).astype(np.uint64), self.device))
+            tables.launch(self.minmax.data_ptr(), w_dev.data_ptr(), scale, self.num_levels)
+        return pytree.unflatten(self.treedef, views)
+
+
+__all__ = ["ClientDeltaSlab", "CodeSlab"]

@@ -164,6 +164,35 @@ int fjcomp_quant_fold(int method, const float* const* in_ptrs, const uint32_t* k
                       int num_levels, float scale, int flags, float* const* out_ptrs, int32_t* hist,
                       void* stream);
 
+/* ---- uniform quantizer, transmitted form: 8-bit level codes ----
+ * For 2 <= num_levels <= 256 a (client, leaf) row of n elements is n uint8 codes c < num_levels
+ * and the float32 pair (vmin, vmax). With top = num_levels - 1 and range = fl(vmax - vmin) a code
+ * decodes to exactly the value fjcomp_quant_fold's UNIFORM operator folds:
+ *   q(c) = fl(vmin + fl(lev[min(c, top)] * range)),   lev[j] = RN_f32(j / top)
+ * (two roundings, no multiply-add; non-finite vmin / range propagate; a code above top counts as
+ * top). A workgroup takes block_codes consecutive codes (fold: FJCOMP_CODES_BLOCK, or
+ * FJCOMP_CODES_BLOCK_SMALL when the larger share would leave most of the chip idle; same bits)
+ * or FJCOMP_CODES_BLOCK element pairs (encode) of one row.
+ *
+ * fjcomp_codes_fold: tree_mean straight from the codes, one launch, no decoded temporary:
+ *   s = fl(q_0 * w_0);  s = fl(s + fl(q_k * w_k)) in client order;  out[l] = SCALE ? fl(s * scale) : s
+ * code_ptrs[K*L] (client-major, any alignment), minmax[K*L][2], w[K], leaf_n[L] (0 allowed),
+ * block_prefix[L+1] the running sum of ceil(leaf_n / block_codes) and nblocks its last
+ * entry, out_ptrs[L]: all device. flags: FJAGG_SCALE only.
+ *
+ * fjcomp_encode_uniform: rows in_ptrs[R] of row_n[R] >= 1 floats with keys[R][2] and the
+ * qparams[R] of fjcomp_row_stats (UNIFORM) become codes at code_ptrs[R] and minmax[R][2], with
+ * fjcomp_quant_fold's draws and decisions: folding the codes gives that call's bits.
+ * block_prefix[R+1] is the running sum of ceil(ceil(row_n / 2) / FJCOMP_CODES_BLOCK). */
+#define FJCOMP_CODES_BLOCK 4096
+#define FJCOMP_CODES_BLOCK_SMALL 1024
+int fjcomp_codes_fold(const uint8_t* const* code_ptrs, const float* minmax, const float* w, int64_t K, int64_t L,
+                      const int64_t* leaf_n, const int64_t* block_prefix, int64_t nblocks, int block_codes,
+                      int num_levels, float scale, int flags, float* const* out_ptrs, void* stream);
+int fjcomp_encode_uniform(const float* const* in_ptrs, const uint32_t* keys, const fjcomp_qparams* qparams,
+                          int64_t R, const int64_t* row_n, const int64_t* block_prefix, int64_t nblocks,
+                          int num_levels, uint8_t* const* code_ptrs, float* minmax, void* stream);
+
 /* Walsh-Hadamard jobs. pass_prefix[npass][J+1] (device): per pass, the running sum of
  * that job's tiles in the pass (0 if the job has fewer passes); pass_tiles[npass] (host):
  * the totals. A job of d = 2^log2d has one pass for log2d <= 13, else
