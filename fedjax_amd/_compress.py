@@ -218,6 +218,23 @@ def check_num_levels(num_levels) -> int:
     return int(num_levels)
 
 
+def check_bits(bits, num_levels: int) -> int:
+    """Bits per transmitted code: 8 (a byte each, the default) or a packed 1, 2 or 4 with
+    ``2**bits >= num_levels`` (a bool is refused)."""
+    if isinstance(bits, (bool, np.bool_)) or not isinstance(bits, (int, np.integer)):
+        raise TypeError(f"bits must be 1, 2, 4 or 8, not {type(bits).__name__}")
+    if int(bits) not in (1, 2, 4, 8):
+        raise ValueError(f"bits must be 1, 2, 4 or 8, got {int(bits)}")
+    if (1 << int(bits)) < num_levels:
+        raise ValueError(f"{int(bits)}-bit codes hold {1 << int(bits)} levels, fewer than num_levels={num_levels}")
+    return int(bits)
+
+
+def packed_bytes(n, bits: int):
+    """Bytes of ``n`` codes of ``bits`` bits each: ``ceil(n * bits / 8)`` (``n`` an int or an array)."""
+    return (n * bits + 7) // 8
+
+
 CODES_MIN_BLOCKS = 1024  # k_codes_fold workgroups wanted before the share grows (4 per CU: one resident set)
 
 
@@ -227,9 +244,10 @@ def _block_prefix(counts: np.ndarray, block: int = _lib.CODES_BLOCK) -> np.ndarr
 
 
 def encode_uniform_table(in_ptrs: np.ndarray, leaf_n: np.ndarray, keys: np.ndarray, num_levels: int,
-                         code_ptrs: np.ndarray, minmax: torch.Tensor, device: torch.device) -> None:
+                         code_ptrs: np.ndarray, minmax: torch.Tensor, device: torch.device, bits: int = 8) -> None:
     """k_encode_uniform over float32 rows in_ptrs [K, L] with keys [K, L, 2]: the statistics pass of
-    the fused round, then one launch writing the codes at code_ptrs [K, L] and minmax [K, L, 2]."""
+    the fused round, then one launch writing the codes at code_ptrs [K, L] and minmax [K, L, 2]
+    (``bits`` < 8: k_encode_uniform_packed, rows of ``packed_bytes(leaf_n, bits)`` bytes)."""
     K, L = in_ptrs.shape
     ns = np.tile(np.asarray(leaf_n, dtype=np.int64), K)
     _, qp = row_stats_table(in_ptrs.reshape(-1), ns, _lib.COMP_UNIFORM, device)
@@ -240,36 +258,47 @@ def encode_uniform_table(in_ptrs: np.ndarray, leaf_n: np.ndarray, keys: np.ndarr
     o_n, o_pre = up.add(ns), up.add(prefix)
     o_codes = up.add(np.ascontiguousarray(code_ptrs, dtype=np.uint64))
     base = up.commit(device)
-    _lib.call("fjcomp_encode_uniform", base + o_in, base + o_keys, qp.data_ptr(), K * L, base + o_n, base + o_pre,
-              int(prefix[-1]), int(num_levels), base + o_codes, minmax.data_ptr(), _stream(device))
+    if bits == 8:
+        _lib.call("fjcomp_encode_uniform", base + o_in, base + o_keys, qp.data_ptr(), K * L, base + o_n, base + o_pre,
+                  int(prefix[-1]), int(num_levels), base + o_codes, minmax.data_ptr(), _stream(device))
+    else:
+        _lib.call("fjcomp_encode_uniform_packed", base + o_in, base + o_keys, qp.data_ptr(), K * L, base + o_n,
+                  base + o_pre, int(prefix[-1]), int(bits), int(num_levels), base + o_codes, minmax.data_ptr(),
+                  _stream(device))
 
 
-def encode_uniform(rows: List[List[torch.Tensor]], keys: np.ndarray, num_levels: int):
+def encode_uniform(rows: List[List[torch.Tensor]], keys: np.ndarray, num_levels: int, bits: int = 8):
     """Level codes of float32 rows [K][L] under keys [K, L, 2]: (codes [K][L] uint8 tensors shaped
-    like the leaves, minmax float32 [K, L, 2]); what quantized_mean(COMP_UNIFORM) decides."""
+    like the leaves, or 1-D of ``packed_bytes(n, bits)`` bytes when ``bits`` < 8, minmax float32
+    [K, L, 2]); what quantized_mean(COMP_UNIFORM) decides."""
     device = rows[0][0].device
     in_ptrs = tree_util._ptr_table(rows, np.uint64)  # (rows may hold client 0's leaves only)
     K, L = in_ptrs.shape
-    codes = [[torch.empty(x.shape, dtype=torch.uint8, device=device) for x in rows[0]] for _ in range(K)]
+    codes = [[torch.empty(x.shape if bits == 8 else packed_bytes(x.numel(), bits), dtype=torch.uint8, device=device)
+              for x in rows[0]] for _ in range(K)]
     minmax = torch.empty(K, L, 2, dtype=torch.float32, device=device)
     encode_uniform_table(in_ptrs, np.array([x.numel() for x in rows[0]], dtype=np.int64),
                          keys, num_levels, np.array([[c.data_ptr() for c in r] for r in codes], dtype=np.uint64),
-                         minmax, device)
+                         minmax, device, bits)
     return codes, minmax
 
 
 class CodesFold:
     """The device tables of one k_codes_fold launch shape (code pointers [K, L], leaf sizes, block
     prefix, output pointers), uploaded once: :meth:`launch` uploads nothing, so it can be captured
-    into a graph, and every replay reads codes, minmax and weights afresh."""
+    into a graph, and every replay reads codes, minmax and weights afresh. ``bits`` < 8: the rows
+    are packed and the launch is k_codes_fold_packed's (``leaf_n`` still counts elements)."""
 
-    def __init__(self, code_ptrs: np.ndarray, leaf_n: np.ndarray, out_ptrs: np.ndarray, device: torch.device):
+    def __init__(self, code_ptrs: np.ndarray, leaf_n: np.ndarray, out_ptrs: np.ndarray, device: torch.device,
+                 bits: int = 8):
         self.K, self.L = code_ptrs.shape
-        self.device = device
+        self.device, self.bits = device, int(bits)
         leaf_n = np.ascontiguousarray(leaf_n, dtype=np.int64)
-        prefix, self.block = _block_prefix(leaf_n), _lib.CODES_BLOCK
+        large, small = ((_lib.CODES_BLOCK, _lib.CODES_BLOCK_SMALL) if bits == 8 else
+                        (_lib.PACKED_BLOCK, _lib.PACKED_BLOCK_SMALL))
+        prefix, self.block = _block_prefix(leaf_n, large), large
         if int(prefix[-1]) < CODES_MIN_BLOCKS:  # few codes in total: the small share fills the chip
-            prefix, self.block = _block_prefix(leaf_n, _lib.CODES_BLOCK_SMALL), _lib.CODES_BLOCK_SMALL
+            prefix, self.block = _block_prefix(leaf_n, small), small
         self.nblocks = int(prefix[-1])
         self._up = Upload()
         o = [self._up.add(np.ascontiguousarray(code_ptrs, dtype=np.uint64)), self._up.add(leaf_n),
@@ -279,19 +308,25 @@ class CodesFold:
 
     def launch(self, minmax_ptr: int, w_ptr: int, scale: Optional[float], num_levels: int) -> None:
         flags = _lib.SCALE if scale is not None else 0
-        _lib.call("fjcomp_codes_fold", self._codes, minmax_ptr, w_ptr, self.K, self.L, self._n, self._prefix,
-                  self.nblocks, self.block, int(num_levels), float(np.float32(scale if scale is not None else 1.0)), flags,
-                  self._outs, _stream(self.device))
+        scale = float(np.float32(scale if scale is not None else 1.0))
+        if self.bits == 8:
+            _lib.call("fjcomp_codes_fold", self._codes, minmax_ptr, w_ptr, self.K, self.L, self._n, self._prefix,
+                      self.nblocks, self.block, int(num_levels), scale, flags, self._outs, _stream(self.device))
+        else:
+            _lib.call("fjcomp_codes_fold_packed", self._codes, minmax_ptr, w_ptr, self.K, self.L, self._n,
+                      self._prefix, self.nblocks, self.block, self.bits, int(num_levels), scale, flags, self._outs,
+                      _stream(self.device))
 
 
 def codes_mean(codes: List[List[torch.Tensor]], minmax: torch.Tensor, w: np.ndarray, scale: Optional[float],
-               outs: List[torch.Tensor], num_levels: int) -> None:
+               outs: List[torch.Tensor], num_levels: int, bits: int = 8) -> None:
     """outs[l] = [scale *] sum_k fl(decode(codes[k][l], minmax[k, l]) * w_k): tree_mean over the
-    decoded deltas straight from the codes (minmax: float32 [K, L, 2] on the device)."""
+    decoded deltas straight from the codes (minmax: float32 [K, L, 2] on the device). The leaf
+    sizes are those of ``outs``: with ``bits`` < 8 a code leaf is its packed bytes."""
     device = outs[0].device
     tables = CodesFold(np.array([[c.data_ptr() for c in r] for r in codes], dtype=np.uint64),
-                       np.array([c.numel() for c in codes[0]], dtype=np.int64),
-                       np.array([o.data_ptr() for o in outs], dtype=np.uint64), device)
+                       np.array([o.numel() for o in outs], dtype=np.int64),
+                       np.array([o.data_ptr() for o in outs], dtype=np.uint64), device, bits)
     w_dev = _lib.upload(torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)), device)
     tables.launch(minmax.data_ptr(), w_dev.data_ptr(), scale, num_levels)
 

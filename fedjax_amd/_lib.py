@@ -49,6 +49,7 @@ COMP_UNIFORM, COMP_TERNGRAD, COMP_BINARY = 1, 2, 3
 WHT_PLAIN, WHT_ROTATE, WHT_UNROTATE, WHT_UNROTATE_DRIVE = 0, 1, 2, 3
 STATS_CHUNK = 16384
 CODES_BLOCK, CODES_BLOCK_SMALL = 4096, 1024  # FJCOMP_CODES_BLOCK, FJCOMP_CODES_BLOCK_SMALL
+PACKED_BLOCK, PACKED_BLOCK_SMALL = 4096, 2048  # FJCOMP_PACKED_BLOCK, FJCOMP_PACKED_BLOCK_SMALL
 TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
@@ -156,6 +157,9 @@ _SIGNATURES = {
                                  _vp, _vp]),
     "fjcomp_codes_fold": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),
     "fjcomp_encode_uniform": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "fjcomp_codes_fold_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp,
+                                        _vp]),
+    "fjcomp_encode_uniform_packed": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "fjcomp_wht_tiles": (_i64, [_i32, _i32]),
     "fjcomp_wht": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "fjcomp_topk_workspace_bytes": (_i64, [_i64]),

@@ -321,36 +321,89 @@ class EncodedDelta:
     tensors shaped like the delta's leaves (the level index of every element), ``minmax``, a
     float32 ``[L, 2]`` tensor of every leaf's (amin, amax), and ``num_levels`` (2 .. 256). A code
     ``c`` of leaf ``l`` stands for ``vmin + lev[c] * (vmax - vmin)``, ``lev[c] = f32(c) / f32(num_levels - 1)``,
-    in float32: the value ``uniform_stochastic_quantize`` returns (compression.py:84-97)."""
+    in float32: the value ``uniform_stochastic_quantize`` returns (compression.py:84-97).
+
+    ``bits`` is 8 (that form) or 1, 2 or 4 with ``2**bits >= num_levels``: every code leaf is then a
+    1-D uint8 tensor of ``ceil(n * bits / 8)`` bytes, element ``i`` in byte ``i // (8 // bits)`` at
+    bit offset ``bits * (i % (8 // bits))``, low bits first (:func:`pack_codes`), and ``shapes``
+    carries the delta's leaf shapes in flatten order, which the packed bytes no longer tell."""
     codes: Any
     minmax: Any
     num_levels: int = _field(metadata={"pytree_node": False})
+    bits: int = _field(default=8, metadata={"pytree_node": False})
+    shapes: Optional[Tuple[Tuple[int, ...], ...]] = _field(default=None, metadata={"pytree_node": False})
 
 
-def _encoded_rows(deltas: Sequence[Any], num_levels: int, shapes=None):
-    """(treedef, codes [K][L], minmax [K]) of EncodedDelta clients after every check the kernels
-    rely on: uint8 codes, one structure and leaf shapes (``shapes``, default client 0's), float32
-    ``[L, 2]`` minmax, and ``num_levels`` everywhere."""
+def pack_codes(codes_u8: torch.Tensor, bits: int) -> torch.Tensor:
+    """The packed form of uint8 level codes below ``2**bits`` (``bits`` 1, 2 or 4): a 1-D uint8
+    tensor of ``ceil(n * bits / 8)`` bytes, element ``i`` of the flattened codes in byte
+    ``i // (8 // bits)`` at bit offset ``bits * (i % (8 // bits))``, padding bits zero. Plain torch
+    ops, for interchange and tests (the encoder writes this form itself)."""
+    if C.check_bits(bits, 2) == 8:
+        raise ValueError("pack_codes packs to 1, 2 or 4 bits")
+    if not isinstance(codes_u8, torch.Tensor) or codes_u8.dtype != torch.uint8:
+        raise TypeError("codes must be a uint8 tensor")
+    per = 8 // bits
+    flat = codes_u8.reshape(-1)
+    fields = torch.zeros(C.packed_bytes(flat.numel(), bits) * per, dtype=torch.int32, device=flat.device)
+    fields[:flat.numel()] = flat & ((1 << bits) - 1)
+    shifts = bits * torch.arange(per, dtype=torch.int32, device=flat.device)
+    return (fields.view(-1, per) << shifts).sum(dim=1).to(torch.uint8)
+
+
+def unpack_codes(packed: torch.Tensor, n: int, bits: int) -> torch.Tensor:
+    """The ``n`` uint8 codes of a :func:`pack_codes` buffer (its padding bits are ignored)."""
+    if C.check_bits(bits, 2) == 8:
+        raise ValueError("unpack_codes unpacks 1, 2 or 4 bits")
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise TypeError("packed codes must be a 1-D uint8 tensor")
+    if packed.numel() != C.packed_bytes(int(n), bits):
+        raise ValueError(f"{n} codes of {bits} bits are {C.packed_bytes(int(n), bits)} bytes, got {packed.numel()}")
+    shifts = bits * torch.arange(8 // bits, dtype=torch.int32, device=packed.device)
+    fields = (packed.to(torch.int32)[:, None] >> shifts) & ((1 << bits) - 1)
+    return fields.reshape(-1)[:int(n)].to(torch.uint8)
+
+
+def _template_shapes(template) -> Tuple[Tuple[int, ...], ...]:
+    return tuple(tuple(tree_util._to_tensor(x).shape) for x in pytree.leaves_of(template))
+
+
+def _encoded_rows(deltas: Sequence[Any], num_levels: int, shapes=None, bits: int = 8):
+    """(treedef, codes [K][L], minmax [K], shapes) of EncodedDelta clients after every check the
+    kernels rely on: uint8 codes, one structure and leaf shapes (``shapes``, default client 0's),
+    float32 ``[L, 2]`` minmax, and ``num_levels`` and ``bits`` everywhere. With ``bits`` < 8 the
+    shapes are the deltas' ``shapes`` fields and a code leaf is 1-D, ``ceil(n * bits / 8)`` bytes."""
     td, rows, mms = None, [], []
     for k, d in enumerate(deltas):
         if not isinstance(d, EncodedDelta):
             raise TypeError(f"client {k}: expected an EncodedDelta, got {type(d).__name__}")
         if C.check_num_levels(d.num_levels) != num_levels:
             raise ValueError(f"client {k} was encoded with num_levels={d.num_levels}, expected {num_levels}")
+        if C.check_bits(d.bits, num_levels) != bits:
+            raise ValueError(f"client {k} was encoded with bits={d.bits}, expected {bits}")
         if td is None:
             leaves, td = pytree.flatten(d.codes)
         else:
             leaves = pytree.flatten_as(td, d.codes)
+        if bits < 8:
+            if d.shapes is None:
+                raise ValueError(f"client {k}: packed codes need the leaf shapes in EncodedDelta.shapes")
+            mine = tuple(tuple(int(v) for v in sh) for sh in d.shapes)
+            if shapes is None:
+                shapes = mine
+            if mine != tuple(tuple(sh) for sh in shapes):
+                raise ValueError(f"client {k} has leaf shapes {mine}, expected {tuple(shapes)}")
         if shapes is None:
             shapes = [tuple(x.shape) if isinstance(x, torch.Tensor) else None for x in leaves]
         if len(leaves) != len(shapes):
             raise ValueError(f"client {k} has {len(leaves)} leaves, expected {len(shapes)}")
-        for l, (x, s) in enumerate(zip(leaves, shapes)):
+        for l, (x, sh) in enumerate(zip(leaves, shapes)):
             if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
                 raise TypeError(f"client {k} leaf {l}: codes must be uint8 tensors, got "
                                 f"{x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
-            if tuple(x.shape) != s:
-                raise ValueError(f"client {k} leaf {l} has shape {tuple(x.shape)}, expected {s}")
+            want = sh if bits == 8 else (C.packed_bytes(int(np.prod(sh, dtype=np.int64)), bits),)
+            if tuple(x.shape) != want:
+                raise ValueError(f"client {k} leaf {l} has shape {tuple(x.shape)}, expected {want}")
         mm = d.minmax
         if not isinstance(mm, torch.Tensor) or mm.dtype != torch.float32:
             raise TypeError(f"client {k}: minmax must be a float32 tensor")
@@ -358,31 +411,38 @@ def _encoded_rows(deltas: Sequence[Any], num_levels: int, shapes=None):
             raise ValueError(f"client {k}: minmax has shape {tuple(mm.shape)}, expected {(len(shapes), 2)}")
         rows.append(leaves)
         mms.append(mm)
-    return td, rows, mms
+    return td, rows, mms, shapes
 
 
-def uniform_stochastic_encode_pytree(params: PyTree, num_levels: int, rng) -> EncodedDelta:
+def uniform_stochastic_encode_pytree(params: PyTree, num_levels: int, rng, bits: int = 8) -> EncodedDelta:
     """The client side of :func:`encoded_mean_aggregator`: ``uniform_stochastic_quantize_pytree``'s
     draws and decisions (leaf keys = split(rng, num_leaves)) kept as level indices, one byte per
-    element, instead of decoded float32 values."""
+    element, instead of decoded float32 values; with ``bits`` 1, 2 or 4 the same indices packed
+    (:class:`EncodedDelta`), written in that form by the encoder."""
     num_levels = C.check_num_levels(num_levels)
+    bits = C.check_bits(bits, num_levels)
     td, rows = _rows([params])
     L = len(rows[0])
+    shapes = None if bits == 8 else tuple(tuple(x.shape) for x in rows[0])
     if not L:
-        return EncodedDelta(pytree.unflatten(td, []), torch.empty(0, 2, dtype=torch.float32), num_levels)
-    codes, minmax = C.encode_uniform(rows, random.split(rng, L).reshape(1, L, 2), num_levels)
-    return EncodedDelta(pytree.unflatten(td, codes[0]), minmax[0], num_levels)
+        return EncodedDelta(pytree.unflatten(td, []), torch.empty(0, 2, dtype=torch.float32), num_levels, bits, shapes)
+    codes, minmax = C.encode_uniform(rows, random.split(rng, L).reshape(1, L, 2), num_levels, bits)
+    return EncodedDelta(pytree.unflatten(td, codes[0]), minmax[0], num_levels, bits, shapes)
 
 
-def encoded_mean_aggregator(num_levels: int) -> aggregator.Aggregator:
+def encoded_mean_aggregator(num_levels: int, bits: int = 8, template: Optional[PyTree] = None) -> aggregator.Aggregator:
     """The server side of a round whose clients transmit :class:`EncodedDelta`: ``apply`` takes
     ``(client_id, EncodedDelta, weight)`` triples and returns ``tree_mean`` over the decoded deltas,
     folded straight from the codes in one launch (a quarter of the float32 fold's bytes, no
     decoded copy), and a :class:`CompressionState` whose ``num_bits`` grows as the reference's
     ``uniform_stochastic_quantizer`` counts them. With clients encoded by
     :func:`uniform_stochastic_encode_pytree` under that aggregator's keys the mean is bit for bit
-    its mean."""
+    its mean. ``bits`` 1, 2 or 4: the clients' codes are packed and folded in that form (an
+    eighth to a thirty-second of the float32 bytes); the leaf shapes are the deltas' ``shapes``
+    fields, checked against ``template``'s (a pytree of the model's leaves) when one is given."""
     num_levels = C.check_num_levels(num_levels)
+    bits = C.check_bits(bits, num_levels)
+    expect = None if template is None else _template_shapes(template)
 
     def init():
         return CompressionState(0.0, None)
@@ -391,16 +451,16 @@ def encoded_mean_aggregator(num_levels: int) -> aggregator.Aggregator:
         deltas, weights = _consume(clients_params_and_weights)
         agg, P, L = None, 0, 0
         if deltas:
-            td, rows, mms = _encoded_rows(deltas, num_levels)
+            td, rows, mms, shapes = _encoded_rows(deltas, num_levels, expect, bits)
             L = len(rows[0])
             if L:
                 device = tree_util._find_device(rows[0])
                 rows = [[x.to(device).contiguous() for x in r] for r in rows]
-                P = sum(x.numel() for x in rows[0])
                 w, scale = _weights(weights)
-                outs = [torch.empty(x.shape, dtype=torch.float32, device=device) for x in rows[0]]
+                outs = [torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes]
+                P = sum(x.numel() for x in outs)
                 minmax = torch.stack([m.to(device) for m in mms])
-                C.codes_mean(rows, minmax, w, scale, outs, num_levels)
+                C.codes_mean(rows, minmax, w, scale, outs, num_levels, bits)
                 agg = pytree.unflatten(td, outs)
             else:
                 agg = pytree.unflatten(td, [])
@@ -450,7 +510,7 @@ def top_k_sparsifier(k) -> aggregator.Aggregator:
 
 
 __all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier", "EncodedDelta", "encoded_mean_aggregator",
-           "uniform_stochastic_encode_pytree",
+           "uniform_stochastic_encode_pytree", "pack_codes", "unpack_codes",
            "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",
            "num_leaves", "rotated_uniform_stochastic_quantizer", "structured_drive_quantizer", "terngrad_quantize",
            "terngrad_quantize_pytree", "terngrad_quantizer", "uniform_stochastic_quantize",

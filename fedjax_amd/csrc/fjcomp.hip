@@ -1247,7 +1247,355 @@ __global__ __launch_bounds__(kCThreads) void k_encode_uniform(UniformTQ quant, c
   store_codes(code_ptrs[r] + h + i0, nb, cb);
 }
 
+// ------------------------------------------------------------------ 1-, 2- and 4-bit packed level codes
+// The same transmitted form with E = 8 / BITS codes to a byte (element i: byte i / E, bit offset
+// BITS * (i % E), low bits first; include/fjcomp.h).
+constexpr int kPPerLane = 16;      // consecutive elements a lane owns: an 8-, 4- or 2-byte load per client
+constexpr int kPPerLaneSmall = 8;  // ... of the small workgroup share: a 4-, 2- or 1-byte load
+static_assert(kCThreads * kPPerLane == FJCOMP_PACKED_BLOCK, "elements per workgroup");
+static_assert(kCThreads * kPPerLaneSmall == FJCOMP_PACKED_BLOCK_SMALL, "elements per small workgroup");
+
+// A lane's NB packed bytes of one client, four to a word.
+template <int NB>
+struct PackedRun {
+  uint32_t v[(NB + 3) / 4];
+};
+
+// The NB bytes at p, of which `bleft` lie inside the packed leaf (the rest read as 0; bleft <= 0:
+// none). One NB-byte load when the run is whole and aligned, else a byte at a time; no address
+// past the leaf's last byte is formed into a load either way.
+template <int NB>
+__device__ inline PackedRun<NB> load_packed(const uint8_t* __restrict__ p, int64_t bleft, bool aligned) {
+  PackedRun<NB> r;
+  if (aligned && bleft >= NB) {
+    if constexpr (NB == 16) {
+      const uint4 x = *reinterpret_cast<const uint4*>(p);
+      r.v[0] = x.x, r.v[1] = x.y, r.v[2] = x.z, r.v[3] = x.w;
+    } else if constexpr (NB == 8) {
+      const uint2 x = *reinterpret_cast<const uint2*>(p);
+      r.v[0] = x.x, r.v[1] = x.y;
+    } else if constexpr (NB == 4) {
+      r.v[0] = *reinterpret_cast<const uint32_t*>(p);
+    } else if constexpr (NB == 2) {
+      r.v[0] = *reinterpret_cast<const uint16_t*>(p);
+    } else {
+      static_assert(NB == 1, "a 16-, 8-, 4-, 2- or 1-byte run");
+      r.v[0] = *p;
+    }
+    return r;
+  }
+#pragma unroll
+  for (int q = 0; q < (NB + 3) / 4; ++q) r.v[q] = 0u;
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (j < bleft) r.v[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+  return r;
+}
+
+// What a byte stands for, in one LDS entry: the byte stays the table index, and entry b holds
+// the E values of its fields, low field first (4 bits: a pair, 2 bits: four values).
+template <int BITS>
+struct PackedEntry;
+template <>
+struct PackedEntry<4> {
+  typedef f2 type;
+};
+template <>
+struct PackedEntry<2> {
+  typedef float4 type;
+};
+template <>
+struct PackedEntry<1> {
+  typedef float type;  // no table: a bit selects between the client's two values
+};
+
+// One client's NB bytes into the lane's 8 * NB / BITS sums: one LDS read per byte (8 bytes for
+// 4 bits, 16 for 2), every value a packed add; for 1 bit a select between v0 and v1 per code.
+template <bool FIRST, int BITS, int NB>
+__device__ inline void fold_packed(const typename PackedEntry<BITS>::type* T, float v0, float v1,
+                                   const PackedRun<NB>& x, f2 (&s)[NB * 4 / BITS]) {
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    const uint32_t by = (x.v[q >> 2] >> (8 * (q & 3))) & 0xffu;
+    if constexpr (BITS == 4) {
+      const f2 t = T[by];
+      s[q] = FIRST ? t : s[q] + t;
+    } else if constexpr (BITS == 2) {
+      const float4 t = T[by];
+      const f2 lo = {t.x, t.y}, hi = {t.z, t.w};
+      s[2 * q] = FIRST ? lo : s[2 * q] + lo;
+      s[2 * q + 1] = FIRST ? hi : s[2 * q + 1] + hi;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f2 t = {(by >> (2 * j)) & 1u ? v1 : v0, (by >> (2 * j + 1)) & 1u ? v1 : v0};
+        s[4 * q + j] = FIRST ? t : s[4 * q + j] + t;
+      }
+    }
+  }
+}
+
+// k_codes_fold over packed rows: the same work split (workgroup b: 256 * PER consecutive
+// elements of one leaf, lane t: PER of them, their sums in registers), the same client staging
+// and group-ahead preparation, the same per-client values
+//   T_k[c] = fl(fl(vmin_k + fl(lev[min(c, top)] * range_k)) * w_k),   lev[j] = RN_f32(j / top)
+// but a table entry is what a whole byte stands for: lane t builds entry t of every client from
+// the E levels lev[min(field_j(t), top)] it keeps in registers (each value the reference's three
+// operations, formed in the lane that stores it: replicating 2^BITS products through LDS would
+// cost a second barrier a group, through the wave a shuffle per value, both more than the three
+// operations they save). With 1 bit there is no table: the two values of a client are formed
+// once when the client is staged and every lane reads them as wave-uniform operands.
+template <int BITS, int PER>
+__global__ __launch_bounds__(kCThreads) void k_codes_fold_packed(const uint8_t* const* __restrict__ code_ptrs,
+                                                                  const float* __restrict__ minmax,
+                                                                  const float* __restrict__ w, int64_t K, int64_t L,
+                                                                  const int64_t* __restrict__ leaf_n,
+                                                                  const int64_t* __restrict__ prefix, int top,
+                                                                  double rcp_top, float scale, int flags,
+                                                                  float* const* __restrict__ out_ptrs) {
+  constexpr int E = 8 / BITS, NB = PER / E, G = kCGroup;
+  static_assert(PER % E == 0 && (NB & (NB - 1)) == 0 && NB <= 16, "a lane owns whole bytes, one load");
+  typedef typename PackedEntry<BITS>::type Entry;
+  const int64_t b = blockIdx.x;
+  const int64_t l = find_segment(prefix, L, b);
+  const int tid = threadIdx.x;
+  const int64_t n = leaf_n[l];
+  const int64_t e0 = ((b - prefix[l]) * kCThreads + tid) * PER;
+  const int64_t left = n - e0;                       // this lane's elements inside the leaf (<= 0: none)
+  const int64_t boff = e0 / E;                       // its first byte in the packed leaf
+  const int64_t bleft = (n + E - 1) / E - boff;      // its bytes inside the packed leaf (<= 0: none)
+  float lev[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    const int field = (tid >> (BITS * j)) & ((1 << BITS) - 1);
+    lev[j] = div_by((float)(field < top ? field : top), rcp_top);
+  }
+  struct PClient {
+    uint64_t ptr;
+    float vmin, range, w;
+    uint32_t aligned;
+    float v0, v1;  // 1 bit: the values of codes 0 and 1
+  };
+  __shared__ PClient qc[kCThreads];
+  __shared__ Entry tab[2][G][BITS == 1 ? 1 : 256];
+  f2 s[PER / 2];
+#pragma unroll
+  for (int q = 0; q < PER / 2; ++q) s[q] = f2{0.0f, 0.0f};
+  // clients j .. j+G-1 of the staged chunk (those < jn; the rest repeat the last one)
+  auto fetch = [&](int64_t j, int64_t jn, PackedRun<NB> (&x)[G]) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const PClient& e = qc[j + u < jn ? j + u : jn - 1];
+      x[u] = load_packed<NB>(reinterpret_cast<const uint8_t*>(e.ptr) + boff, bleft, e.aligned != 0);
+    }
+  };
+  auto build = [&](int64_t j, int64_t jn, Entry (&T)[G][BITS == 1 ? 1 : 256]) {
+    if constexpr (BITS != 1) {
+#pragma unroll
+      for (int u = 0; u < G; ++u) {
+        if (j + u >= jn) break;  // workgroup-uniform
+        const PClient& e = qc[j + u];
+        const f2 lo = (e.vmin + f2{lev[0], lev[1]} * e.range) * e.w;
+        if constexpr (BITS == 4) {
+          T[u][tid] = lo;
+        } else {
+          const f2 hi = (e.vmin + f2{lev[2], lev[3]} * e.range) * e.w;
+          T[u][tid] = float4{lo.x, lo.y, hi.x, hi.y};
+        }
+      }
+    }
+  };
+  auto fold = [&](int64_t kc, int64_t j, int64_t jn, const PackedRun<NB> (&x)[G],
+                  const Entry (&T)[G][BITS == 1 ? 1 : 256]) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (j + u >= jn) break;  // workgroup-uniform
+      float v0 = 0.0f, v1 = 0.0f;
+      if constexpr (BITS == 1) v0 = qc[j + u].v0, v1 = qc[j + u].v1;
+      if (kc + j + u == 0)
+        fold_packed<true, BITS, NB>(T[u], v0, v1, x[u], s);
+      else
+        fold_packed<false, BITS, NB>(T[u], v0, v1, x[u], s);
+    }
+  };
+  for (int64_t kc = 0; kc < K; kc += kCThreads) {
+    const int64_t jn = K - kc < kCThreads ? K - kc : kCThreads;
+    // (every wave left the previous chunk's last group at that group's barrier)
+    if (tid < jn) {
+      const int64_t k = kc + tid, row = k * L + l;
+      PClient e;
+      e.ptr = (uint64_t)code_ptrs[row];
+      e.vmin = minmax[2 * row];
+      e.range = minmax[2 * row + 1] - e.vmin;
+      e.w = w[k];
+      e.aligned = (e.ptr & (NB - 1)) == 0;
+      e.v0 = (e.vmin + div_by(0.0f, rcp_top) * e.range) * e.w;
+      e.v1 = (e.vmin + div_by((float)(top < 1 ? top : 1), rcp_top) * e.range) * e.w;
+      qc[tid] = e;
+    }
+    __syncthreads();
+    PackedRun<NB> xa[G], xb[G];
+    fetch(0, jn, xa);
+    build(0, jn, tab[0]);
+    __syncthreads();
+    for (int64_t j = 0; j < jn; j += 2 * G) {
+      if (j + G < jn) {
+        fetch(j + G, jn, xb);
+        build(j + G, jn, tab[1]);
+      }
+      fold(kc, j, jn, xa, tab[0]);
+      __syncthreads();
+      if (j + G >= jn) break;
+      if (j + 2 * G < jn) {
+        fetch(j + 2 * G, jn, xa);
+        build(j + 2 * G, jn, tab[0]);
+      }
+      fold(kc, j + G, jn, xb, tab[1]);
+      __syncthreads();
+    }
+  }
+  if (left <= 0) return;
+  if (flags & FJAGG_SCALE) {
+#pragma unroll
+    for (int q = 0; q < PER / 2; ++q) s[q] = s[q] * scale;
+  }
+  float* __restrict__ o = out_ptrs[l] + e0;
+  if (left >= PER && ((uintptr_t)o & 15) == 0) {
+#pragma unroll
+    for (int q = 0; q < PER / 4; ++q)
+      reinterpret_cast<float4*>(o)[q] = float4{s[2 * q].x, s[2 * q].y, s[2 * q + 1].x, s[2 * q + 1].y};
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < PER / 2; ++q) {
+    if (2 * q < left) o[2 * q] = s[q].x;
+    if (2 * q + 1 < left) o[2 * q + 1] = s[q].y;
+  }
+}
+
+// NBW bytes of a lane's 16 packed codes, the low `count` of them inside the row: one store where
+// the address allows and all are, else whole bytes one at a time.
+template <int NBW>
+__device__ inline void store_packed(uint8_t* __restrict__ p, int64_t count, uint64_t bits) {
+  if (count <= 0) return;
+  if (count >= NBW && ((uintptr_t)p & (NBW - 1)) == 0) {
+    if constexpr (NBW == 8) {
+      *reinterpret_cast<uint2*>(p) = uint2{(uint32_t)bits, (uint32_t)(bits >> 32)};
+    } else if constexpr (NBW == 4) {
+      *reinterpret_cast<uint32_t*>(p) = (uint32_t)bits;
+    } else {
+      static_assert(NBW == 2, "16 codes of 4, 2 or 1 bits");
+      *reinterpret_cast<uint16_t*>(p) = (uint16_t)bits;
+    }
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < NBW; ++q)
+    if (q < count) p[q] = (uint8_t)(bits >> (8 * q));
+}
+
+// k_encode_uniform with the codes packed E = 8 / BITS to a byte: the same pairs (i, i + h), draws
+// and operator, a lane still owning 16 consecutive pairs, but owning output BYTES, each written
+// whole by one lane. With r = h % E:
+//   first half   the lane's whole bytes below byte h / E (its first-half codes, 16 / E bytes);
+//   second half  the bytes whose lowest element h + p has p in the lane's pairs. When r != 0
+//                they start s = E - r pairs into the lane's run and end s pairs into the next
+//                lane's, whose second-half codes this lane draws again (s <= E - 1 more Threefry
+//                calls a lane; its own first s second-half codes go to the lane before);
+//   byte h / E   (r != 0: r first-half codes, then s second-half codes) by the lane of pair 0,
+//                which draws the first-half codes of pairs h - r .. h - 1 again.
+// Fields past the row's last element are written as 0.
+template <int BITS>
+__global__ __launch_bounds__(kCThreads) void k_encode_uniform_packed(
+    UniformTQ quant, const float* const* __restrict__ in_ptrs, const uint32_t* __restrict__ keys,
+    const fjcomp_qparams* __restrict__ qps, int64_t R, const int64_t* __restrict__ row_n,
+    const int64_t* __restrict__ prefix, uint8_t* const* __restrict__ code_ptrs, float* __restrict__ minmax) {
+  constexpr int E = 8 / BITS, NBW = kCPerLane / E;
+  const int64_t b = blockIdx.x;
+  const int64_t row = find_segment(prefix, R, b);
+  extern __shared__ __attribute__((aligned(16))) unsigned char qtab[];
+  quant.build(qtab);
+  const int64_t n = row_n[row], h = (n + 1) >> 1, hb = n - h;  // hb: elements of the second half
+  const int64_t i0 = (b - prefix[row]) * FJCOMP_CODES_BLOCK + (int64_t)threadIdx.x * kCPerLane;
+  const fjcomp_qparams p = qps[row];
+  if (i0 == 0) {
+    minmax[2 * row] = p.vmin;
+    minmax[2 * row + 1] = p.vmax;
+  }
+  const int64_t na = h - i0, nb = hb - i0;  // this lane's elements inside each half
+  if (na <= 0) return;
+  const uint32_t k0 = keys[2 * row], k1 = keys[2 * row + 1], k2 = k0 ^ k1 ^ 0x1BD11BDAu;
+  const float* __restrict__ in = in_ptrs[row];
+  uint8_t* __restrict__ out = code_ptrs[row];
+  // the levels of pair i from its two elements (the second reads as 0 and counts as absent
+  // when i >= hb, as in k_encode_uniform)
+  auto levels = [&](int64_t i, float a, float c, uint32_t* l0, uint32_t* l1) {
+    uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i < hb ? i + h : 0);
+    threefry_k(k0, k1, k2, c0, c1);
+    const f2 uu = {__uint_as_float(__builtin_amdgcn_alignbit(0x7fu, c0, 9u)),
+                   __uint_as_float(__builtin_amdgcn_alignbit(0x7fu, c1, 9u))};
+    float f0, f1;
+    quant.pair(f2{a, c}, uu - 1.0f, p, &f0, &f1);  // levels are integers in [0, top]
+    *l0 = (uint32_t)f0 & ((1u << BITS) - 1u);
+    *l1 = (uint32_t)f1 & ((1u << BITS) - 1u);
+  };
+  float va[kCPerLane], vb[kCPerLane];
+  load_floats(in + i0, na, va);
+  load_floats(in + h + i0, nb, vb);
+  uint64_t pa = 0, lo = 0;  // the lane's 16 first-half and 16 second-half codes, pair j at bit BITS * j
+#pragma unroll
+  for (int j = 0; j < kCPerLane; ++j) {
+    uint32_t l0, l1;
+    levels(i0 + j, va[j], vb[j], &l0, &l1);
+    pa |= (uint64_t)l0 << (BITS * j);
+    lo |= (uint64_t)(j < nb ? l1 : 0u) << (BITS * j);
+  }
+  store_packed<NBW>(out + i0 / E, (na < kCPerLane ? na : kCPerLane) / E, pa);
+  const int r = (int)(h % E), s = r ? E - r : 0;
+  uint64_t pb = lo;
+  if (s) {  // row-uniform
+    uint64_t ext = 0;
+#pragma unroll
+    for (int q = 0; q < E - 1; ++q) {
+      const int64_t i = i0 + kCPerLane + q;
+      if (q < s && i < hb) {
+        uint32_t l0, l1;
+        levels(i, in[i], in[h + i], &l0, &l1);
+        ext |= (uint64_t)l1 << (BITS * q);
+      }
+    }
+    pb = (lo >> (BITS * s)) | (ext << (BITS * (kCPerLane - s)));
+  }
+  store_packed<NBW>(out + (h + i0 + s) / E, (nb - s + E - 1) / E, pb);
+  if (i0 == 0 && r) {  // the byte both halves share
+    uint32_t sb = (uint32_t)(lo & ((1ull << (BITS * s)) - 1ull)) << (BITS * r);
+#pragma unroll
+    for (int q = 0; q < E - 1; ++q) {
+      const int64_t i = h - r + q;
+      if (q < r) {
+        uint32_t l0, l1;
+        levels(i, in[i], i < hb ? in[h + i] : 0.0f, &l0, &l1);
+        sb |= l0 << (BITS * q);
+      }
+    }
+    out[h / E] = (uint8_t)sb;
+  }
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+template <int BITS>
+void launch_codes_fold_packed(int block_codes, int64_t nblocks, hipStream_t s, const uint8_t* const* code_ptrs,
+                                     const float* minmax, const float* w, int64_t K, int64_t L, const int64_t* leaf_n,
+                                     const int64_t* block_prefix, int top, double rcp_top, float scale, int flags,
+                                     float* const* out_ptrs) {
+  if (block_codes == FJCOMP_PACKED_BLOCK)
+    hipLaunchKernelGGL((k_codes_fold_packed<BITS, kPPerLane>), dim3((unsigned)nblocks), dim3(kCThreads), 0, s,
+                       code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top, rcp_top, scale, flags, out_ptrs);
+  else
+    hipLaunchKernelGGL((k_codes_fold_packed<BITS, kPPerLaneSmall>), dim3((unsigned)nblocks), dim3(kCThreads), 0, s,
+                       code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top, rcp_top, scale, flags, out_ptrs);
+}
 
 void host_split(const uint32_t key[2], int64_t num, uint32_t* out) {
   // threefry_2x32(key, iota(2*num)).reshape(num, 2): flat = [y0 | y1]
@@ -1503,6 +1851,72 @@ int fjcomp_encode_uniform(const float* const* in_ptrs, const uint32_t* keys, con
   hipLaunchKernelGGL(k_encode_uniform, dim3((unsigned)nblocks), dim3(kCThreads), UniformTQ::lds_bytes(num_levels),
                      as_stream(stream), q, in_ptrs, keys, qparams, R, row_n, block_prefix, code_ptrs, minmax);
   return check_launch("k_encode_uniform");
+}
+
+int fjcomp_codes_fold_packed(const uint8_t* const* code_ptrs, const float* minmax, const float* w, int64_t K,
+                             int64_t L, const int64_t* leaf_n, const int64_t* block_prefix, int64_t nblocks,
+                             int block_codes, int bits, int num_levels, float scale, int flags,
+                             float* const* out_ptrs, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (K < 1 || L < 0 || nblocks < 0 || nblocks > INT32_MAX)
+    return fail(FJAGG_EINVAL, "codes_fold_packed: bad sizes (K=%lld L=%lld nblocks=%lld)", (long long)K, (long long)L,
+                (long long)nblocks);
+  if (bits != 1 && bits != 2 && bits != 4) return fail(FJAGG_EINVAL, "codes_fold_packed: bits=%d (1, 2 or 4)", bits);
+  if (num_levels < 2 || num_levels > (1 << bits))
+    return fail(FJAGG_EINVAL, "codes_fold_packed: num_levels=%d outside [2, %d]", num_levels, 1 << bits);
+  if (block_codes != FJCOMP_PACKED_BLOCK && block_codes != FJCOMP_PACKED_BLOCK_SMALL)
+    return fail(FJAGG_EINVAL, "codes_fold_packed: block_codes=%d (%d or %d)", block_codes, FJCOMP_PACKED_BLOCK,
+                FJCOMP_PACKED_BLOCK_SMALL);
+  if (flags & ~FJAGG_SCALE) return fail(FJAGG_EINVAL, "codes_fold_packed: unsupported flags %#x", flags);
+  if (L && (!code_ptrs || !minmax || !w || !leaf_n || !block_prefix || !out_ptrs))
+    return fail(FJAGG_EINVAL, "codes_fold_packed: null table");
+  if (!L || !nblocks) return FJAGG_OK;
+  const int top = num_levels - 1;
+  const double rcp_top = 1.0 / (double)(float)top;
+  hipStream_t s = as_stream(stream);
+  if (bits == 4)
+    launch_codes_fold_packed<4>(block_codes, nblocks, s, code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top,
+                                rcp_top, scale, flags, out_ptrs);
+  else if (bits == 2)
+    launch_codes_fold_packed<2>(block_codes, nblocks, s, code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top,
+                                rcp_top, scale, flags, out_ptrs);
+  else
+    launch_codes_fold_packed<1>(block_codes, nblocks, s, code_ptrs, minmax, w, K, L, leaf_n, block_prefix, top,
+                                rcp_top, scale, flags, out_ptrs);
+  return check_launch("k_codes_fold_packed");
+}
+
+int fjcomp_encode_uniform_packed(const float* const* in_ptrs, const uint32_t* keys, const fjcomp_qparams* qparams,
+                                 int64_t R, const int64_t* row_n, const int64_t* block_prefix, int64_t nblocks,
+                                 int bits, int num_levels, uint8_t* const* code_ptrs, float* minmax, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (R < 0 || nblocks < 0 || nblocks > INT32_MAX)
+    return fail(FJAGG_EINVAL, "encode_uniform_packed: bad sizes (R=%lld nblocks=%lld)", (long long)R,
+                (long long)nblocks);
+  if (bits != 1 && bits != 2 && bits != 4)
+    return fail(FJAGG_EINVAL, "encode_uniform_packed: bits=%d (1, 2 or 4)", bits);
+  if (num_levels < 2 || num_levels > (1 << bits))
+    return fail(FJAGG_EINVAL, "encode_uniform_packed: num_levels=%d outside [2, %d]", num_levels, 1 << bits);
+  if (R && (!in_ptrs || !keys || !qparams || !row_n || !block_prefix || !code_ptrs || !minmax))
+    return fail(FJAGG_EINVAL, "encode_uniform_packed: null table");
+  if (!R || !nblocks) return FJAGG_OK;
+  UniformTQ q{};  // fjcomp_encode_uniform's operator, built the same way
+  q.lm1 = (float)(num_levels - 1);
+  q.num_levels = num_levels;
+  q.rcp_lm1 = 1.0 / (double)q.lm1;
+  const dim3 grid((unsigned)nblocks), block(kCThreads);
+  const size_t smem = UniformTQ::lds_bytes(num_levels);
+  hipStream_t s = as_stream(stream);
+  if (bits == 4)
+    hipLaunchKernelGGL(k_encode_uniform_packed<4>, grid, block, smem, s, q, in_ptrs, keys, qparams, R, row_n,
+                       block_prefix, code_ptrs, minmax);
+  else if (bits == 2)
+    hipLaunchKernelGGL(k_encode_uniform_packed<2>, grid, block, smem, s, q, in_ptrs, keys, qparams, R, row_n,
+                       block_prefix, code_ptrs, minmax);
+  else
+    hipLaunchKernelGGL(k_encode_uniform_packed<1>, grid, block, smem, s, q, in_ptrs, keys, qparams, R, row_n,
+                       block_prefix, code_ptrs, minmax);
+  return check_launch("k_encode_uniform_packed");
 }
 
 int64_t fjcomp_wht_tiles(int log2d, int pass) {

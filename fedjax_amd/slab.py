@@ -865,19 +865,25 @@ class CodeSlab:
     device tensor — row k is client k's leaves in jax flatten order, every leaf starting on a
     16-byte boundary — and ``minmax``, float32 ``[K, L, 2]``, every (client, leaf)'s (amin, amax).
     :meth:`mean` is ``tree_mean`` over the decoded deltas folded straight from the codes: a quarter
-    of the bytes :meth:`ClientDeltaSlab.mean` reads, and no decoded copy."""
+    of the bytes :meth:`ClientDeltaSlab.mean` reads, and no decoded copy.
 
-    def __init__(self, template: PyTree, num_clients: int, num_levels: int, *,
+    ``bits`` 1, 2 or 4 (``2**bits >= num_levels``): the rows hold the codes packed,
+    ``8 // bits`` to a byte, low bits first; a leaf of ``n`` elements is ``ceil(n * bits / 8)`` bytes,
+    still on a 16-byte boundary, and every method works on rows of that form."""
+
+    def __init__(self, template: PyTree, num_clients: int, num_levels: int, bits: int = 8, *,
                  device: Optional[torch.device] = None):
         from fedjax_amd import _compress
 
         self.num_levels = _compress.check_num_levels(num_levels)
+        self.bits = _compress.check_bits(bits, self.num_levels)
         leaves, self.treedef = pytree.flatten(template)
         self.shapes = [tuple(tree_util._to_tensor(x).shape) for x in leaves]
         self.sizes = [int(np.prod(s, dtype=np.int64)) for s in self.shapes]
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)  # of the float32 mean
         self.num_params = int(self.offsets[-1])
-        padded = (np.array(self.sizes, dtype=np.int64) + 15) // 16 * 16
+        self.code_sizes = [int(_compress.packed_bytes(n, self.bits)) for n in self.sizes]  # bytes of a leaf's codes
+        padded = (np.array(self.code_sizes, dtype=np.int64) + 15) // 16 * 16
         self.code_offsets = np.concatenate([[0], np.cumsum(padded)]).astype(np.int64)
         self.row_stride = max(16, int(self.code_offsets[-1]))
         self.num_clients = int(num_clients)
@@ -895,15 +901,19 @@ class CodeSlab:
         from fedjax_amd.aggregators.compression import EncodedDelta
 
         row = self.storage[k]
+        if self.bits < 8:
+            views = [row[o:o + n] for o, n in zip(self.code_offsets[:-1], self.code_sizes)]
+            return EncodedDelta(pytree.unflatten(self.treedef, views), self.minmax[k], self.num_levels, self.bits,
+                                tuple(self.shapes))
         views = [row[o:o + n].view(s) for o, n, s in zip(self.code_offsets[:-1], self.sizes, self.shapes)]
         return EncodedDelta(pytree.unflatten(self.treedef, views), self.minmax[k], self.num_levels)
 
     def set_client(self, k: int, encoded) -> None:
         """Copy one client's :class:`~fedjax_amd.aggregators.EncodedDelta` (device or host tensors)
-        into row k, after checking its dtype, structure, shapes and ``num_levels``."""
+        into row k, after checking its dtype, structure, shapes, ``num_levels`` and ``bits``."""
         from fedjax_amd.aggregators.compression import _encoded_rows
 
-        _, rows, mms = _encoded_rows([encoded], self.num_levels, self.shapes)
+        _, rows, mms, _ = _encoded_rows([encoded], self.num_levels, self.shapes, self.bits)
         dst = self.client(k)
         for d, src in zip(pytree.leaves_of(dst.codes), pytree.flatten_as(self.treedef, encoded.codes)):
             d.copy_(src, non_blocking=True)
@@ -928,7 +938,7 @@ class CodeSlab:
         rows = np.arange(K, dtype=np.int64)[:, None] * delta_slab.row_stride
         in_ptrs = (delta_slab.storage.data_ptr() + 4 * (rows + delta_slab.offsets[None, :-1])).astype(np.uint64)
         _compress.encode_uniform_table(in_ptrs, np.array(self.sizes, dtype=np.int64), keys, self.num_levels,
-                                       self._code_ptrs(), self.minmax, self.device)
+                                       self._code_ptrs(), self.minmax, self.device, self.bits)
         return self
 
     def _kept(self, name: str, key, make):
@@ -981,7 +991,7 @@ class CodeSlab:
             w_dev = self._kept("_weights", w.tobytes(), lambda: _lib.upload(torch.from_numpy(w), self.device))
             tables = self._kept("_tables", out.data_ptr(), lambda: _compress.CodesFold(
                 self._code_ptrs(), np.array(self.sizes, dtype=np.int64),
-                (out.data_ptr() + 4 * self.offsets[:-1]).astype(np.uint64), self.device))
+                (out.data_ptr() + 4 * self.offsets[:-1]).astype(np.uint64), self.device, self.bits))
             tables.launch(self.minmax.data_ptr(), w_dev.data_ptr(), scale, self.num_levels)
         return pytree.unflatten(self.treedef, views)
 

@@ -193,6 +193,29 @@ int fjcomp_encode_uniform(const float* const* in_ptrs, const uint32_t* keys, con
                           int64_t R, const int64_t* row_n, const int64_t* block_prefix, int64_t nblocks,
                           int num_levels, uint8_t* const* code_ptrs, float* minmax, void* stream);
 
+/* ---- the same form with bits = 1, 2 or 4 per code (2^bits >= num_levels) ----
+ * Element i of a row lives in byte i / (8 / bits) at bit offset bits * (i % (8 / bits)), low bits
+ * first; a row of n elements is ceil(n * bits / 8) bytes, and the unused high bits of its last
+ * byte influence nothing (the encoder writes them as 0). A field >= num_levels counts as top.
+ *
+ * fjcomp_codes_fold_packed: fjcomp_codes_fold's sums, bit for bit, from packed rows. A workgroup
+ * takes block_codes consecutive elements (FJCOMP_PACKED_BLOCK, or FJCOMP_PACKED_BLOCK_SMALL when
+ * the larger share would leave most of the chip idle; same bits); leaf_n counts elements and
+ * block_prefix is the running sum of ceil(leaf_n / block_codes).
+ *
+ * fjcomp_encode_uniform_packed: fjcomp_encode_uniform's decisions, written as the packing of
+ * its codes, every output byte stored whole by exactly one lane (no atomics, no cleared
+ * buffer). block_prefix as for fjcomp_encode_uniform. */
+#define FJCOMP_PACKED_BLOCK 4096
+#define FJCOMP_PACKED_BLOCK_SMALL 2048
+int fjcomp_codes_fold_packed(const uint8_t* const* code_ptrs, const float* minmax, const float* w, int64_t K,
+                             int64_t L, const int64_t* leaf_n, const int64_t* block_prefix, int64_t nblocks,
+                             int block_codes, int bits, int num_levels, float scale, int flags,
+                             float* const* out_ptrs, void* stream);
+int fjcomp_encode_uniform_packed(const float* const* in_ptrs, const uint32_t* keys, const fjcomp_qparams* qparams,
+                                 int64_t R, const int64_t* row_n, const int64_t* block_prefix, int64_t nblocks,
+                                 int bits, int num_levels, uint8_t* const* code_ptrs, float* minmax, void* stream);
+
 /* Walsh-Hadamard jobs. pass_prefix[npass][J+1] (device): per pass, the running sum of
  * that job's tiles in the pass (0 if the job has fewer passes); pass_tiles[npass] (host):
  * the totals. A job of d = 2^log2d has one pass for log2d <= 13, else
