@@ -12,6 +12,9 @@ shapes of ``fedjax/aggregators/compression.py``:
                        the reference commute with the weighted mean)
 * ``drive_mean``       per-client rotation: signs -> WHT -> sums -> DRIVE + inverse
                        WHT -> dense fold (compression.py:298-308)
+* ``drive_signs_mean`` the same mean from transmitted sign bits and scales: signs ->
+                       inverse WHT from the bits, the fold in its last pass
+                       (``drive_encode`` is the client's side)
 
 Everything is asynchronous on torch's current stream; only the arithmetic-coding
 bit count (``hist=True``) reads results back. Device work is batched over clients
@@ -38,7 +41,8 @@ QPARAMS = np.dtype([("vmin", "<f4"), ("vmax", "<f4"), ("range", "<f4"), ("thr", 
 STATS = np.dtype([("min", "<f8"), ("max", "<f8"), ("absmax", "<f8"), ("sum", "<f8"), ("sumsq", "<f8"),
                   ("sumabs", "<f8")])
 assert ROW.itemsize == 16 and SIGN_JOB.itemsize == 24 and WHT_JOB.itemsize == 72
-assert QPARAMS.itemsize == 24 and STATS.itemsize == 48
+DRIVE_LEAF = np.dtype([("out", "<u8"), ("n", "<i8"), ("ws_off", "<i8"), ("log2d", "<i4"), ("sqrt_d", "<f4")])
+assert QPARAMS.itemsize == 24 and STATS.itemsize == 48 and DRIVE_LEAF.itemsize == 32
 
 WHT_BITS = 13       # butterfly bits of pass 0
 WHT_HIGH_BITS = 8   # butterfly bits of each later pass
@@ -548,6 +552,125 @@ def drive_mean(rows: List[List[torch.Tensor]], client_keys: np.ndarray, w: np.nd
         kernels.weighted_sum_dense(Z[:kb, :P], w_dev[k0:k0 + kb], scale=scale if last else None, out=out_flat,
                                    accumulate=k0 > 0)
         del t0, t1, t2, signs, stats
+
+
+# ----------------------------------------------------------------------------- DRIVE from sign bits
+class DriveSignsLayout:
+    """Host tables of DRIVE's transmitted form for leaves of ``leaf_n`` elements (plain numpy, no
+    device): per leaf the rotated length ``d``, its ``nbytes = ceil(d / 8)`` sign bytes and its
+    Rademacher ``words``; the float32 workspace row of one client (``ws_off`` per leaf with more
+    than one WHT pass, ``D`` floats in all); the tile prefixes ``pass_prefix[p]`` of the passes
+    before a leaf's last, and of the last pass over the single-pass (``single_prefix``) and the
+    other (``multi_prefix``) leaves; ``client_bytes``, what one client of a batch holds on the
+    device (its workspace row and its Rademacher words)."""
+
+    def __init__(self, leaf_n: Sequence[int]):
+        self.n = np.asarray(leaf_n, dtype=np.int64).reshape(-1)
+        self.d = np.array([padded_size(int(n)) for n in self.n], dtype=np.int64)
+        self.m = np.array([log2_exact(int(d)) for d in self.d], dtype=np.int64)
+        if (self.m > WHT_MAX_LOG2).any():
+            raise ValueError("Walsh-Hadamard length out of range")
+        self.nbytes = (self.d + 7) // 8
+        self.words = (self.d + 31) // 32
+        passes = np.array([wht_passes(int(m)) for m in self.m], dtype=np.int64)
+        multi = passes > 1
+        self.ws_off = np.concatenate([[0], np.cumsum(np.where(multi, self.d, 0))]).astype(np.int64)
+        self.D = int(self.ws_off[-1])
+        self.ws_off = self.ws_off[:-1]
+
+        def prefix(tiles):
+            return np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
+
+        self.pass_prefix = [prefix([wht_tiles(int(m), p) if p < q - 1 else 0 for m, q in zip(self.m, passes)])
+                            for p in range(int(passes.max(initial=1)) - 1)]
+        last = np.array([wht_tiles(int(m), int(q) - 1) for m, q in zip(self.m, passes)], dtype=np.int64)
+        self.single_prefix = prefix(np.where(multi, 0, last))
+        self.multi_prefix = prefix(np.where(multi, last, 0))
+        self.client_bytes = 4 * self.D + 4 * int(self.words.sum())
+
+    def batch(self, K: int, workspace_bytes: int) -> int:
+        return _batch_size(K, self.client_bytes, workspace_bytes)
+
+
+def drive_encode(rows: List[List[torch.Tensor]], keys: np.ndarray):
+    """One client's DRIVE payload from its float32 leaves rows[0] under leaf keys [L, 2]: (sign-bit
+    leaves, 1-D uint8 of ``ceil(d / 8)`` bytes, and scales float32 [L, 2]). The rotation and the
+    two sums are drive_mean's (ROTATE jobs with WHT_F_SUMS partials, stats_from_partials)."""
+    device = rows[0][0].device
+    lay = DriveSignsLayout([x.numel() for x in rows[0]])
+    L = lay.n.size
+    offs = np.concatenate([[0], np.cumsum(lay.d)]).astype(np.int64)
+    signs, woff = rademacher_words(np.asarray(keys, dtype=np.uint32).reshape(L, 2), lay.d, device)
+    sptr = np.uint64(signs.data_ptr()) + 4 * woff[:-1].astype(np.uint64)
+    Y = torch.empty(int(offs[-1]), dtype=torch.float32, device=device)
+    ydst = np.uint64(Y.data_ptr()) + 4 * offs[:-1].astype(np.uint64)
+    last_tiles = _last_pass_tiles(lay.d)
+    part_slot = int(_lib.load().fjcomp_row_stats_workspace_bytes(1))
+    part = torch.empty(max(int(last_tiles.sum()) * part_slot, 16), dtype=torch.uint8, device=device)
+    pre = np.concatenate([[0], np.cumsum(last_tiles)]).astype(np.int64)
+    pptr = np.uint64(part.data_ptr()) + np.uint64(part_slot) * pre[:-1].astype(np.uint64)
+    t1 = run_wht(wht_jobs(tree_util._ptr_table(rows, np.uint64)[0], ydst, ydst, lay.d, kind=_lib.WHT_ROTATE,
+                          n_in=lay.n, signs=sptr, stats=pptr, flags=WHT_F_SUMS), device)
+    stats, _, t0 = stats_from_partials(ydst, lay.d, pre, part, 0, device, want_qparams=False)
+    bits = [torch.empty(int(b), dtype=torch.uint8, device=device) for b in lay.nbytes]
+    scales = torch.empty(L, 2, dtype=torch.float32, device=device)
+    tab = np.empty(L, dtype=ROW)
+    tab["ptr"], tab["n"] = ydst, lay.d
+    prefix = _block_prefix(lay.d, _lib.DRIVE_PACK_BLOCK)
+    up = Upload()
+    o_rows, o_pre = up.add(tab), up.add(prefix)
+    o_out = up.add(np.array([b.data_ptr() for b in bits], dtype=np.uint64))
+    base = up.commit(device)
+    _lib.call("fjcomp_drive_pack", base + o_rows, base + o_pre, L, int(prefix[-1]), stats.data_ptr(), base + o_out,
+              scales.data_ptr(), _stream(device))
+    del t0, t1, up, signs, stats, part, Y
+    return bits, scales
+
+
+def drive_signs_mean(bits: List[List[torch.Tensor]], scales: torch.Tensor, client_keys: np.ndarray, w: np.ndarray,
+                     scale: Optional[float], leaf_n: Sequence[int], out_flat: torch.Tensor, *,
+                     workspace_bytes: int = DEFAULT_WORKSPACE_BYTES) -> None:
+    """tree_mean over DRIVE payloads into out_flat [P] (leaves concatenated in flatten order):
+    bits [K][L] sign-bit leaves, scales float32 [K, L, 2] on the device, client_keys [K, L, 2] the
+    rotation keys. Per batch of clients: the Rademacher words, the passes before the last of the
+    leaves above 8192 padded elements into a [B, D] workspace, then the last pass with the fold in
+    its epilogue (single-pass leaves straight from the bits)."""
+    device = out_flat.device
+    lay = DriveSignsLayout(leaf_n)
+    K, L = len(bits), lay.n.size
+    B = lay.batch(K, workspace_bytes)
+    ws = torch.empty((B, lay.D), dtype=torch.float32, device=device) if lay.D else None
+    ws_ptr = ws.data_ptr() if lay.D else None
+    leaves = np.zeros(L, dtype=DRIVE_LEAF)
+    loff = np.concatenate([[0], np.cumsum(lay.n)]).astype(np.int64)
+    leaves["out"] = np.uint64(out_flat.data_ptr()) + 4 * loff[:-1].astype(np.uint64)
+    leaves["n"], leaves["ws_off"], leaves["log2d"] = lay.n, lay.ws_off, lay.m
+    leaves["sqrt_d"] = np.sqrt(lay.d.astype(np.float32))  # jnp.sqrt(d): correctly rounded f32
+    up = Upload()
+    o_leaves = up.add(leaves)
+    o_pass = [up.add(p) for p in lay.pass_prefix]
+    o_single, o_multi = up.add(lay.single_prefix), up.add(lay.multi_prefix)
+    o_bits = up.add(np.array([[x.data_ptr() for x in r] for r in bits], dtype=np.uint64))
+    o_w = up.add(np.ascontiguousarray(w, dtype=np.float32))
+    base = up.commit(device)
+    for k0 in range(0, K, B):
+        kb = min(B, K - k0)
+        signs, woff = rademacher_words(client_keys[k0:k0 + kb].reshape(-1, 2), np.tile(lay.d, kb), device)
+        sup = Upload()
+        o_signs = sup.add(np.uint64(signs.data_ptr()) + 4 * woff[:-1].astype(np.uint64))
+        sptr = sup.commit(device) + o_signs
+        bptr, sc = base + o_bits + 8 * k0 * L, scales.data_ptr() + 8 * k0 * L
+        for p, o_pre in enumerate(o_pass):
+            _lib.call("fjcomp_drive_pass", base + o_leaves, base + o_pre, L, int(lay.pass_prefix[p][-1]), p, bptr, sc,
+                      kb, ws_ptr, lay.D, _stream(device))
+        flags = (_lib.SCALE if scale is not None and k0 + kb == K else 0) | (_lib.ACCUMULATE if k0 else 0)
+        for single, o_pre, pre in ((1, o_single, lay.single_prefix), (0, o_multi, lay.multi_prefix)):
+            _lib.call("fjcomp_drive_fold", base + o_leaves, base + o_pre, L, int(pre[-1]), single, bptr, sptr, sc,
+                      base + o_w + 4 * k0, kb, ws_ptr, lay.D, float(np.float32(scale if scale is not None else 1.0)),
+                      flags, _stream(device))
+        # (freed blocks are reused only in stream order, so a batch's words and table can go now)
+        del signs, sup
+    del up
 
 
 # ----------------------------------------------------------------------------- bits

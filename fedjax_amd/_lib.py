@@ -50,6 +50,7 @@ WHT_PLAIN, WHT_ROTATE, WHT_UNROTATE, WHT_UNROTATE_DRIVE = 0, 1, 2, 3
 STATS_CHUNK = 16384
 CODES_BLOCK, CODES_BLOCK_SMALL = 4096, 1024  # FJCOMP_CODES_BLOCK, FJCOMP_CODES_BLOCK_SMALL
 PACKED_BLOCK, PACKED_BLOCK_SMALL = 4096, 2048  # FJCOMP_PACKED_BLOCK, FJCOMP_PACKED_BLOCK_SMALL
+DRIVE_PACK_BLOCK = 2048  # FJCOMP_DRIVE_PACK_BLOCK
 TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
@@ -162,6 +163,9 @@ _SIGNATURES = {
     "fjcomp_encode_uniform_packed": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "fjcomp_wht_tiles": (_i64, [_i32, _i32]),
     "fjcomp_wht": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "fjcomp_drive_pack": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "fjcomp_drive_pass": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "fjcomp_drive_fold": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _i32, _vp]),
     "fjcomp_topk_workspace_bytes": (_i64, [_i64]),
     "fjcomp_topk_select_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "fjcomp_topk_select_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32,

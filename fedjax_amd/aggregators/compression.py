@@ -471,6 +471,131 @@ def encoded_mean_aggregator(num_levels: int, bits: int = 8, template: Optional[P
 
 
 @dataclasses.dataclass
+class DriveDelta:
+    """A DRIVE-compressed delta as a client transmits it: ``signs``, a pytree shaped like the delta
+    whose every leaf is a 1-D uint8 tensor of ``ceil(d / 8)`` bytes, ``d = 2 ** ceil(log2(n))`` the
+    leaf's rotated length: rotated coordinate ``i`` in byte ``i // 8`` at bit ``i % 8``, low bit
+    first (:func:`pack_codes`' order), 1 where the rotated value is ``< 0`` (zeros, ``-0.0`` and NaNs
+    are sent as 0; the padding bits of a leaf with ``d < 8`` are written as zero and ignored on
+    reading); ``scales``, a float32 ``[L, 2]`` tensor of every rotated leaf's
+    ``(f32(sum y**2), f32(sum |y|))``; ``shapes``, the delta's leaf shapes in flatten order. A sign
+    ``s`` of leaf ``l`` stands for ``(A * s) / b`` in float32 with ``(A, b) = scales[l]``:
+    ``drive_pytree``'s value (compression.py:269-277)."""
+    signs: Any
+    scales: Any
+    shapes: Tuple[Tuple[int, ...], ...] = _field(metadata={"pytree_node": False})
+
+
+def drive_round_keys(rng, num_clients: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(new_rng, client_keys [num_clients, 2])``: the key stream of one
+    ``structured_drive_quantizer`` round (compression.py:298-301), so that clients and server
+    derive the same rotation keys. Client ``k`` encodes with ``client_keys[k]``."""
+    new_rng, rotation_rng = random.split(np.asarray(rng, np.uint32))
+    return new_rng, random.PRNGSequence(rotation_rng).take(int(num_clients))
+
+
+def drive_encode_pytree(params: PyTree, rng) -> DriveDelta:
+    """The client side of :func:`drive_mean_aggregator`: every leaf rotated under its key of
+    ``split(rng, num_leaves)`` (``structured_rotation_pytree``'s rotation), then only the sign bits
+    and the two sums ``drive_pytree`` needs are kept (:class:`DriveDelta`). Float32 leaves."""
+    td, rows = _rows([params])
+    L = len(rows[0])
+    shapes = tuple(tuple(x.shape) for x in rows[0])
+    if not L:
+        return DriveDelta(pytree.unflatten(td, []), torch.empty(0, 2, dtype=torch.float32), shapes)
+    bits, scales = C.drive_encode(rows, random.split(rng, L))
+    return DriveDelta(pytree.unflatten(td, bits), scales, shapes)
+
+
+def _drive_rows(deltas: Sequence[Any], shapes=None):
+    """(treedef, sign leaves [K][L], scales [K], shapes) of DriveDelta clients after every check the
+    kernels rely on: one structure, equal ``shapes`` (``shapes``, default client 0's), 1-D uint8
+    leaves of ``ceil(d / 8)`` bytes and float32 ``[L, 2]`` scales."""
+    td, rows, scs = None, [], []
+    for k, d in enumerate(deltas):
+        if not isinstance(d, DriveDelta):
+            raise TypeError(f"client {k}: expected a DriveDelta, got {type(d).__name__}")
+        if td is None:
+            leaves, td = pytree.flatten(d.signs)
+        else:
+            leaves = pytree.flatten_as(td, d.signs)
+        mine = tuple(tuple(int(v) for v in sh) for sh in d.shapes)
+        if shapes is None:
+            shapes = mine
+        if mine != tuple(tuple(sh) for sh in shapes):
+            raise ValueError(f"client {k} has leaf shapes {mine}, expected {tuple(shapes)}")
+        if len(leaves) != len(shapes):
+            raise ValueError(f"client {k} has {len(leaves)} leaves, expected {len(shapes)}")
+        for l, (x, sh) in enumerate(zip(leaves, shapes)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+                raise TypeError(f"client {k} leaf {l}: sign bits must be uint8 tensors, got "
+                                f"{x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
+            want = ((C.padded_size(int(np.prod(sh, dtype=np.int64))) + 7) // 8,)
+            if tuple(x.shape) != want:
+                raise ValueError(f"client {k} leaf {l} has shape {tuple(x.shape)}, expected {want}")
+        sc = d.scales
+        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.float32:
+            raise TypeError(f"client {k}: scales must be a float32 tensor")
+        if tuple(sc.shape) != (len(shapes), 2):
+            raise ValueError(f"client {k}: scales has shape {tuple(sc.shape)}, expected {(len(shapes), 2)}")
+        rows.append(leaves)
+        scs.append(sc)
+    return td, rows, scs, shapes
+
+
+def drive_mean_aggregator(rng, template: Optional[PyTree] = None, *,
+                          workspace_bytes: int = C.DEFAULT_WORKSPACE_BYTES) -> aggregator.Aggregator:
+    """The server side of a round whose clients transmit :class:`DriveDelta`: ``apply`` takes
+    ``(client_id, DriveDelta, weight)`` triples, advances its key as ``structured_drive_quantizer``
+    does (:func:`drive_round_keys`) and returns ``tree_mean`` over the decoded, inverse-rotated
+    deltas: one inverse Walsh-Hadamard transform per client straight from the sign bits, the fold
+    in the epilogue of its last pass, so neither the decoded nor the unrotated deltas reach HBM
+    (leaves of at most 8192 padded elements touch no intermediate at all). ``num_bits`` grows as
+    ``structured_drive_quantizer`` counts it. With clients encoded by :func:`drive_encode_pytree`
+    under this round's keys the mean is bit for bit that aggregator's over clients with no rotated
+    coordinate that is exactly zero or NaN. Such a coordinate is sent as ``+``: it decodes to
+    ``+A/b`` where the fused round has ``sign(0) = 0``, which moves every output of that leaf by
+    ``(A/b) / sqrt(d) * w_k / W``. With billions of rotated coordinates a round (1024 clients x
+    millions of parameters) a few tens of them occur in every round, so the two means then differ
+    by a few 1e-5 (DESIGN.md §3za has the counts). ``template`` (a pytree of the model's leaves) checks the
+    clients' ``shapes``; ``workspace_bytes`` bounds the batch of clients whose workspace rows
+    (leaves above 8192 padded elements only) and rotation signs are held at once."""
+    expect = None if template is None else _template_shapes(template)
+
+    def init():
+        return CompressionState(0.0, np.asarray(rng, np.uint32))
+
+    def apply(clients_params_and_weights, aggregator_state):
+        deltas, weights = _consume(clients_params_and_weights)
+        new_rng, client_keys = drive_round_keys(aggregator_state.rng, len(deltas))
+        agg, P, L = None, 0, 0
+        if deltas:
+            td, rows, scs, shapes = _drive_rows(deltas, expect)
+            L = len(rows[0])
+            if L:
+                device = tree_util._find_device(rows[0])
+                rows = [[x.to(device).contiguous() for x in r] for r in rows]
+                w, scale = _weights(weights)
+                leaf_n = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+                P = sum(leaf_n)
+                flat = torch.empty(P, dtype=torch.float32, device=device)
+                scales = torch.stack([s.to(device) for s in scs]).contiguous()
+                C.drive_signs_mean(rows, scales, random.split_many(client_keys, L), w, scale, leaf_n, flat,
+                                   workspace_bytes=workspace_bytes)
+                outs, o = [], 0
+                for sh, n in zip(shapes, leaf_n):
+                    outs.append(flat[o:o + n].view(sh))
+                    o += n
+                agg = pytree.unflatten(td, outs)
+            else:
+                agg = pytree.unflatten(td, [])
+        new_bits = F32(P + 32 * 2 * L)
+        return agg, CompressionState(F32(aggregator_state.num_bits + new_bits), new_rng)
+
+    return aggregator.Aggregator(init, apply)
+
+
+@dataclasses.dataclass
 class SparsifierState:
     """State of :func:`top_k_sparsifier`: the bits transmitted so far, ``0.0`` at first and a 0-d
     float64 device tensor after the first non-empty round (reading it is the only synchronisation)."""
@@ -510,7 +635,8 @@ def top_k_sparsifier(k) -> aggregator.Aggregator:
 
 
 __all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier", "EncodedDelta", "encoded_mean_aggregator",
-           "uniform_stochastic_encode_pytree", "pack_codes", "unpack_codes",
+           "uniform_stochastic_encode_pytree", "pack_codes", "unpack_codes", "DriveDelta", "drive_round_keys",
+           "drive_encode_pytree", "drive_mean_aggregator",
            "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",
            "num_leaves", "rotated_uniform_stochastic_quantizer", "structured_drive_quantizer", "terngrad_quantize",
            "terngrad_quantize_pytree", "terngrad_quantizer", "uniform_stochastic_quantize",

@@ -25,7 +25,10 @@
 //                                  floats (128-byte segments: coalesced); butterflies run
 //                                  radix-16 in registers (4 stages per LDS round trip); the
 //                                  rotation prologue (zero pad, sign) and epilogue (sign,
-//                                  / sqrt(d), truncate) are fused into the first/last pass.
+//                                  / sqrt(d), truncate) are fused into the first/last pass;
+//   k_drive_pack / k_drive_pass /  DRIVE's transmitted form: sign bits out of a rotated leaf, and the
+//   k_drive_fold                   clients' inverse rotations straight from the bits with tree_mean's
+//                                  fold in the last pass's epilogue.
 //
 // Arithmetic follows the reference's float32 op sequence. Division: a quotient by a
 // per-row constant b is RN_f32(a * RN_f64(1/b)); the f64 error (< 2^-52 relative) is
@@ -54,6 +57,7 @@ static_assert(sizeof(fjcomp_qparams) == 24, "fjcomp_qparams layout");
 static_assert(sizeof(fjcomp_row) == 16, "fjcomp_row layout");
 static_assert(sizeof(fjcomp_sign_job) == 24, "fjcomp_sign_job layout");
 static_assert(sizeof(fjcomp_wht_job) == 72, "fjcomp_wht_job layout");
+static_assert(sizeof(fjcomp_drive_leaf) == 32, "fjcomp_drive_leaf layout");
 
 namespace {
 
@@ -1001,6 +1005,261 @@ __global__ __launch_bounds__(kWhtThreads) void k_wht(const fjcomp_wht_job* __res
   if (tile_stats) mm.store(reinterpret_cast<Partial*>(const_cast<fjcomp_stats*>(jb.stats)) + tix, tile_sums);
 }
 
+// ------------------------------------------------------------------ DRIVE from sign bits
+// A client that really transmits its DRIVE payload sends, per leaf, the sign bit of every rotated
+// coordinate and the pair (A, b) = (f32(sum y^2), f32(sum |y|)). k_drive_pack writes that form from
+// a rotated leaf; k_drive_pass and k_drive_fold are the server: the inverse rotation of every
+// client straight from the bits, with tree_mean's fold in the epilogue of the last pass, so the
+// unrotated deltas never reach HBM. Tiling, stage order and element arithmetic are k_wht's
+// (UNROTATE_DRIVE), so every decoded value carries k_wht's bits.
+constexpr int kDrivePackThreads = 256;
+static_assert(kDrivePackThreads * 8 == FJCOMP_DRIVE_PACK_BLOCK, "a lane packs one byte");
+constexpr int kDriveChunk = 256;  // clients whose constants k_drive_fold stages in LDS at a time
+
+__global__ __launch_bounds__(kDrivePackThreads) void k_drive_pack(const fjcomp_row* __restrict__ rows,
+                                                                   const int64_t* __restrict__ prefix, int64_t R,
+                                                                   const fjcomp_stats* __restrict__ stats,
+                                                                   uint8_t* const* __restrict__ sign_ptrs,
+                                                                   float* __restrict__ scales) {
+  const int64_t b = blockIdx.x;
+  const int64_t r = find_segment(prefix, R, b);
+  const fjcomp_row row = rows[r];
+  const int64_t blk = b - prefix[r];
+  if (blk == 0 && threadIdx.x == 0) {
+    scales[2 * r] = (float)stats[r].sumsq;
+    scales[2 * r + 1] = (float)stats[r].sumabs;
+  }
+  const int64_t i0 = 8 * (blk * kDrivePackThreads + threadIdx.x);
+  if (i0 >= row.n) return;
+  uint32_t byte = 0;
+  if (i0 + 8 <= row.n && ((uintptr_t)row.ptr & 15) == 0) {
+    const float4 q0 = *reinterpret_cast<const float4*>(row.ptr + i0);
+    const float4 q1 = *reinterpret_cast<const float4*>(row.ptr + i0 + 4);
+    const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+    for (int u = 0; u < 8; ++u) byte |= (v[u] < 0.0f ? 1u : 0u) << u;
+  } else {
+    for (int u = 0; u < 8 && i0 + u < row.n; ++u) byte |= (row.ptr[i0 + u] < 0.0f ? 1u : 0u) << u;
+  }
+  sign_ptrs[r][i0 >> 3] = (uint8_t)byte;
+}
+
+// Where tile `tix` of pass `pass` sits in a 2^m transform (k_wht's mapping).
+struct DriveTile {
+  WhtTiling t;
+  int64_t base;
+  __device__ inline int64_t g(int e) const { return base + ((int64_t)(e >> t.lc) << t.lo) + (e & (t.c - 1)); }
+};
+__device__ inline DriveTile drive_tile(int m, int pass, int64_t tix) {
+  DriveTile d;
+  d.t = wht_tiling(m, pass);
+  const int64_t cph = ((int64_t)1 << d.t.lo) / d.t.c;
+  d.base = ((tix / cph) << (d.t.lo + d.t.nb)) + (tix % cph) * d.t.c;
+  return d;
+}
+
+// The sign bits of a pass-0 tile (nbytes <= 1024 bytes at p), one word in each of the lower 32
+// lanes of every wave: lane i of wave v holds bits [32 * (32 v + i), + 32). A 4-byte load when
+// the pointer allows, bytes otherwise; nothing past nbytes is read.
+__device__ inline uint32_t drive_load_bits(const uint8_t* __restrict__ p, int nbytes) {
+  const int lane = threadIdx.x & 63, o = 4 * ((threadIdx.x >> 6) * 32 + lane);
+  uint32_t w = 0;
+  if (lane < 32 && o < nbytes) {
+    if (((uintptr_t)p & 3) == 0 && o + 4 <= nbytes) {
+      w = *reinterpret_cast<const uint32_t*>(p + o);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (o + u < nbytes) w |= (uint32_t)p[o + u] << (8 * u);
+    }
+  }
+  return w;
+}
+
+// ... expanded into the LDS tile: lane t owns elements 16 t .. 16 t + 15 (half of the word its
+// wave's lane t / 2 holds), each div_by(A * +-1, rcp_b) as k_wht's UNROTATE_DRIVE load has it.
+// Every lane of the workgroup calls it (the shuffle reads lanes that own nothing themselves).
+__device__ inline void drive_expand(float* sm, uint32_t w, float A, double rcp_b, int tile) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t h = (uint32_t)__shfl((int)w, lane >> 1) >> (16 * (lane & 1));
+  const int e0 = 16 * threadIdx.x;
+  if (e0 >= tile) return;
+  const float pos = div_by(A * 1.0f, rcp_b), neg = div_by(A * -1.0f, rcp_b);
+  float* o = sm + lds_pad(e0);  // 16 elements of one 32-block: contiguous
+#pragma unroll
+  for (int u = 0; u < 16; ++u)
+    if (e0 + u < tile) o[u] = ((h >> u) & 1u) ? neg : pos;
+}
+
+// The lane's quads of a full workspace tile (elements 4 t + 2048 i, i < 4) between HBM and LDS.
+__device__ inline void drive_load_quads(const float* __restrict__ row, const DriveTile& dt, float4 (&q)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    q[i] = *reinterpret_cast<const float4*>(row + dt.g(4 * threadIdx.x + 4 * kWhtThreads * i));
+}
+__device__ inline void drive_store_quads(float* sm, const float4 (&q)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float* o = sm + lds_pad(4 * threadIdx.x + 4 * kWhtThreads * i);
+    o[0] = q[i].x, o[1] = q[i].y, o[2] = q[i].z, o[3] = q[i].w;
+  }
+}
+
+__device__ inline void drive_stages(float* sm, const WhtTiling& t) {
+  for (int s0 = 0; s0 < t.nb; s0 += 4) {
+    const int p = t.lc + s0;
+    switch (t.nb - s0 < 4 ? t.nb - s0 : 4) {
+      case 1: wht_group<1>(sm, t.tile, p); break;
+      case 2: wht_group<2>(sm, t.tile, p); break;
+      case 3: wht_group<3>(sm, t.tile, p); break;
+      default: wht_group<4>(sm, t.tile, p); break;
+    }
+    __syncthreads();
+  }
+}
+
+// A pass before the last of the leaves with more than one pass (d > 8192: every tile is full).
+// Grid: (client of the batch, leaf, tile). Pass 0 expands 1 KiB of sign bits; later passes work
+// in place on the client's workspace row.
+__global__ __launch_bounds__(kWhtThreads) void k_drive_pass(const fjcomp_drive_leaf* __restrict__ leaves,
+                                                             const int64_t* __restrict__ prefix, int64_t L,
+                                                             int64_t tiles, int pass,
+                                                             const uint8_t* const* __restrict__ bit_ptrs,
+                                                             const float* __restrict__ scales,
+                                                             float* __restrict__ ws, int64_t D) {
+  __shared__ float sm[kWhtTile + kWhtTile / 32];
+  const int64_t k = blockIdx.x / tiles, r = blockIdx.x % tiles;
+  const int64_t l = find_segment(prefix, L, r);
+  const fjcomp_drive_leaf lf = leaves[l];
+  const DriveTile dt = drive_tile(lf.log2d, pass, r - prefix[l]);
+  float* __restrict__ row = ws + k * D + lf.ws_off;
+  if (pass == 0) {
+    const int64_t cl = k * L + l;
+    const uint32_t w = drive_load_bits(bit_ptrs[cl] + (dt.base >> 3), kWhtTile / 8);
+    drive_expand(sm, w, scales[2 * cl], 1.0 / (double)scales[2 * cl + 1], kWhtTile);
+  } else {
+    float4 q[4];
+    drive_load_quads(row, dt, q);
+    drive_store_quads(sm, q);
+  }
+  __syncthreads();
+  drive_stages(sm, dt.t);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int e = 4 * threadIdx.x + 4 * kWhtThreads * i;
+    const float* o = sm + lds_pad(e);
+    *reinterpret_cast<float4*>(row + dt.g(e)) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// The last pass of every client's inverse rotation with the fold in its epilogue. Grid: (leaf,
+// last-pass tile); the workgroup walks the batch's clients in order. A lane owns the quads
+// 4 t + 2048 i (i < 4) of the tile: 16 running sums in registers for the whole client loop.
+// While a client's butterflies run, the next client's tile (one word of sign bits, or the lane's
+// four workspace quads) is already on its way into registers.
+struct DriveClient {
+  const uint8_t* bits;
+  const uint32_t* signs;
+  double rcp_b;
+  float A, w;
+};
+template <bool SINGLE>
+__global__ __launch_bounds__(kWhtThreads) void k_drive_fold(const fjcomp_drive_leaf* __restrict__ leaves,
+                                                             const int64_t* __restrict__ prefix, int64_t L,
+                                                             const uint8_t* const* __restrict__ bit_ptrs,
+                                                             const uint32_t* const* __restrict__ sign_ptrs,
+                                                             const float* __restrict__ scales,
+                                                             const float* __restrict__ w, int64_t kb,
+                                                             const float* __restrict__ ws, int64_t D, float scale,
+                                                             int flags) {
+  __shared__ float sm[kWhtTile + kWhtTile / 32];
+  __shared__ DriveClient qc[kDriveChunk];
+  const int64_t b = blockIdx.x;
+  const int64_t l = find_segment(prefix, L, b);
+  const fjcomp_drive_leaf lf = leaves[l];
+  const int m = lf.log2d;
+  const DriveTile dt = drive_tile(m, wht_passes(m) - 1, b - prefix[l]);
+  const int tile = (int)dt.t.tile;          // d for a single-pass leaf, 8192 otherwise
+  const int nbytes = (tile + 7) >> 3;
+  const double rcp_sqrt_d = 1.0 / (double)lf.sqrt_d;
+  const int tid = threadIdx.x;
+  int64_t g[4];
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    g[i] = dt.g(4 * tid + 4 * kWhtThreads * i);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      acc[i][u] = ((flags & FJAGG_ACCUMULATE) && 4 * tid + 4 * kWhtThreads * i < tile && g[i] + u < lf.n)
+                      ? lf.out[g[i] + u] : 0.0f;
+  }
+  for (int64_t kc = 0; kc < kb; kc += kDriveChunk) {
+    const int jn = (int)(kb - kc < kDriveChunk ? kb - kc : kDriveChunk);
+    // (every wave left the previous chunk's last client at that client's closing barrier)
+    if (tid < jn) {
+      const int64_t cl = (kc + tid) * L + l;
+      DriveClient c;
+      c.bits = SINGLE ? bit_ptrs[cl] : nullptr;
+      c.signs = sign_ptrs[cl];
+      c.A = scales[2 * cl];
+      c.rcp_b = 1.0 / (double)scales[2 * cl + 1];
+      c.w = w[kc + tid];
+      qc[tid] = c;
+    }
+    __syncthreads();
+    uint32_t wbits = 0;
+    float4 q[4];
+    if constexpr (SINGLE) wbits = drive_load_bits(qc[0].bits, nbytes);
+    else drive_load_quads(ws + kc * D + lf.ws_off, dt, q);
+    for (int j = 0; j < jn; ++j) {
+      const DriveClient c = qc[j];
+      if constexpr (SINGLE) drive_expand(sm, wbits, c.A, c.rcp_b, tile);
+      else drive_store_quads(sm, q);
+      __syncthreads();
+      if (j + 1 < jn) {  // the next client's tile, in flight under this client's stages
+        if constexpr (SINGLE) wbits = drive_load_bits(qc[j + 1].bits, nbytes);
+        else drive_load_quads(ws + (kc + j + 1) * D + lf.ws_off, dt, q);
+      }
+      uint32_t sw[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        sw[i] = 4 * tid + 4 * kWhtThreads * i < tile ? c.signs[g[i] >> 5] >> (g[i] & 31) : 0u;
+      drive_stages(sm, dt.t);
+      const bool first = kc + j == 0 && !(flags & FJAGG_ACCUMULATE);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = 4 * tid + 4 * kWhtThreads * i;
+        if (e >= tile) break;
+        const float* o = sm + lds_pad(e);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (e + u >= tile) break;  // d < 4
+          const float z = div_by(o[u] * (((sw[i] >> u) & 1u) ? -1.0f : 1.0f), rcp_sqrt_d);
+          const float p = z * c.w;
+          acc[i][u] = first ? p : acc[i][u] + p;
+        }
+      }
+      __syncthreads();  // the tile is free for the next client
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (4 * tid + 4 * kWhtThreads * i >= tile || g[i] >= lf.n) continue;
+    if (flags & FJAGG_SCALE) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[i][u] = acc[i][u] * scale;
+    }
+    float* __restrict__ o = lf.out + g[i];
+    if (g[i] + 3 < lf.n && ((uintptr_t)o & 15) == 0) {
+      *reinterpret_cast<float4*>(o) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (g[i] + u < lf.n) o[u] = acc[i][u];
+    }
+  }
+}
+
 // ------------------------------------------------------------------ 8-bit level codes
 // A client that really transmits its uniformly quantized delta sends, per leaf, one byte per
 // element (the level index c < num_levels <= 256) and the pair (vmin, vmax). k_encode_uniform
@@ -1938,6 +2197,57 @@ int fjcomp_wht(const fjcomp_wht_job* jobs, const int64_t* pass_prefix, int64_t J
     if (int rc = check_launch("k_wht")) return rc;
   }
   return FJAGG_OK;
+}
+
+int fjcomp_drive_pack(const fjcomp_row* rows, const int64_t* block_prefix, int64_t R, int64_t nblocks,
+                      const fjcomp_stats* stats, uint8_t* const* sign_ptrs, float* scales, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (R < 0 || nblocks < 0 || nblocks > INT32_MAX)
+    return fail(FJAGG_EINVAL, "drive_pack: bad sizes (R=%lld nblocks=%lld)", (long long)R, (long long)nblocks);
+  if (R && (!rows || !block_prefix || !stats || !sign_ptrs || !scales))
+    return fail(FJAGG_EINVAL, "drive_pack: null table");
+  if (!R || !nblocks) return FJAGG_OK;
+  hipLaunchKernelGGL(k_drive_pack, dim3((unsigned)nblocks), dim3(kDrivePackThreads), 0, as_stream(stream), rows,
+                     block_prefix, R, stats, sign_ptrs, scales);
+  return check_launch("k_drive_pack");
+}
+
+int fjcomp_drive_pass(const fjcomp_drive_leaf* leaves, const int64_t* tile_prefix, int64_t L, int64_t tiles,
+                      int pass, const uint8_t* const* bit_ptrs, const float* scales, int64_t kb, float* ws,
+                      int64_t D, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (L < 0 || tiles < 0 || kb < 1 || D < 0 || pass < 0 || pass >= wht_passes(FJCOMP_WHT_MAX_LOG2) - 1 ||
+      (tiles && kb > INT32_MAX / tiles))
+    return fail(FJAGG_EINVAL, "drive_pass: bad sizes (L=%lld tiles=%lld kb=%lld pass=%d)", (long long)L,
+                (long long)tiles, (long long)kb, pass);
+  if (!L || !tiles) return FJAGG_OK;
+  if (!leaves || !tile_prefix || !bit_ptrs || !scales || !ws) return fail(FJAGG_EINVAL, "drive_pass: null table");
+  hipLaunchKernelGGL(k_drive_pass, dim3((unsigned)(kb * tiles)), dim3(kWhtThreads), 0, as_stream(stream), leaves,
+                     tile_prefix, L, tiles, pass, bit_ptrs, scales, ws, D);
+  return check_launch("k_drive_pass");
+}
+
+int fjcomp_drive_fold(const fjcomp_drive_leaf* leaves, const int64_t* tile_prefix, int64_t L, int64_t tiles,
+                      int single, const uint8_t* const* bit_ptrs, const uint32_t* const* sign_ptrs,
+                      const float* scales, const float* w, int64_t kb, const float* ws, int64_t D, float scale,
+                      int flags, void* stream) {
+  fjagg_g_err[0] = 0;
+  if (L < 0 || tiles < 0 || tiles > INT32_MAX || kb < 1 || D < 0)
+    return fail(FJAGG_EINVAL, "drive_fold: bad sizes (L=%lld tiles=%lld kb=%lld)", (long long)L, (long long)tiles,
+                (long long)kb);
+  if (flags & ~(FJAGG_SCALE | FJAGG_ACCUMULATE)) return fail(FJAGG_EINVAL, "drive_fold: unsupported flags %#x", flags);
+  if (!L || !tiles) return FJAGG_OK;
+  if (!leaves || !tile_prefix || !sign_ptrs || !scales || !w || (single ? !bit_ptrs : !ws))
+    return fail(FJAGG_EINVAL, "drive_fold: null table");
+  const dim3 grid((unsigned)tiles), block(kWhtThreads);
+  hipStream_t s = as_stream(stream);
+  if (single)
+    hipLaunchKernelGGL(k_drive_fold<true>, grid, block, 0, s, leaves, tile_prefix, L, bit_ptrs, sign_ptrs, scales, w,
+                       kb, ws, D, scale, flags);
+  else
+    hipLaunchKernelGGL(k_drive_fold<false>, grid, block, 0, s, leaves, tile_prefix, L, bit_ptrs, sign_ptrs, scales,
+                       w, kb, ws, D, scale, flags);
+  return check_launch("k_drive_fold");
 }
 
 }  // extern "C"

@@ -226,6 +226,45 @@ int fjcomp_wht(const fjcomp_wht_job* jobs, const int64_t* pass_prefix, int64_t J
 /* tiles of pass p for a job of 2^log2d (host helper, mirrors the kernel's tiling) */
 int64_t fjcomp_wht_tiles(int log2d, int pass);
 
+/* ---- DRIVE's transmitted form: sign bits + (sum y^2, sum |y|) per leaf ----
+ * A client sends, per leaf, the d = 2^log2d sign bits of its rotated leaf (coordinate i in byte
+ * i / 8 at bit i % 8, 1 <=> negative; ceil(d / 8) bytes, padding bits of d < 8 ignored) and
+ * scales = (A, b) = (f32(sum y^2), f32(sum |y|)). Sign s stands for (A * s) / b, the value
+ * FJCOMP_WHT_UNROTATE_DRIVE loads.
+ *
+ * fjcomp_drive_pack: the client's side. Row r (ptr: its rotated leaf, n = d floats) becomes
+ * d sign bits at sign_ptrs[r], every byte stored whole by one lane, and scales[2r .. 2r+1] from
+ * stats[r]. block_prefix: running sum of ceil(d / FJCOMP_DRIVE_PACK_BLOCK).
+ *
+ * fjcomp_drive_pass: pass `pass` (not the last) of the inverse transforms of kb clients' leaves
+ * with more than one pass, into / in place on ws[kb][D] (leaf l at ws_off). tile_prefix[L + 1]:
+ * running sum of fjcomp_wht_tiles(log2d, pass), 0 for a leaf whose last pass is <= pass; the
+ * grid is kb * tiles. Pass 0 reads the sign bits, later passes the workspace.
+ *
+ * fjcomp_drive_fold: the last pass with tree_mean's fold in its epilogue. One workgroup per
+ * (leaf, last-pass tile) walks the kb clients in order: tile from the sign bits (single != 0:
+ * leaves of one pass, tile_prefix counts 1 per such leaf and 0 otherwise) or from ws (single == 0:
+ * the others), butterflies, * Rademacher sign, / sqrt(d), fl(z * w_k) added in client order into
+ * registers. FJAGG_ACCUMULATE starts from out, FJAGG_SCALE multiplies by scale at the end. Only
+ * the leaf's first n coordinates are written. Bits: k_wht's UNROTATE_DRIVE + the dense fold's. */
+typedef struct fjcomp_drive_leaf {
+  float* out;      /* n floats */
+  int64_t n;       /* elements of the leaf (<= d) */
+  int64_t ws_off;  /* multi-pass leaf: its offset (floats) in a client's workspace row */
+  int32_t log2d;
+  float sqrt_d;    /* f32(sqrt(d)), correctly rounded */
+} fjcomp_drive_leaf;
+#define FJCOMP_DRIVE_PACK_BLOCK 2048
+int fjcomp_drive_pack(const fjcomp_row* rows, const int64_t* block_prefix, int64_t R, int64_t nblocks,
+                      const fjcomp_stats* stats, uint8_t* const* sign_ptrs, float* scales, void* stream);
+int fjcomp_drive_pass(const fjcomp_drive_leaf* leaves, const int64_t* tile_prefix, int64_t L, int64_t tiles,
+                      int pass, const uint8_t* const* bit_ptrs, const float* scales, int64_t kb, float* ws,
+                      int64_t D, void* stream);
+int fjcomp_drive_fold(const fjcomp_drive_leaf* leaves, const int64_t* tile_prefix, int64_t L, int64_t tiles,
+                      int single, const uint8_t* const* bit_ptrs, const uint32_t* const* sign_ptrs,
+                      const float* scales, const float* w, int64_t kb, const float* ws, int64_t D, float scale,
+                      int flags, void* stream);
+
 /* ---- top-k sparsified mean (fjsparse.hip) ----
  * Client k's row is its leaves back to back, P float32 elements. With the magnitude key
  * m(v) = bits(v) & 0x7fffffff compared as uint32 (|NaN| > inf > finite > subnormal > 0: a NaN is
