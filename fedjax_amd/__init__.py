@@ -12,7 +12,7 @@ from fedjax_amd import random
 from fedjax_amd import server
 from fedjax_amd import tree_util
 from fedjax_amd.dataclasses import dataclass
-from fedjax_amd.slab import ClientDeltaSlab, CodeSlab
+from fedjax_amd.slab import ClientDeltaSlab, CodeSlab, SparseSlab
 from fedjax_amd.typing import ClientId, OptState, Params, PRNGKey, PyTree
 
 __version__ = "0.1.0"

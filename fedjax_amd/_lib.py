@@ -52,6 +52,7 @@ CODES_BLOCK, CODES_BLOCK_SMALL = 4096, 1024  # FJCOMP_CODES_BLOCK, FJCOMP_CODES_
 PACKED_BLOCK, PACKED_BLOCK_SMALL = 4096, 2048  # FJCOMP_PACKED_BLOCK, FJCOMP_PACKED_BLOCK_SMALL
 DRIVE_PACK_BLOCK = 2048  # FJCOMP_DRIVE_PACK_BLOCK
 TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
+SPARSE_WAVE_TILE, SPARSE_GROUP_TILE = 1024, 4096  # FJCOMP_SPARSE_WAVE_TILE, FJCOMP_SPARSE_GROUP_TILE
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
 _i64, _i32, _f32, _vp, _u64 = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64
@@ -173,6 +174,11 @@ _SIGNATURES = {
     "fjcomp_topk_mean_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fjcomp_topk_mean_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp,
                                      _i64, _i32, _vp]),
+    "fjcomp_topk_compact_workspace_bytes": (_i64, [_i64, _i64]),
+    "fjcomp_topk_compact_dense": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "fjcomp_topk_compact_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                        _i64, _i32, _vp]),
+    "fjcomp_sparse_fold": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _i32, _vp]),
     # include/fjcomm.h
     "fjcomm_abi_version": (_i32, []),
     "fjcomm_unique_id": (_i32, [_vp]),

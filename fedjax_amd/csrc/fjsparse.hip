@@ -27,6 +27,9 @@
 // walks the clients in order with eight rows' loads in flight, and applies the same multiply, add
 // and scale as the exact fold. Built with contraction off: no multiply-add is fused.
 //
+// fjcomp_topk_compact_dense / _ptrs write the kept coordinates out as sorted (index, value) lists,
+// the form a top-k client transmits (the compaction section below; fjsparsefold.hip folds them).
+//
 // Both addressings share the kernels through a row functor: DenseRows (base, leading dimension)
 // and PtrRows (in_ptrs[K*L], leaf_n[L], chunk_prefix[L+1]); a chunk never spans two leaves, and
 // one histogram per client spans all its leaves. Float32 only.
@@ -81,6 +84,7 @@ struct DenseRows {
   }
   __device__ __forceinline__ const float* row(int64_t k, int64_t) const { return base + k * ld; }
   __device__ __forceinline__ float* out(int64_t) const { return y; }
+  __device__ __forceinline__ int64_t first(int64_t) const { return 0; }
 };
 
 struct PtrRows {
@@ -102,6 +106,12 @@ struct PtrRows {
   }
   __device__ __forceinline__ const float* row(int64_t k, int64_t leaf) const { return in_ptrs[k * L + leaf]; }
   __device__ __forceinline__ float* out(int64_t leaf) const { return out_ptrs[leaf]; }
+  // the leaf's first element in the client's row (the leaves back to back): the compaction's index base
+  __device__ __forceinline__ int64_t first(int64_t leaf) const {
+    int64_t o = 0;
+    for (int64_t l = 0; l < leaf; ++l) o += leaf_n[l];
+    return o;
+  }
 };
 
 // Four consecutive elements' bits from p[i .. i+cnt), zeros past cnt. VEC: p + i is 16-byte aligned.
@@ -275,6 +285,124 @@ __global__ __launch_bounds__(kThreads) void k_topk_fold(ROWS rows, int64_t K, co
   }
 }
 
+// ------------------------------------------------------------------ compaction (the transmitted form)
+// The kept coordinates of every row as sorted (int32 index, float32 value) lists: order-preserving
+// stream compaction against max(T_k, 1), in three launches whose order is the only ordering there
+// is (no workgroup waits on another): k_topk_count, the kept elements of every chunk;
+// k_topk_chunk_scan, one workgroup per client turns its chunk counts into first slots; k_topk_write
+// re-reads the chunk in steps of kFoldTile elements (a lane owns four consecutive ones), ranks the
+// kept elements of a wave with one ballot per element slot and popcounts below the lane, adds the
+// wave bases through LDS (two buffers, one barrier a step) and stores index and value at
+// offsets[k] + slot. Slots are integers derived from counts: two runs write the same bytes.
+template <class ROWS, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_topk_count(ROWS rows, const uint32_t* __restrict__ thr,
+                                                         uint32_t* __restrict__ counts) {
+  __shared__ uint32_t total;
+  const int64_t k = blockIdx.y;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  int64_t leaf, n, i0;
+  rows.locate(blockIdx.x, &leaf, &n, &i0);
+  const float* __restrict__ p = rows.row(k, leaf);
+  const uint32_t T = thr[k] > 1u ? thr[k] : 1u;
+  const int64_t end = i0 + kChunk < n ? i0 + kChunk : n;
+  uint32_t c = 0;
+  for (int64_t i = i0 + threadIdx.x * 4; i < end; i += kFoldTile) {
+    uint32_t v[4];
+    load4<VEC>(p, i, end - i >= 4 ? 4 : (int)(end - i), v);  // zeros past the end: never kept (T >= 1)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c += key(v[j]) >= T ? 1u : 0u;
+  }
+  if (c) atomicAdd(&total, c);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[k * gridDim.x + blockIdx.x] = total;
+}
+
+// counts[k][0 .. nchunks) -> their exclusive prefix sums, in place (a row's total is < 2^31).
+__global__ __launch_bounds__(kThreads) void k_topk_chunk_scan(uint32_t* __restrict__ counts, int64_t nchunks) {
+  __shared__ uint32_t sums[kThreads];
+  uint32_t* __restrict__ row = counts + (int64_t)blockIdx.x * nchunks;
+  const int t = threadIdx.x;
+  uint32_t carry = 0;
+  for (int64_t base = 0; base < nchunks; base += kThreads) {
+    const int64_t e = base + t;
+    const uint32_t v = e < nchunks ? row[e] : 0u;
+    sums[t] = v;
+    __syncthreads();
+    for (int d = 1; d < kThreads; d <<= 1) {
+      const uint32_t add = t >= d ? sums[t - d] : 0u;
+      __syncthreads();
+      sums[t] += add;
+      __syncthreads();
+    }
+    if (e < nchunks) row[e] = carry + sums[t] - v;
+    carry += sums[kThreads - 1];
+    __syncthreads();
+  }
+}
+
+template <class ROWS, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_topk_write(ROWS rows, const uint32_t* __restrict__ thr,
+                                                         const uint32_t* __restrict__ first_slot,
+                                                         const int64_t* __restrict__ offsets, int64_t cap,
+                                                         int32_t* __restrict__ idx_out, float* __restrict__ val_out) {
+  constexpr int kWaves = kThreads / 64;
+  __shared__ uint32_t wave_kept[2][kWaves];
+  const int64_t k = blockIdx.y;
+  int64_t leaf, n, i0;
+  rows.locate(blockIdx.x, &leaf, &n, &i0);
+  const float* __restrict__ p = rows.row(k, leaf);
+  const uint32_t T = thr[k] > 1u ? thr[k] : 1u;
+  const int64_t end = i0 + kChunk < n ? i0 + kChunk : n;
+  // the row's slots [o0, o1), clamped into the output before they form an address
+  int64_t o0 = offsets[k], o1 = offsets[k + 1];
+  o0 = o0 < 0 ? 0 : (o0 > cap ? cap : o0);
+  o1 = o1 < o0 ? o0 : (o1 > cap ? cap : o1);
+  const int64_t room = o1 - o0;
+  const int64_t index0 = rows.first(leaf);
+  int64_t run = first_slot[k * gridDim.x + blockIdx.x];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  int step = 0;
+  for (int64_t ib = i0; ib < end; ib += kFoldTile, ++step) {  // the same trip count in every lane
+    const int64_t i = ib + threadIdx.x * 4;
+    const int64_t left = end - i;
+    const int cnt = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+    if (cnt > 0) load4<VEC>(p, i, cnt, v);
+    bool keep[4];
+    uint32_t rank = 0, kept = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      keep[j] = key(v[j]) >= T;
+      const uint64_t b = __ballot(keep[j]);
+      rank += (uint32_t)__popcll(b & below);
+      kept += (uint32_t)__popcll(b);
+    }
+    if (lane == 0) wave_kept[step & 1][wave] = kept;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      const uint32_t c = wave_kept[step & 1][w];
+      before += w < wave ? c : 0u;
+      all += c;
+    }
+    int64_t slot = run + before + rank;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (keep[j]) {
+        if (slot < room) {
+          idx_out[o0 + slot] = (int32_t)(index0 + i + j);
+          val_out[o0 + slot] = __uint_as_float(v[j]);
+        }
+        ++slot;
+      }
+    }
+    run += all;
+  }
+}
+
 // ------------------------------------------------------------------ launchers
 struct Ws {
   uint32_t *hist, *prefix, *rank;
@@ -315,6 +443,41 @@ int run_fold(const ROWS& rows, bool vec, int64_t K, int64_t nchunks, const float
   if (vec) hipLaunchKernelGGL((k_topk_fold<ROWS, true>), grid, dim3(kThreads), 0, s, rows, K, w, t, scale);
   else hipLaunchKernelGGL((k_topk_fold<ROWS, false>), grid, dim3(kThreads), 0, s, rows, K, w, t, scale);
   return launched("k_topk_fold");
+}
+
+template <class ROWS>
+int run_compact(const ROWS& rows, bool vec, int64_t K, int64_t nchunks, const float* thr, const int64_t* offsets,
+                int64_t cap, int32_t* idx, float* val, void* ws_dev, hipStream_t s) {
+  const dim3 grid((unsigned)nchunks, (unsigned)K);
+  const uint32_t* t = reinterpret_cast<const uint32_t*>(thr);
+  uint32_t* counts = static_cast<uint32_t*>(ws_dev);
+  if (vec) hipLaunchKernelGGL((k_topk_count<ROWS, true>), grid, dim3(kThreads), 0, s, rows, t, counts);
+  else hipLaunchKernelGGL((k_topk_count<ROWS, false>), grid, dim3(kThreads), 0, s, rows, t, counts);
+  hipLaunchKernelGGL(k_topk_chunk_scan, dim3((unsigned)K), dim3(kThreads), 0, s, counts, nchunks);
+  if (vec)
+    hipLaunchKernelGGL((k_topk_write<ROWS, true>), grid, dim3(kThreads), 0, s, rows, t, counts, offsets, cap, idx, val);
+  else
+    hipLaunchKernelGGL((k_topk_write<ROWS, false>), grid, dim3(kThreads), 0, s, rows, t, counts, offsets, cap, idx, val);
+  return launched("k_topk_count / k_topk_chunk_scan / k_topk_write");
+}
+
+// What the compaction entries check before any launch.
+int check_compact(const char* what, int in_dtype, int64_t K, int64_t P, int64_t nchunks, const void* thr,
+                  const void* offsets, int64_t cap, const void* idx, const void* val, const void* ws,
+                  int64_t ws_bytes) {
+  if (in_dtype != FJAGG_F32) return refuse(FJAGG_EUNSUPPORTED, "%s: float32 deltas only", what);
+  if (K < 1) return refuse(FJAGG_EINVAL, "%s: K must be >= 1 (got %lld)", what, (long long)K);
+  if (K > kMaxClients)
+    return refuse(FJAGG_EUNSUPPORTED, "%s: K <= %d clients (got %lld)", what, kMaxClients, (long long)K);
+  if (P < 0) return refuse(FJAGG_EINVAL, "%s: P must be >= 0 (got %lld)", what, (long long)P);
+  if (P >= (1ll << 31)) return refuse(FJAGG_EUNSUPPORTED, "%s: P < 2^31 elements per client (got %lld)", what, (long long)P);
+  if (cap < 0) return refuse(FJAGG_EINVAL, "%s: the output capacity must be >= 0 (got %lld)", what, (long long)cap);
+  if (P == 0 || cap == 0) return FJAGG_OK;
+  if (!thr || !offsets || !idx || !val || !ws) return refuse(FJAGG_EINVAL, "%s: null pointer argument", what);
+  if (ws_bytes < fjcomp_topk_compact_workspace_bytes(K, nchunks))
+    return refuse(FJAGG_EINVAL, "%s: workspace too small (need %lld bytes)", what,
+                  (long long)fjcomp_topk_compact_workspace_bytes(K, nchunks));
+  return FJAGG_OK;
 }
 
 // What every entry checks before any launch. P == 0 is the caller's to skip (nothing to launch).
@@ -419,6 +582,42 @@ int fjcomp_topk_mean_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, 
   const bool vec = !(flags & FJAGG_UNALIGNED);
   if (int rc = run_select(rows, vec, K, nchunks, c, thresholds_dev, sent_dev, ws_dev, s)) return rc;
   return run_fold(rows, vec, K, nchunks, w_dev, thresholds_dev, scale, s);
+}
+
+int64_t fjcomp_topk_compact_workspace_bytes(int64_t K, int64_t nchunks) {
+  if (K < 1 || nchunks < 1) return 0;
+  return K * nchunks * (int64_t)sizeof(uint32_t);
+}
+
+int fjcomp_topk_compact_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                              const float* thresholds_dev, const int64_t* offsets_dev, int64_t capacity,
+                              int32_t* indices_dev, float* values_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  const char* what = "topk_compact_dense";
+  const int64_t nchunks = P > 0 ? (P + kChunk - 1) / kChunk : 0;
+  if (int rc = check_compact(what, in_dtype, K, P, nchunks, thresholds_dev, offsets_dev, capacity, indices_dev,
+                             values_dev, ws_dev, ws_bytes))
+    return rc;
+  if (P == 0 || capacity == 0) return FJAGG_OK;
+  if (int rc = check_dense(what, x_dev, ld, K, P)) return rc;
+  const DenseRows rows{static_cast<const float*>(x_dev), K > 1 ? ld : P, P, nullptr};
+  const bool vec = aligned16(x_dev) && (K == 1 || ld % 4 == 0);
+  return run_compact(rows, vec, K, nchunks, thresholds_dev, offsets_dev, capacity, indices_dev, values_dev, ws_dev,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
+int fjcomp_topk_compact_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, int64_t L, const int64_t* leaf_n,
+                             const int64_t* chunk_prefix, int64_t nchunks, int64_t P, const float* thresholds_dev,
+                             const int64_t* offsets_dev, int64_t capacity, int32_t* indices_dev, float* values_dev,
+                             void* ws_dev, int64_t ws_bytes, int flags, void* stream) {
+  const char* what = "topk_compact_ptrs";
+  if (int rc = check_compact(what, in_dtype, K, P, nchunks, thresholds_dev, offsets_dev, capacity, indices_dev,
+                             values_dev, ws_dev, ws_bytes))
+    return rc;
+  if (P == 0 || capacity == 0) return FJAGG_OK;
+  if (int rc = check_ptrs(what, in_ptrs, L, leaf_n, chunk_prefix, nchunks, P, flags)) return rc;
+  const PtrRows rows{in_ptrs, nullptr, leaf_n, chunk_prefix, L};
+  return run_compact(rows, !(flags & FJAGG_UNALIGNED), K, nchunks, thresholds_dev, offsets_dev, capacity,
+                     indices_dev, values_dev, ws_dev, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -2198,6 +2198,143 @@ def topk_mean_ptrs(tables: TopKTables, c: int, *, scale: float):
     return thr, sent
 
 
+SPARSE_WAVE_TILE = _lib.SPARSE_WAVE_TILE  # output coordinates a wave of the sparse fold accumulates in LDS
+SPARSE_GROUP_TILE = _lib.SPARSE_GROUP_TILE  # ... and a workgroup of four waves owns
+
+
+def _topk_compact_workspace(dev: torch.device, K: int, nchunks: int) -> torch.Tensor:
+    """The compaction's chunk counts, in the select's cached workspace (:func:`_topk_workspace`)
+    grown to hold them: the thresholds are read from their own tensor, and the stream orders the
+    two uses."""
+    need = int(_lib.load().fjcomp_topk_compact_workspace_bytes(K, nchunks))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 4096), dtype=torch.uint8, device=dev)
+    ws = _topk_workspace(dev, K)
+    if ws.numel() < need:
+        ws = _TOPK_WS[(dev.index, _stream_handle(dev))] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def sparse_offsets(sent: torch.Tensor) -> torch.Tensor:
+    """``offsets`` int64 [K + 1] of the compaction from the select's ``sent``: its running sum, on
+    the device with torch ops (no synchronisation)."""
+    off = torch.zeros(sent.numel() + 1, dtype=torch.int64, device=sent.device)
+    off[1:] = torch.cumsum(sent, 0, dtype=torch.int64)
+    return off
+
+
+def _check_compact_args(K: int, thr, offsets, indices, values) -> int:
+    _f32_vector("thresholds", thr, K)
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (K + 1,) \
+            or not offsets.is_contiguous():
+        raise TypeError(f"offsets must be a contiguous int64 tensor of {K + 1} elements")
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32:
+        raise TypeError("indices must be an int32 tensor")
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32:
+        raise TypeError("values must be a float32 tensor")
+    if indices.dim() != 1 or values.dim() != 1 or indices.numel() != values.numel() \
+            or not indices.is_contiguous() or not values.is_contiguous():
+        raise ValueError("indices and values must be contiguous 1-D tensors of one length")
+    return indices.numel()
+
+
+def topk_compact_dense(x: torch.Tensor, thresholds: torch.Tensor, offsets: torch.Tensor, indices: torch.Tensor,
+                       values: torch.Tensor) -> None:
+    """The transmitted form of a float32 slab ``x[K, P]``: row ``k``'s coordinates with magnitude
+    key ``>= max(T_k, 1)`` as sorted ``(index, value)`` pairs at ``offsets[k] .. offsets[k + 1]`` of
+    ``indices`` (int32) and ``values`` (float32). ``thresholds`` is :func:`topk_select_dense`'s,
+    ``offsets`` :func:`sparse_offsets` of its ``sent`` (device int64 [K + 1]); the outputs hold at
+    least ``sum(sent)`` elements, and nothing is written outside them whatever the table holds.
+    Three launches, no host synchronisation (``fjcomp_topk_compact_dense``)."""
+    K, P = _check_topk_slab(x)
+    cap = _check_compact_args(K, thresholds, offsets, indices, values)
+    dev = _require_device(x, thresholds, offsets, indices, values)
+    if P == 0 or cap == 0:
+        return
+    ws = _topk_compact_workspace(dev, K, (P + TOPK_CHUNK - 1) // TOPK_CHUNK)
+    ld = x.stride(0) if K > 1 else P
+    _lib.call("fjcomp_topk_compact_dense", _lib.F32, x.data_ptr(), ld, K, P, thresholds.data_ptr(),
+              offsets.data_ptr(), cap, indices.data_ptr(), values.data_ptr(), ws.data_ptr(), ws.numel(),
+              _stream_handle(dev))
+
+
+def topk_compact_ptrs(tables: TopKTables, thresholds: torch.Tensor, offsets: torch.Tensor, indices: torch.Tensor,
+                      values: torch.Tensor) -> None:
+    """:func:`topk_compact_dense` over uploaded :class:`TopKTables`: an index counts the elements
+    of the client's row, its ``L`` leaves back to back (``fjcomp_topk_compact_ptrs``)."""
+    if not isinstance(tables, TopKTables) or not hasattr(tables, "image_dev"):
+        raise TypeError("tables must be uploaded TopKTables")
+    cap = _check_compact_args(tables.K, thresholds, offsets, indices, values)
+    dev = _require_device(tables.image_dev, thresholds, offsets, indices, values)
+    if tables.P == 0 or cap == 0:
+        return
+    ws = _topk_compact_workspace(dev, tables.K, tables.nchunks)
+    _lib.call("fjcomp_topk_compact_ptrs", _lib.F32, tables.in_p, tables.K, tables.L, tables.n_p, tables.prefix_p,
+              tables.nchunks, tables.P, thresholds.data_ptr(), offsets.data_ptr(), cap, indices.data_ptr(),
+              values.data_ptr(), ws.data_ptr(), ws.numel(), _lib.UNALIGNED if tables.unaligned else 0,
+              _stream_handle(dev))
+
+
+class SparseTables:
+    """The device tables of :func:`sparse_fold` on the host, one int64 image ``idx_ptrs[K] |
+    val_ptrs[K] | counts[K] | w`` (the float32 weights packed two to a word, absent when the fold
+    is given a weight vector of its own)."""
+
+    def __init__(self, idx_ptrs, val_ptrs, counts, P: int, w=None):
+        idx_ptrs, val_ptrs, counts = (np.asarray(a, dtype=np.int64) for a in (idx_ptrs, val_ptrs, counts))
+        self.K = check_topk_clients(idx_ptrs.size)
+        if not idx_ptrs.shape == val_ptrs.shape == counts.shape == (self.K,):
+            raise ValueError(f"idx_ptrs, val_ptrs and counts must each hold {self.K} entries")
+        self.P = int(P)
+        if not 0 <= self.P <= TOPK_MAX_PARAMS:
+            raise ValueError(f"the sparse fold supports 0 <= P < 2^31 coordinates, got P = {P}")
+        if (counts < 0).any() or (counts > self.P).any():
+            raise ValueError(f"a client's list holds between 0 and P = {self.P} coordinates")
+        words = np.zeros(0, np.int64)
+        if w is not None:
+            w = np.asarray(w, dtype=np.float32)
+            if w.shape != (self.K,):
+                raise ValueError(f"need {self.K} weights, got {w.size}")
+            words = np.zeros((self.K + 1) // 2, dtype=np.int64)
+            words.view(np.float32)[: self.K] = w
+        self.has_w = w is not None
+        self.host = np.concatenate([idx_ptrs, val_ptrs, counts, words])
+
+    def upload(self, device: torch.device) -> "SparseTables":
+        """The image on ``device`` through the pinned upload (refused under stream capture)."""
+        self.image_dev = _lib.upload(torch.from_numpy(self.host), device)
+        base, K = self.image_dev.data_ptr(), self.K
+        self.idx_p, self.val_p, self.cnt_p, self.w_p = base, base + 8 * K, base + 16 * K, base + 24 * K
+        return self
+
+
+def sparse_fold(tables: SparseTables, *, scale: float, out: torch.Tensor, w: Optional[torch.Tensor] = None):
+    """``tree_mean`` folded from K clients' sorted ``(index, value)`` lists into the flat float32
+    ``out[P]``, every element written: per coordinate ``s = +0``, then ``s = fl(s + fl(v * w_k))``
+    for the clients that sent it, in client order, and ``out = fl(s * f32(scale))``, the multiply
+    and the add separate (``fjcomp_sparse_fold``; one launch, no workspace, no host step, no
+    atomics). ``w``: a device float32 [K] vector, or ``None`` for the weights the tables were made
+    with. An index outside ``[0, P)`` is ignored; an unsorted list gives an unspecified, in-bounds
+    result. Returns ``out``."""
+    if not isinstance(tables, SparseTables) or not hasattr(tables, "image_dev"):
+        raise TypeError("tables must be uploaded SparseTables")
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+        raise TypeError("out must be a float32 tensor")
+    if out.dim() != 1 or out.numel() != tables.P or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of {tables.P} elements")
+    if w is None:
+        if not tables.has_w:
+            raise ValueError("sparse_fold needs weights: in the tables or as w")
+        dev, w_p = _require_device(tables.image_dev, out), tables.w_p
+    else:
+        _f32_vector("w", w, tables.K)
+        dev, w_p = _require_device(tables.image_dev, out, w), w.data_ptr()
+    if tables.P:
+        _lib.call("fjcomp_sparse_fold", tables.idx_p, tables.val_p, tables.cnt_p, tables.K, tables.P, w_p,
+                  float(np.float32(scale)), out.data_ptr(), 0, _stream_handle(dev))
+    return out
+
+
 def fill_synth(x: torch.Tensor, *, k0: int = 0, seed: int = 0, amp: float = 0.01) -> torch.Tensor:
     """Synthetic deltas x[k, p] = amp * u(seed, k0 + k, p) (tests/bench only)."""
     if x.dim() != 2 or x.stride(1) != 1:

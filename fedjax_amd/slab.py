@@ -854,6 +854,19 @@ class ClientDeltaSlab:
         flat, thr, sent = kernels.topk_mean_dense(self.rows, w_dev, c, scale=scale, out=out)
         return tree_util.TopKMean(self.unflatten(flat), thr, sent)
 
+    def topk_encode(self, k) -> "SparseSlab":
+        """The slab's rows in top-k's transmitted form, a :class:`SparseSlab`: the select of
+        :meth:`topk_thresholds`, then one order-preserving compaction of all K rows. The lists'
+        lengths are read back once to size them (one host synchronisation: not capturable)."""
+        kernels.refuse_capture("topk_encode", "it reads the numbers of kept coordinates back to size the lists")
+        c = self._topk_keep("topk_encode", k)
+        if c == 0:
+            thr = torch.zeros(self.num_clients, dtype=torch.float32, device=self.device)
+            sent = torch.zeros_like(thr, dtype=torch.int32)
+        else:
+            thr, sent = kernels.topk_select_dense(self.rows, c)
+        return SparseSlab(self, thr, sent)
+
     def l2_norms(self) -> torch.Tensor:
         """Per-client delta l2 norms (float32[K]) in one pass over the slab."""
         return torch.sqrt(kernels.l2_squared_dense(self.rows))
@@ -996,4 +1009,63 @@ class CodeSlab:
         return pytree.unflatten(self.treedef, views)
 
 
-__all__ = ["ClientDeltaSlab", "CodeSlab"]
+class SparseSlab:
+    """K top-k sparsified client deltas in their transmitted form, made by
+    :meth:`ClientDeltaSlab.topk_encode`: ``indices`` (int32) and ``values`` (float32), the sorted
+    ``(index, value)`` lists of all clients back to back; ``offsets``, device int64 ``[K + 1]``,
+    client k's list being ``offsets[k] .. offsets[k + 1]``; and the select's ``thresholds`` and
+    ``sent``. :meth:`mean` is ``tree_mean`` over the sparsified deltas folded straight from the
+    lists: it reads ``8 * nnz`` bytes where :meth:`ClientDeltaSlab.topk_mean` reads the dense slab
+    four times. Building it costs one host synchronisation (the offsets are read back to size the
+    lists and to lay out the fold's pointer tables, which are uploaded here, once)."""
+
+    def __init__(self, delta_slab: ClientDeltaSlab, thresholds: torch.Tensor, sent: torch.Tensor):
+        self.treedef, self.shapes, self.sizes = delta_slab.treedef, delta_slab.shapes, delta_slab.sizes
+        self.leaf_offsets, self.num_params = delta_slab.offsets, delta_slab.num_params
+        self.num_clients, self.device = delta_slab.num_clients, delta_slab.device
+        self.thresholds, self.sent = thresholds, sent
+        self.offsets = kernels.sparse_offsets(sent)
+        self.host_offsets = self.offsets.cpu().numpy()  # the one synchronisation
+        self.nnz = int(self.host_offsets[-1])
+        self.indices = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        self.values = torch.empty(self.nnz, dtype=torch.float32, device=self.device)
+        kernels.topk_compact_dense(delta_slab.rows, thresholds, self.offsets, self.indices, self.values)
+        self._weights = None
+        self._tables = kernels.SparseTables(
+            self.indices.data_ptr() + 4 * self.host_offsets[:-1], self.values.data_ptr() + 4 * self.host_offsets[:-1],
+            np.diff(self.host_offsets), self.num_params).upload(self.device)
+
+    _kept = CodeSlab._kept
+
+    def client(self, k: int):
+        """Client k as a :class:`~fedjax_amd.aggregators.SparseDelta` of views into the slab."""
+        from fedjax_amd.aggregators.compression import SparseDelta
+
+        a, b = int(self.host_offsets[k]), int(self.host_offsets[k + 1])
+        return SparseDelta(self.indices[a:b], self.values[a:b], tuple(self.shapes))
+
+    def mean(self, weights: Sequence, out: Optional[torch.Tensor] = None) -> PyTree:
+        """Weighted mean of the K sparsified rows: ``tree_mean`` with the reference's W and f32(1/W),
+        one launch over the lists (:func:`kernels.sparse_fold`), bit for bit
+        :meth:`ClientDeltaSlab.topk_mean`'s mean wherever that is not a ``-0``. Returns the
+        template's pytree of float32 views into ``out`` (flat float32, ``num_params`` elements;
+        allocated when ``None``). The weight vector is uploaded on the first call and kept, so a
+        later call with the same weights uploads nothing and can be captured into a graph."""
+        if len(weights) != self.num_clients:
+            raise ValueError(f"need {self.num_clients} weights, got {len(weights)}")
+        W, hw = 0.0, []
+        for x in weights:
+            x = tree_util._host_weight(x)
+            hw.append(np.float32(x))
+            W += x
+        scale = tree_util._inverse(W)
+        if out is None:
+            out = torch.empty(self.num_params, dtype=torch.float32, device=self.device)
+        w = np.array(hw, dtype=np.float32)
+        w_dev = self._kept("_weights", w.tobytes(), lambda: _lib.upload(torch.from_numpy(w), self.device))
+        kernels.sparse_fold(self._tables, scale=scale, out=out, w=w_dev)
+        views = [out[o:o + n].view(s) for o, n, s in zip(self.leaf_offsets[:-1], self.sizes, self.shapes)]
+        return pytree.unflatten(self.treedef, views)
+
+
+__all__ = ["ClientDeltaSlab", "CodeSlab", "SparseSlab"]

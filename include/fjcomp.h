@@ -300,6 +300,51 @@ int fjcomp_topk_mean_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, 
                           float scale, float* const* out_ptrs, float* thresholds_dev, int32_t* sent_dev, void* ws_dev,
                           int64_t ws_bytes, int flags, void* stream);
 
+/* ---- top-k's transmitted form: sorted (index, value) lists ----
+ * A top-k client sends the coordinates it keeps, those with m(x) >= max(T_k, 1) (zeros are never
+ * sent), as n = sent[k] pairs: indices, int32, strictly increasing, an index counting the elements
+ * of the client's row as above (the leaves back to back); and values, float32, the elements
+ * verbatim.
+ *
+ * fjcomp_topk_compact_dense / _ptrs: the client's side, rows addressed as in fjcomp_topk_select_*
+ * and thresholds_dev from that call. Order-preserving stream compaction in three launches (the
+ * kept elements of every FJCOMP_TOPK_CHUNK chunk; one scan of the chunk counts per row; a write
+ * pass that ranks the kept elements with wave ballots), ordered by the launch boundaries alone.
+ * Row k's pairs go to indices_dev / values_dev at offsets_dev[k] .. offsets_dev[k + 1]
+ * (int64 [K + 1], device: the running sum of sent). Every offset is clamped into [0, capacity]
+ * before it forms an address and a row writes no slot at or past its end, so a table that
+ * disagrees with the thresholds truncates rows but never writes outside the capacity elements
+ * of either output. Two calls write the same bytes. The workspace
+ * (fjcomp_topk_compact_workspace_bytes(K, nchunks) bytes, nchunks = ceil(P / FJCOMP_TOPK_CHUNK) for
+ * _dense) needs no initialisation. P == 0 or capacity == 0 launches nothing.
+ *
+ * fjcomp_sparse_fold: the server's side, tree_mean from K such lists in one launch with no
+ * workspace and no host step. idx_ptrs[K], val_ptrs[K] and counts[K] (int64) are device tables,
+ * w_dev[K] the float32 weights, out_dev flat float[P] (every element is written). Per coordinate
+ *   s = +0;  for every client that sent it, in client order: s = fl(s + fl(v * w_k));
+ *   out = fl(s * scale)
+ * the multiply and the add separate. For finite weights this is the masked fold of
+ * fjcomp_topk_mean_* over the same clients, bit for bit wherever the result is not a zero. It
+ * yields +0 in the one place the masked fold can yield -0: every term of the coordinate is a zero
+ * and the first of them is -0. The output is partitioned (a workgroup owns
+ * FJCOMP_SPARSE_GROUP_TILE coordinates, each of its four waves FJCOMP_SPARSE_WAVE_TILE of them in
+ * LDS), so there are no atomics on the result and two calls give the same bits. An entry is
+ * applied only if its index lies in the tile being formed: an index outside [0, P) is ignored,
+ * an unsorted list gives an unspecified but in-bounds result, and a count is clamped to [0, P].
+ * 1 <= K <= FJCOMP_TOPK_MAX_CLIENTS, P < 2^31, flags must be 0. */
+#define FJCOMP_SPARSE_WAVE_TILE 1024
+#define FJCOMP_SPARSE_GROUP_TILE 4096
+int64_t fjcomp_topk_compact_workspace_bytes(int64_t K, int64_t nchunks);
+int fjcomp_topk_compact_dense(int in_dtype, const void* x_dev, int64_t ld, int64_t K, int64_t P,
+                              const float* thresholds_dev, const int64_t* offsets_dev, int64_t capacity,
+                              int32_t* indices_dev, float* values_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+int fjcomp_topk_compact_ptrs(int in_dtype, const float* const* in_ptrs, int64_t K, int64_t L, const int64_t* leaf_n,
+                             const int64_t* chunk_prefix, int64_t nchunks, int64_t P, const float* thresholds_dev,
+                             const int64_t* offsets_dev, int64_t capacity, int32_t* indices_dev, float* values_dev,
+                             void* ws_dev, int64_t ws_bytes, int flags, void* stream);
+int fjcomp_sparse_fold(const int32_t* const* idx_ptrs, const float* const* val_ptrs, const int64_t* counts, int64_t K,
+                       int64_t P, const float* w_dev, float scale, float* out_dev, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
