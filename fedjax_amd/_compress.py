@@ -15,6 +15,8 @@ shapes of ``fedjax/aggregators/compression.py``:
 * ``drive_signs_mean`` the same mean from transmitted sign bits and scales: signs ->
                        inverse WHT from the bits, the fold in its last pass
                        (``drive_encode`` is the client's side)
+* ``sign_vote``        signSGD's majority vote (or the mean of the signs) from one sign bit per
+                       coordinate, counted in bit-sliced integers (``sign_pack`` is the client's side)
 
 Everything is asynchronous on torch's current stream; only the arithmetic-coding
 bit count (``hist=True``) reads results back. Device work is batched over clients
@@ -333,6 +335,85 @@ def codes_mean(codes: List[List[torch.Tensor]], minmax: torch.Tensor, w: np.ndar
                        np.array([o.data_ptr() for o in outs], dtype=np.uint64), device, bits)
     w_dev = _lib.upload(torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)), device)
     tables.launch(minmax.data_ptr(), w_dev.data_ptr(), scale, num_levels)
+
+
+# ----------------------------------------------------------------------------- sign bits, majority vote
+def check_vote_clients(K: int) -> int:
+    """The client counts k_sign_vote's 13 bit planes hold: 1 .. 4096."""
+    if not 1 <= int(K) <= _lib.VOTE_MAX_CLIENTS:
+        raise ValueError(f"the majority vote takes 1 <= K <= {_lib.VOTE_MAX_CLIENTS} clients, got {int(K)}")
+    return int(K)
+
+
+def check_vote_output(output) -> int:
+    if output not in ("sign", "mean"):
+        raise ValueError(f"output must be 'sign' or 'mean', got {output!r}")
+    return _lib.VOTE_SIGN if output == "sign" else _lib.VOTE_MEAN
+
+
+class SignPack:
+    """The device tables of one k_sign_pack launch (float32 row pointers [R], row sizes, block
+    prefix, output pointers [R]), uploaded once: :meth:`launch` uploads nothing."""
+
+    def __init__(self, in_ptrs: np.ndarray, row_n: np.ndarray, sign_ptrs: np.ndarray, device: torch.device):
+        row_n = np.ascontiguousarray(row_n, dtype=np.int64).reshape(-1)
+        self.R, self.device = row_n.size, device
+        prefix = _block_prefix(row_n, _lib.SIGN_PACK_BLOCK)
+        self.nblocks = int(prefix[-1])
+        self._up = Upload()
+        o = [self._up.add(np.ascontiguousarray(in_ptrs, dtype=np.uint64)), self._up.add(row_n), self._up.add(prefix),
+             self._up.add(np.ascontiguousarray(sign_ptrs, dtype=np.uint64))]
+        base = self._up.commit(device)
+        self._in, self._n, self._prefix, self._out = (base + x for x in o)
+
+    def launch(self) -> None:
+        _lib.call("fjcomp_sign_pack", self._in, self.R, self._n, self._prefix, self.nblocks, self._out,
+                  _stream(self.device))
+
+
+def sign_pack(rows: List[torch.Tensor]) -> List[torch.Tensor]:
+    """k_sign_pack over float32 device rows: per row a 1-D uint8 tensor of ``ceil(n / 8)`` bytes,
+    bit ``i % 8`` of byte ``i // 8`` set where element ``i`` is ``< 0``. One launch, one upload."""
+    device = rows[0].device
+    ns = np.array([x.numel() for x in rows], dtype=np.int64)
+    bits = [torch.empty(int(packed_bytes(int(n), 1)), dtype=torch.uint8, device=device) for n in ns]
+    SignPack(np.array([x.data_ptr() for x in rows], dtype=np.uint64), ns,
+             np.array([b.data_ptr() for b in bits], dtype=np.uint64), device).launch()
+    return bits
+
+
+class SignVote:
+    """The device tables of one k_sign_vote launch shape (bit-row pointers [K, L], leaf sizes in
+    elements, block prefix, output pointers [L]), uploaded once: :meth:`launch` uploads nothing
+    and every call reads the bits afresh."""
+
+    def __init__(self, bit_ptrs: np.ndarray, leaf_n: np.ndarray, out_ptrs: np.ndarray, device: torch.device):
+        self.K, self.L = bit_ptrs.shape
+        check_vote_clients(self.K)
+        self.device = device
+        leaf_n = np.ascontiguousarray(leaf_n, dtype=np.int64)
+        prefix = _block_prefix(leaf_n, _lib.VOTE_TILE)
+        self.nblocks = int(prefix[-1])
+        self._up = Upload()
+        o = [self._up.add(np.ascontiguousarray(bit_ptrs, dtype=np.uint64)), self._up.add(leaf_n),
+             self._up.add(prefix), self._up.add(np.ascontiguousarray(out_ptrs, dtype=np.uint64))]
+        base = self._up.commit(device)
+        self._bits, self._n, self._prefix, self._outs = (base + x for x in o)
+        # f32(1 / K) as _weights forms f32(1 / W): the float64 quotient, rounded once
+        self.scale = float(np.float32(1.0 / self.K))
+
+    def launch(self, mode: int) -> None:
+        _lib.call("fjcomp_sign_vote", self._bits, self.K, self.L, self._n, self._prefix, self.nblocks, int(mode),
+                  self.scale, self._outs, _stream(self.device))
+
+
+def sign_vote(bits: List[List[torch.Tensor]], mode: int, outs: List[torch.Tensor]) -> None:
+    """k_sign_vote over bits [K][L] (1-D uint8 device rows of ``ceil(n / 8)`` bytes, the leaf sizes
+    those of ``outs``): outs[l] = the majority's sign (``VOTE_SIGN``) or the mean of the signs
+    (``VOTE_MEAN``, ``fl(f32(K - 2c) * f32(1 / K))``). One launch, one upload."""
+    SignVote(np.array([[x.data_ptr() for x in r] for r in bits], dtype=np.uint64).reshape(len(bits), len(outs)),
+             np.array([o.numel() for o in outs], dtype=np.int64),
+             np.array([o.data_ptr() for o in outs], dtype=np.uint64), outs[0].device).launch(mode)
 
 
 def rademacher_words(keys: np.ndarray, ds: Sequence[int], device: torch.device,

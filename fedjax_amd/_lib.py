@@ -53,6 +53,9 @@ PACKED_BLOCK, PACKED_BLOCK_SMALL = 4096, 2048  # FJCOMP_PACKED_BLOCK, FJCOMP_PAC
 DRIVE_PACK_BLOCK = 2048  # FJCOMP_DRIVE_PACK_BLOCK
 TOPK_CHUNK, TOPK_MAX_CLIENTS = 16384, 4096
 SPARSE_WAVE_TILE, SPARSE_GROUP_TILE = 1024, 4096  # FJCOMP_SPARSE_WAVE_TILE, FJCOMP_SPARSE_GROUP_TILE
+VOTE_SIGN, VOTE_MEAN = 0, 1  # FJCOMP_VOTE_SIGN, FJCOMP_VOTE_MEAN
+VOTE_TILE, VOTE_MAX_CLIENTS = 8192, 4096  # FJCOMP_VOTE_TILE, FJCOMP_VOTE_MAX_CLIENTS
+SIGN_PACK_BLOCK = 2048  # FJCOMP_SIGN_PACK_BLOCK
 
 # every symbol include/fjagg.h declares: (name, restype, argtypes)
 _i64, _i32, _f32, _vp, _u64 = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64
@@ -179,6 +182,8 @@ _SIGNATURES = {
     "fjcomp_topk_compact_ptrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
                                         _i64, _i32, _vp]),
     "fjcomp_sparse_fold": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _i32, _vp]),
+    "fjcomp_sign_pack": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "fjcomp_sign_vote": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
     # include/fjcomm.h
     "fjcomm_abi_version": (_i32, []),
     "fjcomm_unique_id": (_i32, [_vp]),

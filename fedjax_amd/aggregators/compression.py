@@ -750,8 +750,104 @@ def sparse_mean_aggregator(template: Optional[PyTree] = None) -> aggregator.Aggr
     return aggregator.Aggregator(init, apply)
 
 
+# ----------------------------------------------------------------------------- sign bits, majority vote
+@dataclasses.dataclass
+class SignDelta:
+    """A delta as a signSGD client transmits it: ``signs``, a pytree shaped like the delta whose
+    every leaf is a 1-D uint8 tensor of ``ceil(n / 8)`` bytes: coordinate ``i`` of the flattened
+    leaf in byte ``i // 8`` at bit ``i % 8``, low bit first (``pack_codes(codes, 1)``'s order), 1
+    exactly where the value is ``< 0`` (``+0``, ``-0`` and NaN are sent as 0; the padding bits of
+    the last byte are written as 0 and ignored by the server); ``shapes``, the delta's leaf shapes
+    in flatten order."""
+    signs: Any
+    shapes: Tuple[Tuple[int, ...], ...] = _field(metadata={"pytree_node": False})
+
+
+def sign_encode_pytree(params: PyTree) -> SignDelta:
+    """The client side of :func:`majority_vote_aggregator`: one bit per coordinate, written packed
+    by one launch over all leaves, with no host synchronisation. Float32 leaves (int32 leaves are
+    converted; bfloat16 raises ``TypeError``)."""
+    kernels.refuse_capture("sign_encode_pytree", "it uploads the leaf table through a pinned staging buffer")
+    td, rows = _rows([params])
+    shapes = tuple(tuple(x.shape) for x in rows[0])
+    if not rows[0]:
+        return SignDelta(pytree.unflatten(td, []), shapes)
+    return SignDelta(pytree.unflatten(td, C.sign_pack([x.contiguous() for x in rows[0]])), shapes)
+
+
+def _sign_rows(deltas: Sequence[Any], shapes=None):
+    """(treedef, sign leaves [K][L], shapes) of SignDelta clients after every check the kernel relies
+    on: one structure, equal ``shapes`` (``shapes``, default client 0's) and 1-D uint8 leaves of
+    ``ceil(n / 8)`` bytes."""
+    td, rows = None, []
+    for k, d in enumerate(deltas):
+        if not isinstance(d, SignDelta):
+            raise TypeError(f"client {k}: expected a SignDelta, got {type(d).__name__}")
+        if td is None:
+            leaves, td = pytree.flatten(d.signs)
+        else:
+            leaves = pytree.flatten_as(td, d.signs)
+        mine = tuple(tuple(int(v) for v in sh) for sh in d.shapes)
+        if shapes is None:
+            shapes = mine
+        if mine != tuple(tuple(sh) for sh in shapes):
+            raise ValueError(f"client {k} has leaf shapes {mine}, expected {tuple(shapes)}")
+        if len(leaves) != len(shapes):
+            raise ValueError(f"client {k} has {len(leaves)} leaves, expected {len(shapes)}")
+        for l, (x, sh) in enumerate(zip(leaves, shapes)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+                raise TypeError(f"client {k} leaf {l}: sign bits must be uint8 tensors, got "
+                                f"{x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
+            want = (C.packed_bytes(int(np.prod(sh, dtype=np.int64)), 1),)
+            if tuple(x.shape) != want:
+                raise ValueError(f"client {k} leaf {l} has shape {tuple(x.shape)}, expected {want}")
+        rows.append(leaves)
+    return td, rows, shapes
+
+
+def majority_vote_aggregator(output: str = "sign", template: Optional[PyTree] = None) -> aggregator.Aggregator:
+    """signSGD with majority vote (Bernstein et al., ICLR 2019), the server side of a round whose
+    clients transmit :class:`SignDelta`: ``apply`` takes ``(client_id, SignDelta, weight)`` triples.
+    The weights are ignored, as in every robust rule here: a client must not scale its own vote.
+    Per coordinate, with ``c`` of the ``K`` clients sending a 1 (negative):
+
+    * ``output="sign"``: float32 ``-1.0`` if ``2c > K``, ``+1.0`` if ``2c < K``, ``+0.0`` on a tie;
+    * ``output="mean"``: the mean of the clients' signs, ``fl(f32(K - 2c) * f32(1 / K))``.
+
+    One launch counts the bits in bit-sliced integer counters (``fjcomp_sign_vote``), so the result
+    does not depend on any order and two rounds over the same bits agree bit for bit. The state is
+    a :class:`CompressionState` whose ``num_bits`` grows by ``F32(P)`` a round (one bit per
+    parameter, nothing else) and whose ``rng`` stays ``None``. ``1 <= K <= 4096``. ``template`` (a
+    pytree of the model's leaves) checks the clients' ``shapes``. An empty round returns ``None``
+    and the state unchanged. Not capturable into a graph: the call uploads a pointer table."""
+    mode = C.check_vote_output(output)
+    expect = None if template is None else _template_shapes(template)
+
+    def init():
+        return CompressionState(0.0, None)
+
+    def apply(clients_params_and_weights, aggregator_state):
+        deltas, _ = _consume(clients_params_and_weights)
+        if not deltas:
+            return None, aggregator_state
+        kernels.refuse_capture("majority_vote_aggregator", "it uploads a pointer table through a pinned staging buffer")
+        td, rows, shapes = _sign_rows(deltas, expect)
+        C.check_vote_clients(len(rows))
+        if not rows[0]:
+            return pytree.unflatten(td, []), aggregator_state
+        device = tree_util._find_device(rows[0])
+        rows = [[x.to(device).contiguous() for x in r] for r in rows]
+        outs = [torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes]
+        C.sign_vote(rows, mode, outs)
+        P = sum(x.numel() for x in outs)
+        return pytree.unflatten(td, outs), CompressionState(F32(aggregator_state.num_bits + F32(P)), None)
+
+    return aggregator.Aggregator(init, apply)
+
+
 __all__ = ["CompressionState", "SparsifierState", "top_k_sparsifier", "EncodedDelta", "encoded_mean_aggregator",
            "SparseDelta", "topk_encode_pytree", "sparse_mean_aggregator",
+           "SignDelta", "sign_encode_pytree", "majority_vote_aggregator",
            "uniform_stochastic_encode_pytree", "pack_codes", "unpack_codes", "DriveDelta", "drive_round_keys",
            "drive_encode_pytree", "drive_mean_aggregator",
            "arithmetic_encoding_num_bits", "binary_stochastic_quantize", "drive_pytree",

@@ -17,6 +17,10 @@
  *   fjcomp_wht            walsh_hadamard_transform with the structured_rotation /
  *                         inverse_structured_rotation (and DRIVE) pre/epilogues
  *                         walsh_hadamard.py:25-176, compression.py:269-277
+ *   fjcomp_sign_pack      signSGD's client: one sign bit per coordinate, bit-packed
+ *   fjcomp_sign_vote      signSGD with majority vote (Bernstein et al., ICLR 2019): the sign the
+ *                         majority of the clients sent, or the mean of the signs, from bit-sliced
+ *                         integer counts
  *   fjcomp_random_bits / fjcomp_uniform   jax.random.bits / uniform of one key
  *   fjcomp_normal / fjcomp_normal_from_bits   jax.random.normal of one key; its bits -> z map
  *
@@ -344,6 +348,38 @@ int fjcomp_topk_compact_ptrs(int in_dtype, const float* const* in_ptrs, int64_t 
                              void* ws_dev, int64_t ws_bytes, int flags, void* stream);
 int fjcomp_sparse_fold(const int32_t* const* idx_ptrs, const float* const* val_ptrs, const int64_t* counts, int64_t K,
                        int64_t P, const float* w_dev, float scale, float* out_dev, int flags, void* stream);
+
+/* ---- signSGD with majority vote: one sign bit per coordinate (fjsignvote.hip) ----
+ * A client sends, per leaf of n elements, ceil(n / 8) bytes: coordinate i in byte i / 8 at bit
+ * i % 8, low bit first (the 1-bit packing above), 1 <=> the value is < 0 (+0, -0 and NaN are
+ * sent as 0). The encoder writes the padding bits of a last byte as 0; the server ignores them.
+ *
+ * fjcomp_sign_pack: the client's side. Row r (in_ptrs[r], row_n[r] float32 elements, 0 allowed)
+ * becomes its sign bits at sign_ptrs[r], every byte stored whole by exactly one lane.
+ * block_prefix[R+1] is the running sum of ceil(row_n / FJCOMP_SIGN_PACK_BLOCK), nblocks its last
+ * entry; all tables device. R >= 1.
+ *
+ * fjcomp_sign_vote: the server's side, one launch, integer until the last instruction. With c
+ * the number of the K clients whose bit is 1, per coordinate
+ *   FJCOMP_VOTE_SIGN   out = -1 if 2c > K,  +1 if 2c < K,  +0 if 2c == K
+ *   FJCOMP_VOTE_MEAN   out = fl(f32(K - 2c) * scale)   (the mean of the signs for scale = f32(1 / K))
+ * bit_ptrs[K*L] (client-major, any alignment), leaf_n[L] elements (0 allowed), block_prefix[L+1]
+ * the running sum of ceil(leaf_n / FJCOMP_VOTE_TILE) and nblocks its last entry, out_ptrs[L]
+ * (float32, 4-byte aligned): all device. A workgroup owns FJCOMP_VOTE_TILE coordinates of one
+ * leaf and keeps their counts bit-sliced; the clients are split over its four waves and the
+ * partial counts added as integers, so there are no atomics and two calls give the same bits.
+ * No byte past a packed leaf's last is read and no output past leaf_n is written.
+ * 1 <= K <= FJCOMP_VOTE_MAX_CLIENTS (above: FJAGG_EUNSUPPORTED), L >= 1. */
+#define FJCOMP_VOTE_SIGN 0
+#define FJCOMP_VOTE_MEAN 1
+#define FJCOMP_VOTE_TILE 8192
+#define FJCOMP_VOTE_MAX_CLIENTS 4096
+#define FJCOMP_SIGN_PACK_BLOCK 2048
+int fjcomp_sign_pack(const float* const* in_ptrs, int64_t R, const int64_t* row_n, const int64_t* block_prefix,
+                     int64_t nblocks, uint8_t* const* sign_ptrs, void* stream);
+int fjcomp_sign_vote(const uint8_t* const* bit_ptrs, int64_t K, int64_t L, const int64_t* leaf_n,
+                     const int64_t* block_prefix, int64_t nblocks, int mode, float scale, float* const* out_ptrs,
+                     void* stream);
 
 #ifdef __cplusplus
 }
